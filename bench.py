@@ -14,6 +14,8 @@ collective is the bucketed gradient all-reduce (RCCL over xGMI).
 (and fails loudly when fewer than N GPUs are visible).  --scaling strong keeps the GLOBAL batch fixed (B / N per rank).
 --grad-accum G: one step = one OPTIMIZER step over G micro-batches (the recipe: 4 x 150 s), --accum sequential (G forward +
 backward passes accumulate, the reference's fit_batch) or fused (trainer.fuse_microbatches: ONE batch, same gradients).
+--dump-outputs DIR: after the timed steps, what the last one computed (encoder output; training: also the updated weights and
+the gradients) as DIR/<name>.npy - the inputs are seeded, so two builds of the project compare output for output.
 
 Prints ONE JSON line (rank 0) with the driver contract fields plus
   "roofline":     roofline of the DOMINANT KERNEL of the step: the kernel symbol (template instantiation, as rocprofv3 --stats
@@ -484,6 +486,10 @@ def main():
     ap.add_argument("--roofline-step-only", action="store_true",
                     help="(the extra_points child runs) only roofline_step - the step's algorithmic bytes / flops over the timed step - "
                          "instead of the per-kernel roofline objects")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32; rank 0): the encoder "
+                         "output and, when training, the updated weights and the gradients - at most 60 MiB in all, larger arrays as a "
+                         "fixed sample of their elements (dump_outputs)")
     ap.add_argument("--dry-run-ranks", type=int, default=0, metavar="N",
                     help="no GPU needed: build the model on the CPU, print the N-rank data-parallel plan (gradient buckets in "
                          "launch order, the rs_ag shard map, bytes on the wire, the hipGraph split decision, the RCCL environment) "
@@ -572,6 +578,8 @@ def main():
         parts = [int(x) for x in args.dynchunk.split(",")]
         enc_kw["dynchunktrain_config"] = DynChunkTrainConfig(parts[0], parts[1] if len(parts) > 1 else None)
 
+    latest = {}    # the encoder output of the latest step (--dump-outputs; under a hipGraph: the tensor every replay rewrites)
+
     def fwd_bwd_all():
         # (gradient accumulation: the kernels ADD into the flat gradient buffer; the bucket hooks fire on the last micro-batch only)
         opt.zero_grad()
@@ -579,7 +587,9 @@ def main():
             for s_, wl_, r_, _ in micro[:-1]:
                 enc(s_, wl_, **enc_kw).backward(r_)
         s_, wl_, r_, _ = micro[-1]
-        enc(s_, wl_, **enc_kw).backward(r_)
+        y = enc(s_, wl_, **enc_kw)
+        y.backward(r_)
+        latest["encoder_out"] = y.detach()
 
     def step():
         if train:
@@ -594,7 +604,7 @@ def main():
             opt.step()
         else:
             with torch.no_grad():
-                enc(src, wav_len, **enc_kw)
+                latest["encoder_out"] = enc(src, wav_len, **enc_kw)
 
     def barrier():
         if world > 1 or force_dist:
@@ -680,6 +690,8 @@ def main():
         run()
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:          # (before the roofline's instrumented steps move the weights on)
+        dump_outputs(args.dump_outputs, dict(latest, **({"parameters": opt.flat_p, "gradients": opt.flat_g} if train else {})))
     if world > 1 or force_dist:
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
@@ -775,6 +787,24 @@ def main():
         torch.distributed.destroy_process_group()
 
 
+DUMP_BYTES = 60 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy in float32, DUMP_BYTES in all.  An array over its share keeps a fixed
+    sample of its elements - flat indices drawn by a CPU generator of seed 0, sorted - the same from run to run and build to build,
+    so two dumps of one command compare element for element."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_BYTES // 4 // len(arrays)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > cap:
+            idx = torch.randint(t.numel(), (cap,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+
+
 def F_stream_f32(dtype):
     from summarymixing_amd import functional as F
     return dtype == torch.bfloat16 and F.stream_dtype(dtype) == torch.float32
@@ -826,9 +856,11 @@ def main_stack(args, cfg, dtype, dev, rank, world):
         if sp:
             x, pad = SP.shard(x), SP.shard(pad)
 
+        latest = {}
+
         def step():
             with torch.no_grad():
-                enc(x, src_key_padding_mask=pad)
+                latest["encoder_out"] = enc(x, src_key_padding_mask=pad)[0]
 
         def barrier():
             if world > 1:
@@ -842,6 +874,8 @@ def main_stack(args, cfg, dtype, dev, rank, world):
             step()
         barrier()
         dt = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, latest)
     if world > 1:
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)

@@ -63,3 +63,22 @@ def test_bench_dry_run_ranks_8_prints_the_plan_without_a_gpu():
     assert len(set(d["rs_ag_shard_elements_per_rank"])) == 1 and d["rs_ag_shard_elements_per_rank"][0] * 8 == d["flat_elements"]
     assert sum(b["wire_dtype_bytes"] for b in d["buckets_in_launch_order"]) == 2 * d["flat_elements"]      # bf16 on the wire
     assert d["hipgraph"] is False and "HSA_ENABLE_IPC_MODE_LEGACY" in d["rccl_env"]
+
+
+def test_bench_dump_outputs_keeps_its_budget_and_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: float32 .npy files, at most 64 MB in all; an array over its share of the budget keeps a sample of
+    its elements that is the same on every call, a small one is written whole, in its shape."""
+    import numpy as np
+    import bench
+    big = torch.arange(bench.DUMP_BYTES // 4, dtype=torch.float32)          # element value = flat index
+    small = torch.randn(3, 5).bfloat16()
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"big": big, "small": small})
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["big.npy", "small.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 * 10 ** 6
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float32 and a.size == bench.DUMP_BYTES // 4 // 2 and np.array_equal(a, b)
+    assert (np.diff(a) >= 0).all() and a[0] >= 0 and a[-1] < big.numel() and np.unique(a).size > a.size // 2
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and np.array_equal(s, small.float().numpy())

@@ -191,9 +191,11 @@ with torch.cuda.stream(side):
 torch.cuda.current_stream().wait_stream(side)
 torch.cuda.synchronize()
 ga, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-with torch.cuda.graph(ga):
+# (thread_local, as bench.py: the RCCL watchdog thread may still poll the warm-up all-reduce's event with hipEventQuery - in the
+#  default global capture mode that call from ANOTHER thread fails while a capture is open and the watchdog aborts the process)
+with torch.cuda.graph(ga, capture_error_mode="thread_local"):
     fwd_bwd()
-with torch.cuda.graph(gb):
+with torch.cuda.graph(gb, capture_error_mode="thread_local"):
     opt.update_only()
 for _ in range(2):                                                   # steps 2 and 3 as graph replays
     ga.replay(); opt.all_reduce_all(); gb.replay()
