@@ -279,7 +279,8 @@ int smx_masked_mean_bwd(int dtype, const float* g, const float* inv_count, void*
                         int D, float drop_p, uint64_t drop_seed, const uint64_t* epoch, void* stream);
 
 /* Small batches (round 6): the masked mean over time AND its broadcast in ONE launch, fixed summation order (no atomics), for
- * smx_pool_bcast_ok(B, T, D) shapes (B * T <= 16 384 frames, T <= 4096):
+ * smx_pool_bcast_ok(B, T, D) shapes: T <= 4096 and either B * T <= SMX_POOL_FUSE_MAX_ROWS frames (default 16 384) or at least
+ * 256 (utterance, 64-column group) pairs, B * ceil(D / 64) >= 256 (a large batch of ordinary utterances fills the chip on its own):
  *   sum[b,:] = sum_t S[b,t,:] * mask_in[b,t];  mean_out[b,:] (optional) = sum (* 1 / count[b] when scale_by_count);
  *   inv_out[b] (optional) = 1 / count[b];
  *   dS[b,t,:] (optional) = D( value[b,:] * (inv_in ? inv_in[b] : 1) ) [* act'(Z[b,t,:]) * mask_out[b,t] when Z / mask_out are given]

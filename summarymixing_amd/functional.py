@@ -17,6 +17,7 @@ Reference behaviour mirrored here (paths relative to the reference root):
 """
 import weakref
 
+import collections
 import ctypes
 import os
 
@@ -25,6 +26,42 @@ import torch
 from . import _lib as L
 from . import ops
 from . import sequence_parallel as SP
+
+# ---- A/B knobs: the environment is read here, once; the values stay module attributes read at call time (tests assign them) ----
+# The panel-resident GEMM takes the output-bound Linears with a short reduction (K = 256 / 512: FFN up-projection, the act-grad
+# dgrad of the down-projection, the conv module's pointwise Linear, the cgMLP projections) from this many rows on
+# (tools/experiments/ab_panel_rows.sh: 16 000 rows C2b 8.17 -> 7.83 ms, C2a 16.42 -> 15.81; 8 000 rows a tie; 32 000 rows -3 %).
+_PANEL = os.environ.get("SMX_PANEL", "1") != "0"
+_PANEL_MIN_ROWS = int(os.environ.get("SMX_PANEL_MIN_ROWS", "2048"))   # (round 6: 64- / 32-row panels below 12 288 rows, chosen by the library)
+
+# Split-K over workgroups for the Linears of a SMALL batch (smx_gemm_panel_slabs + smx_slab_epilogue / smx_layernorm_bwd2_slabs; round 6):
+# panel-sized K-slices whose slabs the row kernel that follows the Linear anyway sums (its epilogue + the LayerNorm, or the LayerNorm
+# backward behind a dgrad).  Up to 2048 frames: at 3750 the slab traffic eats the gain (tools/experiments/r06_smalln/README.md, 4.).
+_SPLITK = os.environ.get("SMX_SPLITK", "1") != "0"
+_SPLITK_MAX_ROWS = int(os.environ.get("SMX_SPLITK_MAX_ROWS", "2048"))
+
+# LayerNorms in the GEMM epilogues: SMX_LN_FUSE = 1 (default) both directions, 0 none, "fwd" / "bwd" only the forward (SMX_EPI_LN_FWD)
+# / backward (SMX_EPI_LN_BWD) one (C2b B = 128: 19.79 ms both, 19.90 without the forward, 20.84 without the backward fusion)
+_LN_FUSE, _LN_FUSE_FWD, _LN_FUSE_BWD = (os.environ.get("SMX_LN_FUSE", "1").lower() != off for off in ("0", "bwd", "fwd"))
+# The LayerNorm-fused GEMM runs one row-complete tile per workgroup: below ~280 tiles the grid leaves CUs idle and each workgroup's
+# serial chain (K loop, four epilogue phases) IS the kernel's duration.  Fused from 17 500 rows (was 36 864 before round 6; same-box
+# A/B of the steps: tools/experiments/r06_smalln/README.md - C2b B = 32 (16 000 rows) 7.66 | 8.28 ms separate | fused, B = 36 9.81 | 9.64).
+_LN_FUSE_MIN_ROWS = int(os.environ.get("SMX_LN_FUSE_MIN_ROWS", "17500"))
+# norm2 of a Conformer layer + the first LayerNorm of the next layer in ONE pass over the float32 stream (smx_layernorm_fwd_pair_x32;
+# tests switch it off to compare with the two-launch path)
+_LN_PAIR = True
+
+_POOL_FUSE = os.environ.get("SMX_POOL_FUSE", "1") != "0"   # small batches: smx_pool_bcast instead of masked mean + broadcast (3 launches)
+
+# Residual-stream dtype of a bf16 model.  "fp32" (default) = torch autocast semantics, the reference's `precision: bf16`
+# (…transducer.yaml:61): what a GEMM reads or writes is bf16, the residual adds (Conformer.py:507,530,532-536) and the stream
+# tensors the LayerNorms read are float32.  "bf16" (SMX_RESIDUAL=bf16, the round-1/2 behaviour) stores the stream in bf16 too:
+# ~7 % faster, 2e-2 instead of < 1e-2 max-rel on the 12-layer forward.  Gradients are bf16 in both.
+RESIDUAL_F32 = os.environ.get("SMX_RESIDUAL", "fp32").lower() not in ("bf16", "bfloat16")
+
+_DEFER_REDUCE = os.environ.get("SMX_DEFER_REDUCE", "1") != "0"
+_WGRAD_GROUP = os.environ.get("SMX_WGRAD_GROUP", "1") != "0"
+_WGRAD_DIRECT_MAX_ROWS = int(os.environ.get("SMX_WGRAD_DIRECT_MAX_ROWS", "8192"))
 
 # ----------------------------------------------------------------------------------------------------
 # parameter plumbing: compute-dtype shadows of fp32 master weights, gradient buffers
@@ -163,23 +200,7 @@ def wpacked(param, dtype, transposed=False, bias=None, kslice=0):
     return out
 
 
-# The panel-resident GEMM takes the output-bound Linears with a short reduction (K = 256 / 512: FFN up-projection, the act-grad
-# dgrad of the down-projection, the conv module's pointwise Linear, the cgMLP projections) from this many rows on.  One 128-row
-# panel per CU; below ~190 panels the kernel deals a panel's chunk rounds to 2 or 4 workgroups.  Same-box A/B of the steps
-# (tools/experiments/ab_panel_rows.sh): 16 000 rows C2b 8.17 -> 7.83 ms, C2a 16.42 -> 15.81; 8 000 rows a tie; 32 000 rows -3 %.
-_PANEL = os.environ.get("SMX_PANEL", "1") != "0"
-_PANEL_MIN_ROWS = int(os.environ.get("SMX_PANEL_MIN_ROWS", "2048"))   # (round 6: 64- / 32-row panels below 12 288 rows, chosen by the library)
 _PANEL_ACTS = (L.ACT_NONE, L.ACT_SWISH, L.ACT_GELU, L.ACT_RELU)
-
-
-# Split-K over workgroups for the Linears of a SMALL batch (smx_gemm_panel_slabs + smx_slab_epilogue / smx_layernorm_bwd2_slabs; round 6):
-# the reduction is cut into panel-sized K-slices, the slabs are summed by the row kernel that follows the Linear anyway (its epilogue +
-# the LayerNorm, or the LayerNorm backward behind a dgrad).  Measured (tools/experiments/r06_smalln/splitk_bench.py, us, GEMM + LayerNorm
-# pair, tiled | split-K): d_model 256 at 500 frames K = 1024: 13.2 | 10.2, 512: 10.8 | 9.3, 256: 9.5 | 8.8; 2000 frames: 14.1 | 13.8, 11.6 | 11.2;
-# d_model 512 at 500 frames: 18.4 | 14.3, 13.3 | 12.6; 2000 frames 21.9 | 20.8; at 3750 frames the slab traffic (S x N x M x 4 bytes
-# written and read back) eats the gain (27.5 | 26.1 at K = 2048, a loss below) - hence up to 2048 frames only.
-_SPLITK = os.environ.get("SMX_SPLITK", "1") != "0"
-_SPLITK_MAX_ROWS = int(os.environ.get("SMX_SPLITK_MAX_ROWS", "2048"))
 
 
 def splitk_cfg(N, M, K, dtype):
@@ -197,20 +218,14 @@ def _span_ok(*ts):
     return all(t is None or ((t.shape[0] - 1) * t.stride(0) + t.shape[1]) * t.element_size() < (1 << 31) for t in ts)
 
 
-def panel_ok(x, M, K, act):
-    return (_PANEL and x.dtype == torch.bfloat16 and act in _PANEL_ACTS and x.shape[0] >= _PANEL_MIN_ROWS and _vec_ok(x) and
-            _span_ok(x) and ops.gemm_panel_ok(x, M, K))
+def _panel_ok(a, M, K, act, out, z):
+    """The panel-resident GEMM can run out (N x M; None: a fresh one of a's dtype, whose alignment and span smx_gemm_panel_ok
+    implies) [+ the Z view z] = epi(a W)."""
+    return ((out is None or out.dtype == a.dtype) and _PANEL and a.dtype == torch.bfloat16 and act in _PANEL_ACTS and
+            a.shape[0] >= _PANEL_MIN_ROWS and _vec_ok(a, out, z) and _span_ok(a, out, z) and ops.gemm_panel_ok(a, M, K))
 
 
-_POOL_FUSE = os.environ.get("SMX_POOL_FUSE", "1") != "0"   # small batches: smx_pool_bcast instead of masked mean + broadcast (3 launches)
 _WGRAD_BIAS = True   # (round 4: the SMX_NO_WGRAD_BIAS A/B knob is gone)     # A/B knob: bias gradients as a by-product of the wgrad GEMM
-
-# Residual-stream dtype of a bf16 model.  "fp32" (default) = torch autocast semantics, what the reference's `precision: bf16`
-# means (…transducer.yaml:61): Linear inputs / outputs in bf16, the residual adds (Conformer.py:507,530,532-536) and the
-# LayerNorm inputs in float32 - the stream tensors x, x + 1/2 FFN, + cell, + conv, and the layer-final LayerNorm output are
-# stored in float32, everything a GEMM reads or writes stays bf16.  "bf16" (SMX_RESIDUAL=bf16, the round-1/2 behaviour) stores
-# the stream in bf16 too: ~7 % faster, 2e-2 instead of < 1e-2 max-rel on the 12-layer forward.  Gradients are bf16 in both.
-RESIDUAL_F32 = os.environ.get("SMX_RESIDUAL", "fp32").lower() not in ("bf16", "bfloat16")
 
 
 def stream_dtype(compute_dtype):
@@ -244,21 +259,21 @@ def mask_u8(mask, B, T, device):
 # device (workspace and gradient addresses are stable), so steady-state steps - and hipGraph capture - copy nothing.
 # ----------------------------------------------------------------------------------------------------
 class _Deferred:
-    enabled = os.environ.get("SMX_DEFER_REDUCE", "1") != "0"
+    enabled = _DEFER_REDUCE           # (the knobs: top of the file)
     jobs = []        # (src_ptr, dst_ptr, src_stride, ldd, nsrc, rows, cols, alpha)
     pending = set()  # workspace keys written since the last flush
     ws = {}          # key -> persistent uint8 workspace
     cache = {}       # tuple(jobs) -> (jobs_dev, starts_dev, njobs, total_blocks)
     # grouped wgrad: the bf16 weight gradients of a block (= encoder layer) whose dims are multiples of 256 are recorded
     # and computed by ONE smx_wgrad_group launch at the end of the block's backward (SMX_WGRAD_GROUP=0: one slab GEMM each)
-    group_enabled = os.environ.get("SMX_WGRAD_GROUP", "1") != "0"
+    group_enabled = _WGRAD_GROUP
     group = []       # (dz, x, gW, dbias, N, M, K)
     # (from the kernel's minimum of 64 frames: below 2048 the eight slab GEMMs + reductions it replaces are eight latency-bound
     #  launches - C2b training step at B = 1 x 500: 5.36 -> 4.00 ms, C2a at 2 x 375: 7.11 -> 5.43 ms)
     group_min_rows = 64
     # up to this many frames the grouped wgrad runs WITHOUT split-K slabs (smx_wgrad_group_direct: 128 x 128 tiles over all the frames,
     # added into the gradients; SMX_WGRAD_DIRECT_MAX_ROWS=0 switches it off): measured in tools/experiments/r06_smalln/wgrad_direct_bench.py
-    group_direct_max_rows = int(os.environ.get("SMX_WGRAD_DIRECT_MAX_ROWS", "8192"))
+    group_direct_max_rows = _WGRAD_DIRECT_MAX_ROWS
 
 
 def _evict_workspaces():
@@ -413,36 +428,47 @@ def _vec_ok(*ts):
     return all(t is None or (t.data_ptr() % 16 == 0 and (t.stride(0) * t.element_size()) % 16 == 0) for t in ts)
 
 
-# SMX_LN_FUSE = 1 (default) both directions, 0 none, "fwd" / "bwd": only the forward (SMX_EPI_LN_FWD) / only the backward (SMX_EPI_LN_BWD)
-# fusion (C2b B = 128: 19.79 both, 19.90 without the forward, 20.84 without the backward one)
-_LN_FUSE_FWD = os.environ.get("SMX_LN_FUSE", "1").lower() != "bwd"
-_LN_FUSE_BWD = os.environ.get("SMX_LN_FUSE", "1").lower() != "fwd"
+def _splitk_open(x, M, wparam, c0, out, z, res, drop_cols):
+    """splitk_cfg, when the reducer (smx_slab_epilogue) can apply this Linear's epilogue too; else None."""
+    sk = splitk_cfg(x.shape[0], M, x.shape[1], x.dtype) if (wparam is not None and c0 is None and drop_cols % 4 == 0) else None
+    return sk if (sk is not None and _vec_ok(x, out, z, res) and out.stride(0) % 4 == 0 and (res is None or res.stride(0) % 4 == 0)) else None
 
 
-def ln_next_ok(x, M, ln_next, W=None, res=None, training=True, wparam=None):
-    """Can - and should - the LayerNorm that follows a Linear (its output: N x M) ride in that GEMM's epilogue (SMX_EPI_LN_FWD)?
-    W / res: the weight (view) and residual the GEMM will be given - a column slice with an odd offset is not 16-byte aligned
-    and the fused instantiation has no scalar path.
-    training: at M = 512 the row-complete tile is ONE workgroup per CU, whose epilogue nothing overlaps; in a training step the
-    fusion still wins (C2a 49.2 -> 48.4 ms, each direction ~0.75 ms), in a forward-only pass the standalone LayerNorm (a pure
-    stream at 5.9 TB/s, paired with the next layer's) is faster (C5 forward 60.2 vs 62.0 ms fused, C2a forward 16.97 vs 17.25;
-    tools/experiments/ab_lnfuse_d512.sh): not fused there."""
-    if (wparam is not None and ln_next is not None and _LN_FUSE and _LN_FUSE_FWD and x.dtype == torch.bfloat16 and _vec_ok(x, res) and
-            splitk_cfg(x.shape[0], M, x.shape[1], x.dtype) is not None):
-        return True                                        # small batch: split-K slabs, the LayerNorm rides in the reducer (linear_fwd)
-    if M > 256 and not training:
-        return False
-    return (_LN_FUSE and _LN_FUSE_FWD and ln_next is not None and x.dtype == torch.bfloat16 and x.shape[0] >= _LN_FUSE_MIN_ROWS and _vec_ok(x, W, res) and
-            L.lib().smx_gemm_ln_fused_ok(L.BF16, x.shape[0], M, x.shape[1]) == 1)
+# The LayerNorm after a Linear (linear_fwd(ln_next=...)).  want_stats: a backward will run (training).  stream_out: its output is the
+# residual stream (norm2): stream dtype, else x.dtype.  pair = (gamma2, beta2, eps2): a second LayerNorm of its output (the next layer's).
+LnNext = collections.namedtuple("LnNext", "gamma beta eps want_stats stream_out pair", defaults=(False, None))
+
+
+def _fwd_route(x, M, W, wparam, act, res, c0, out, out_f32, z, drop_cols, ln):
+    """linear_fwd's kernel route: (route, LayerNorm fused, pair fused, splitk_cfg | None).  "slabs": split-K slices summed by
+    smx_slab_epilogue; "tiled": the tiled GEMM, LayerNorm(s) in its row-complete epilogue; "panel": the panel-resident GEMM.  A
+    LayerNorm that cannot ride along is left to the caller, the route chosen as if none was requested.  The tile needs W aligned
+    too; at M = 512 it fuses in training only (C2a step 49.2 -> 48.4 ms, C5 forward 60.2 vs 62.0 ms fused)."""
+    N, K = x.shape
+    want = ln is not None and _LN_FUSE and _LN_FUSE_FWD and x.dtype == torch.bfloat16
+    sk = _splitk_open(x, M, wparam, c0, out, z, res, drop_cols) if want else None
+    if want and (sk is not None or ((M <= 256 or ln.want_stats) and N >= _LN_FUSE_MIN_ROWS and _vec_ok(x, W, res) and
+                                    L.lib().smx_gemm_ln_fused_ok(L.BF16, N, M, K) == 1)):
+        # the second LayerNorm: the split-K reducer holds the row in registers; the tile needs smx_gemm_ln_pair_ok (128 x 512)
+        pair = (ln.pair is not None and _LN_PAIR and res is not None and res.dtype == torch.float32 and
+                (sk is not None or L.lib().smx_gemm_ln_pair_ok(L.BF16, N, M, K) == 1) and
+                all(v.is_contiguous() and v.data_ptr() % 16 == 0 for v in ln.pair[:2]))
+        return ("tiled" if sk is None else "slabs"), True, pair, sk
+    if wparam is not None and res is None and c0 is None and not out_f32 and drop_cols % 64 == 0 and _panel_ok(x, M, K, act, out, z):
+        return "panel", False, False, None
+    if not want:
+        sk = _splitk_open(x, M, wparam, c0, out, z, res, drop_cols)
+    if sk is not None and sk[1] > 1:       # (one slice and no LayerNorm to absorb: the reducer would be a launch more, not less)
+        return "slabs", False, False, sk
+    return "tiled", False, False, None
 
 
 def linear_fwd(x, W, bias=None, act=L.ACT_NONE, mask=None, res=None, alpha=1.0, c0=None, c0_mode=L.C0_NONE,
                c0_div=0, save_z=False, out=None, out_f32=False, drop=None, c0_post=False, ln_next=None, ln_post=None,
                drop_cols=0, wparam=None):
-    """ln_next = (gamma, beta, eps, act, want_stats[, stream_out[, pair]]): the LayerNorm that follows this Linear runs in the GEMM
-    epilogue (check ln_next_ok first); ln_post (a list) receives (LN output, stats | None).  pair = (gamma2, beta2, eps2): a second
-    LayerNorm of the first one's output in the same epilogue (check ln_pair_ok); ln_post then receives a second entry,
-    (LN2 output in x.dtype, stats2 | None)."""
+    """ln_next (LnNext): the LayerNorm after this Linear, fused where the route allows (_fwd_route); ln_post (a list) then receives
+    (LN output, stats | None) [and (LN2 output in x.dtype, stats2 | None) for ln_next.pair], else stays empty.  wparam = the fp32
+    parameter behind W: the panel and split-K routes run on its packed image."""
     N, K = x.shape
     M = W.shape[0]
     if res is not None and res.dtype == torch.float32 and x.dtype != torch.float32:
@@ -450,56 +476,33 @@ def linear_fwd(x, W, bias=None, act=L.ACT_NONE, mask=None, res=None, alpha=1.0, 
     if out is None:
         out = torch.empty((N, M), dtype=torch.float32 if out_f32 else x.dtype, device=x.device)
     z = torch.empty((N, M), dtype=x.dtype, device=x.device) if (save_z and act != L.ACT_NONE) else None
-    # wparam = the fp32 parameter behind W: bias / activation / saved Z / dropout only -> the panel-resident kernel on its packed image
-    if (wparam is not None and res is None and c0 is None and not out_f32 and ln_next is None and
-            drop_cols % 64 == 0 and out.dtype == x.dtype and panel_ok(x, M, K, act) and _vec_ok(out, z) and _span_ok(out, z)):
+    route, ln_fused, pair_fused, sk = _fwd_route(x, M, W, wparam, act, res, c0, out, out_f32, z, drop_cols, ln_next)
+    if route == "panel":
         ops.gemm_panel(x, wpacked(wparam, x.dtype, False, bias), out, N, M, K,
                        ops.epilogue(act=act, z=z, drop=drop, row_mask=mask, alpha=alpha, drop_cols=drop_cols))
         return out, z
     lnf = lnf2 = None
-    if ln_next is not None:
-        g, b, eps, lact, want_stats = ln_next[:5]
-        # ln_next[5] = True: the LayerNorm output is itself the stream (the layer-final norm2): stream dtype, else GEMM input dtype
-        hy = torch.empty((N, M), dtype=out.dtype if (len(ln_next) > 5 and ln_next[5]) else x.dtype, device=x.device)
-        st = torch.empty((N, 2), dtype=torch.float32, device=x.device) if want_stats else None
-        lnf = (g.detach(), b.detach(), hy, st, eps, lact)
+    if ln_fused:
+        hy = torch.empty((N, M), dtype=out.dtype if ln_next.stream_out else x.dtype, device=x.device)
+        st = torch.empty((N, 2), dtype=torch.float32, device=x.device) if ln_next.want_stats else None
+        lnf = (ln_next.gamma.detach(), ln_next.beta.detach(), hy, st, ln_next.eps, L.ACT_NONE)
         ln_post.append((hy, st))
-        if len(ln_next) > 6 and ln_next[6] is not None:
-            g2, b2, eps2 = ln_next[6]
+        if pair_fused:
             hy2 = torch.empty((N, M), dtype=x.dtype, device=x.device)
-            st2 = torch.empty((N, 2), dtype=torch.float32, device=x.device) if want_stats else None
-            lnf2 = (g2.detach(), b2.detach(), hy2, st2, eps2)
+            st2 = torch.empty((N, 2), dtype=torch.float32, device=x.device) if ln_next.want_stats else None
+            lnf2 = (ln_next.pair[0].detach(), ln_next.pair[1].detach(), hy2, st2, ln_next.pair[2])
             ln_post.append((hy2, st2))
     e = ops.epilogue(bias=bias, c0=c0, c0_mode=c0_mode, c0_div=c0_div, act=act, z=z, row_mask=mask, res=res,
                      alpha=alpha, out_mode=L.OUT_F32 if out_f32 else L.OUT_T, drop=drop, c0_post=c0_post, ln_fwd=lnf,
                      drop_cols=drop_cols, ln_fwd2=lnf2)
-    sk = splitk_cfg(N, M, K, x.dtype) if (wparam is not None and c0 is None and drop_cols % 4 == 0) else None
-    if sk is not None and sk[1] == 1 and ln_next is None:
-        sk = None                                          # (one slice and no LayerNorm to absorb: the reducer would be a launch more, not less)
-    if sk is not None and _vec_ok(x, out, z, res) and out.stride(0) % 4 == 0 and (res is None or res.stride(0) % 4 == 0):
+    if route == "slabs":
         # small batch: K-slices on the panel kernel -> float32 slabs; the reducer applies this epilogue (and the LayerNorms) to their sum
         slabs = torch.empty((sk[1], N, M), dtype=torch.float32, device=x.device)
         ops.gemm_panel_slabs(x, wpacked(wparam, x.dtype, False, None, kslice=sk[0]), slabs, N, M, sk[0], sk[1])
         ops.slab_epilogue(slabs, sk[1], out, N, M, e)
         return out, z
-    assert ln_next is None or L.lib().smx_gemm_ln_fused_ok(L.BF16, N, M, K) == 1, "ln_next given for a shape only the split-K path fuses"
     ops.gemm(L.GEMM_NT, x, W, out, N, M, K, e)
     return out, z
-
-
-_LN_FUSE = os.environ.get("SMX_LN_FUSE", "1") != "0"   # A/B knob: LayerNorm backward / forward inside the GEMM epilogues
-# The LayerNorm-fused GEMM runs one 128-row tile per workgroup (the tile holds whole rows): below ~280 tiles the grid leaves
-# CUs idle and each workgroup's serial chain (K loop, four epilogue phases) IS the kernel's duration - 64 us at 16 000 frames
-# against 76 us at 64 000.  Measured on the C2b step (fused / separate kernels, ms): B = 16: 8.30 / 5.97, 32: 9.77 / 8.15,
-# 48: 11.33 / 10.63, 64: 12.97 / 12.56, 80: 15.20 / 15.74, 96: 16.52 / 17.49, 128: 19.11 / 20.24 -> fuse from 36 864 rows.
-# Round 6, re-measured on the round-5/6 kernels (one-pass LayerNorm epilogue, DPP row sums; tools/experiments/r06_smalln/ab_lnfuse_mid*.sh,
-# same box, separate | fused, ms): C2b B = 32 (16 000 rows) 7.66 | 8.28, B = 36 9.81 | 9.64, 40: 10.13 | 9.91, 48: 10.66 | 10.45, 56: 11.34 | 10.99,
-# 64: 12.00 | 11.53; C2a (d_model 512) B = 32 15.87 | 17.13, 40: 20.70 | 20.55, 48: 22.26 | 21.91, 56: 24.79 | 23.49, 64: 26.85 | 25.31; the recipe's
-# 4 fused micro-batches (15 000 rows) 15.40 | 16.73; C4 at 16 000 / 24 000 rows: ties -> fuse from 17 500 rows (was 36 864).
-_LN_FUSE_MIN_ROWS = int(os.environ.get("SMX_LN_FUSE_MIN_ROWS", "17500"))
-# norm2 of a Conformer layer + the first LayerNorm of the next layer in ONE pass over the float32 stream (smx_layernorm_fwd_pair_x32;
-# tests switch it off to compare with the two-launch path)
-_LN_PAIR = True
 
 
 def ln_fusable(ln_spec, N, K_out, dtype, reduce, W=None):
@@ -514,6 +517,25 @@ def ln_fusable(ln_spec, N, K_out, dtype, reduce, W=None):
             and L.lib().smx_gemm_ln_fused_ok(L.BF16, N, K_out, reduce) == 1 and _vec_ok(x, W))
 
 
+def _dgrad_route(dz, K, wparam, up, dx_drop, res_grad, dx_out, ln, dx_split, slabs_ok):
+    """linear_bwd's dgrad route: (route, splitk_cfg | None).  "split": a tiled GEMM per dx_split range; "slabs": float32 split-K
+    slabs (slabs_ok: the consumer sums them); "ln": the LayerNorm backward in the tiled epilogue (ln: found ln_fusable); "panel":
+    the panel-resident kernel, W packed transposed (plain, dropout or upstream act-grad epilogue); "tiled": the tiled GEMM."""
+    if dx_split is not None:
+        return "split", None
+    N, M = dz.shape
+    sk = (splitk_cfg(N, K, M, dz.dtype) if (slabs_ok and wparam is not None and ln is None and up is None and dx_drop is None and
+                                            res_grad is None and dx_out is None and _vec_ok(dz)) else None)
+    if sk is not None:
+        return "slabs", sk
+    if ln is not None:
+        return "ln", None
+    z_up, act_up, gb_up = (up[0], up[1], up[5]) if up is not None else (None, L.ACT_NONE, None)
+    if wparam is not None and res_grad is None and gb_up is None and _panel_ok(dz, K, M, act_up, dx_out, z_up):
+        return "panel", None
+    return "tiled", None
+
+
 def linear_bwd(dy, x, W, z, act, mask, alpha, gW, gb, need_dx=True, res_grad=None, dgroup=None, gdiv=0, dx_out=None,
                drop=None, dz_ready=False, up=None, dx_drop=None, ln=None, ln_second=None, dx_split=None, wparam=None, slabs_ok=False):
     """Backward of y = res + alpha*D(act(x W^T + b + c0))*mask (D = the forward's fused dropout, regenerated from its
@@ -525,8 +547,8 @@ def linear_bwd(dy, x, W, z, act, mask, alpha, gW, gb, need_dx=True, res_grad=Non
     the upstream layer's own wgrad yields its bias gradient).
     dx_drop = (p, seed): x is the output of a dropout of that seed; its backward rides in the dgrad epilogue.
     ln = the `.spec` of a LayerNorm backward closure whose OUTPUT is x (x = LN(ln["x"])): the dgrad epilogue then runs that
-    LayerNorm backward (SMX_EPI_LN_BWD; check ln_fusable first): returns the gradient w.r.t. ln["x"] (+ res_grad), and,
-    with ln_second = (alpha, mask, drop), the pair (dx, alpha * D(dx) * mask).
+    LayerNorm backward (SMX_EPI_LN_BWD; check ln_fusable first - dgrad_ln_bwd does): returns the gradient w.r.t. ln["x"]
+    (+ res_grad), and, with ln_second = (alpha, mask, drop), the pair (dx, alpha * D(dx) * mask).  slabs_ok: dx may be ops.Slabs.
     dx_split = [(lo, hi, epilogue kwargs | None), ...]: x is a concatenation whose column ranges go to different consumers;
     the dgrad then runs as one GEMM per range over the column slice W[:, lo:hi], each with the first elementwise step of ITS
     consumer in the epilogue (dropout backward, an activation gradient: ops.epilogue keywords); returns the list of outputs."""
@@ -547,58 +569,61 @@ def linear_bwd(dy, x, W, z, act, mask, alpha, gW, gb, need_dx=True, res_grad=Non
         ops.act_mask_bwd(dy, z, mask, act, alpha, dz, gb_pass, dgroup, gdiv, drop)
     if gW is not None:
         _wgrad(dz, x, gW, N, M, K, gb if wb else None)
-    dx = None
-    if need_dx:
-        if dx_split is not None:
-            assert ln is None and up is None and dx_drop is None and res_grad is None and dx_out is None
-            outs = []
-            for lo, hi, ekw in dx_split:
-                o = torch.empty((N, hi - lo), dtype=dy.dtype, device=dy.device)
-                ops.gemm(L.GEMM_NN, dz, W[:, lo:hi], o, N, hi - lo, M, ops.epilogue(**ekw) if ekw else None)
-                outs.append(o)
-            return outs, dz
-        if (slabs_ok and wparam is not None and ln is None and up is None and dx_drop is None and res_grad is None and dx_out is None and
-                _vec_ok(dz) and splitk_cfg(N, K, M, dz.dtype) is not None):
-            # small batch, the caller's next step is a LayerNorm backward: the dgrad as float32 split-K slabs, summed inside that kernel
-            ks, ns = splitk_cfg(N, K, M, dz.dtype)
-            slabs = torch.empty((ns, N, K), dtype=torch.float32, device=dy.device)
-            ops.gemm_panel_slabs(dz, wpacked(wparam, dz.dtype, True, None, kslice=ks), slabs, N, K, ks, ns)
-            return ops.Slabs(slabs), dz
-        dx = dx_out if dx_out is not None else torch.empty((N, K), dtype=dy.dtype, device=dy.device)
-        if ln is not None:
-            assert up is None and dx_drop is None and K % 64 == 0
-            gw_ln, gb_ln = gacc(ln["gw_param"]).view(-1), gacc(ln["gb_param"]).view(-1)
-            tr = L.lib().smx_gemm_ln_tile_rows_for(N, K)      # rows per LayerNorm-fused tile = per partial row pair (64 or 128)
-            ntile = (N + tr - 1) // tr
-            ws = deferred_ws(gw_ln.data_ptr(), ntile * 2 * K * 4, dy.device)
-            dx2 = torch.empty((N, K), dtype=dy.dtype, device=dy.device) if ln_second is not None else None
-            lact = (ln["b"].detach(), ln["act"]) if ln["act"] != L.ACT_NONE else None
-            e = ops.epilogue(res=res_grad, ln_bwd=(ln["x"], ln["stats"], ln["w"].detach(), ws, dx2, ln_second, lact,
-                                                   ln["x"].dtype != dy.dtype))
-            ops.gemm(L.GEMM_NN, dz, W, dx, N, K, M, e)
-            defer(ws.data_ptr(), gw_ln, 2 * K, ntile, 1, K)
-            defer(ws.data_ptr() + 4 * K, gb_ln, 2 * K, ntile, 1, K)
-            return ((dx, dx2) if ln_second is not None else dx), dz
-        if up is not None:
-            assert res_grad is None
-            z_up, act_up, mask_up, alpha_up, drop_up, gb_up = up
-            # wparam = the fp32 parameter behind W (M, K): the act-grad dgrad on the panel-resident kernel, W packed transposed
-            if (wparam is not None and gb_up is None and dx.dtype == dz.dtype and panel_ok(dz, K, M, act_up) and _vec_ok(dx, z_up) and
-                    _span_ok(dx, z_up)):
-                ops.gemm_panel(dz, wpacked(wparam, dz.dtype, True), dx, N, K, M,
-                               ops.epilogue(act=act_up, act_grad_z=z_up, drop=drop_up, row_mask=mask_up, alpha=alpha_up))
-                return dx, dz
-            e = ops.epilogue(act=act_up, act_grad_z=z_up, row_mask=mask_up, alpha=alpha_up, drop=drop_up, colsum=gb_up)
-        else:
-            assert dx_drop is None or res_grad is None
-            # plain (or dropout-backward) dgrad with a short reduction and a wide output: the panel-resident kernel, W packed transposed
-            if (wparam is not None and res_grad is None and dx.dtype == dz.dtype and panel_ok(dz, K, M, L.ACT_NONE) and _vec_ok(dx) and
-                    _span_ok(dx)):
-                ops.gemm_panel(dz, wpacked(wparam, dz.dtype, True), dx, N, K, M, ops.epilogue(drop=dx_drop))
-                return dx, dz
-            e = ops.epilogue(res=res_grad, drop=dx_drop)
+    if not need_dx:
+        return None, dz
+    route, sk = _dgrad_route(dz, K, wparam, up, dx_drop, res_grad, dx_out, ln, dx_split, slabs_ok)
+    if route == "split":
+        assert ln is None and up is None and dx_drop is None and res_grad is None and dx_out is None
+        outs = []
+        for lo, hi, ekw in dx_split:
+            o = torch.empty((N, hi - lo), dtype=dy.dtype, device=dy.device)
+            ops.gemm(L.GEMM_NN, dz, W[:, lo:hi], o, N, hi - lo, M, ops.epilogue(**ekw) if ekw else None)
+            outs.append(o)
+        return outs, dz
+    if route == "slabs":
+        # small batch, the caller's next step is a LayerNorm backward: the dgrad as float32 split-K slabs, summed inside that kernel
+        ks, ns = sk
+        slabs = torch.empty((ns, N, K), dtype=torch.float32, device=dy.device)
+        ops.gemm_panel_slabs(dz, wpacked(wparam, dz.dtype, True, None, kslice=ks), slabs, N, K, ks, ns)
+        return ops.Slabs(slabs), dz
+    dx = dx_out if dx_out is not None else torch.empty((N, K), dtype=dy.dtype, device=dy.device)
+    if route == "ln":
+        assert up is None and dx_drop is None and K % 64 == 0
+        gw_ln, gb_ln = gacc(ln["gw_param"]).view(-1), gacc(ln["gb_param"]).view(-1)
+        tr = L.lib().smx_gemm_ln_tile_rows_for(N, K)      # rows per LayerNorm-fused tile = per partial row pair (64 or 128)
+        ntile = (N + tr - 1) // tr
+        ws = deferred_ws(gw_ln.data_ptr(), ntile * 2 * K * 4, dy.device)
+        dx2 = torch.empty((N, K), dtype=dy.dtype, device=dy.device) if ln_second is not None else None
+        lact = (ln["b"].detach(), ln["act"]) if ln["act"] != L.ACT_NONE else None
+        e = ops.epilogue(res=res_grad, ln_bwd=(ln["x"], ln["stats"], ln["w"].detach(), ws, dx2, ln_second, lact,
+                                               ln["x"].dtype != dy.dtype))
+        ops.gemm(L.GEMM_NN, dz, W, dx, N, K, M, e)
+        defer(ws.data_ptr(), gw_ln, 2 * K, ntile, 1, K)
+        defer(ws.data_ptr() + 4 * K, gb_ln, 2 * K, ntile, 1, K)
+        return ((dx, dx2) if ln_second is not None else dx), dz
+    assert res_grad is None or (up is None and dx_drop is None)
+    e = (ops.epilogue(act=up[1], act_grad_z=up[0], row_mask=up[2], alpha=up[3], drop=up[4], colsum=up[5]) if up is not None else
+         ops.epilogue(res=res_grad, drop=dx_drop))
+    if route == "panel":
+        ops.gemm_panel(dz, wpacked(wparam, dz.dtype, True), dx, N, K, M, e)
+    else:
         ops.gemm(L.GEMM_NN, dz, W, dx, N, K, M, e)
     return dx, dz
+
+
+def dgrad_ln_bwd(ln_b, dy, x, W, wparam, bparam, z=None, act=L.ACT_NONE, mask=None, alpha=1.0, res=None, second=None,
+                 packed=True, **kw):
+    """linear_bwd of x = LN(x0) carried on through that LayerNorm (ln_b: its backward closure): ln_b(dx, res=, second=).  The
+    LayerNorm backward rides in the dgrad epilogue where ln_fusable, else follows the dgrad (split-K slabs / panel kernel on
+    wparam's image when `packed`).  wparam / bparam: the Linear's parameters (gradients taken after ln_fusable's)."""
+    fused = ln_fusable(ln_b.spec, x.shape[0], x.shape[1], W.dtype, W.shape[0], W)
+    gW, gb = gacc(wparam), gacc(bparam)
+    if gW is not None and gW.dim() != 2:
+        gW = gW.view(W.shape)                              # (a Conv1d(k = 1) weight (out, in, 1) seen as a Linear's)
+    if fused:
+        return linear_bwd(dy, x, W, z, act, mask, alpha, gW, gb, res_grad=res, ln=ln_b.spec, ln_second=second, **kw)[0]
+    dx, _ = linear_bwd(dy, x, W, z, act, mask, alpha, gW, gb, wparam=wparam if packed else None, slabs_ok=packed, **kw)
+    return ln_b(dx, res=res, second=second)
 
 
 # ----------------------------------------------------------------------------------------------------
@@ -933,6 +958,7 @@ def cell_run(P, cfg, B, T, mask, sum_mask, p_drop=0.0):
         lw = local.shape[1]
         Wl, Ws = Wm[:, :lw], Wm[:, lw:]
         post = []
+        lnn = None if ln_next is None else LnNext(ln_next[0], ln_next[1], ln_next[2], need_bwd)
         if p_drop > 0.0:
             # training: dropout acts on cat[local, repeat(sbar)] per FRAME (summary_mixing.py:237-239,282-284), which
             # breaks the per-utterance factorisation -> materialise the dropped concatenation once and run K = l + s
@@ -951,13 +977,11 @@ def cell_run(P, cfg, B, T, mask, sum_mask, p_drop=0.0):
             else:
                 ops.dropout(sbar, p_drop, s2, out=cat[:, lw:])
             sbar_t = None
-            lnn = (ln_next[0], ln_next[1], ln_next[2], L.ACT_NONE, need_bwd) if (ln_next is not None and ln_next_ok(cat, Wm.shape[0], ln_next, Wm, res, need_bwd, wparam=mg["W"])) else None
             y, zm = linear_fwd(cat, Wm, mg["b"], act, None, res=res, save_z=need_bwd, ln_next=lnn, ln_post=post, out=out,
                                drop=out_drop, wparam=mg["W"])
         elif pool_kind == "mean":
             sbar_t = ops.cast(sbar, dtype)                                         # (B, sdim) in compute dtype
             c0, _ = linear_fwd(sbar_t, Ws, None, out_f32=True)                     # (B, s_out) fp32
-            lnn = (ln_next[0], ln_next[1], ln_next[2], L.ACT_NONE, need_bwd) if (ln_next is not None and ln_next_ok(local, Wl.shape[0], ln_next, Wl, res, need_bwd)) else None
             y, zm = linear_fwd(local, Wl, mg["b"], act, None, res=res, c0=c0, c0_mode=L.C0_GROUP, c0_div=T,
                                save_z=need_bwd, ln_next=lnn, ln_post=post, out=out, drop=out_drop)
         else:
@@ -1193,17 +1217,6 @@ def dwconv_bwd_deferred(dy, p_, wd, bd, gwd, gbd, B, T, D, k, glu, pad_mode, chu
     return dp, dg
 
 
-def ln_pair_ok(x, M, res, affine, wparam=None):
-    """Can the epilogue that runs a LayerNorm behind this Linear (ln_next_ok holds) also run a SECOND LayerNorm on its output
-    (smx_gemm_ln_pair_ok: the 128 x 512 tile, float32 residual stream)?"""
-    if (wparam is not None and _LN_PAIR and res is not None and res.dtype == torch.float32 and x.dtype == torch.bfloat16 and
-            splitk_cfg(x.shape[0], M, x.shape[1], x.dtype) is not None and all(v.is_contiguous() and v.data_ptr() % 16 == 0 for v in affine)):
-        return True                                        # (the split-K reducer runs both LayerNorms on the row in registers)
-    return (_LN_PAIR and res is not None and res.dtype == torch.float32 and x.dtype == torch.bfloat16 and
-            L.lib().smx_gemm_ln_pair_ok(L.BF16, x.shape[0], M, x.shape[1]) == 1 and
-            all(v.is_contiguous() and v.data_ptr() % 16 == 0 for v in affine))
-
-
 def ffn_module_fwd(x, P, act, need_bwd, dtype, alpha=0.5, p=0.0, pre_ln=None, ln_next=None, ln_pair=None):
     """y = x + alpha * D2(W2 D1(act(W1 LN(x) + b1)) + b2)   (Conformer.py:458-472,507,536; D = dropout, p = 0 in eval).
     With p == 0 the second Linear's epilogue carries the residual and alpha (no extra pass).
@@ -1217,9 +1230,8 @@ def ffn_module_fwd(x, P, act, need_bwd, dtype, alpha=0.5, p=0.0, pre_ln=None, ln
     d2 = (p, ops.new_dropout_seed()) if p > 0.0 else None
     a, z1 = linear_fwd(h, W1, P["b1"], act, None, save_z=need_bwd, drop=d1, wparam=P["W1"])
     post = []
-    lnn = ((ln_next[0], ln_next[1], ln_next[2], L.ACT_NONE, need_bwd) + tuple(ln_next[3:4])) if (ln_next is not None and ln_next_ok(a, W2.shape[0], ln_next, W2, x, need_bwd, wparam=P["W2"])) else None
-    if lnn is not None and ln_pair and len(lnn) > 5 and ln_pair_ok(a, W2.shape[0], x, ln_pair[:2], wparam=P["W2"]):
-        lnn = lnn + (ln_pair,)
+    lnn = None if ln_next is None else LnNext(ln_next[0], ln_next[1], ln_next[2], need_bwd, len(ln_next) > 3 and ln_next[3],
+                                             ln_pair if (ln_pair and len(ln_next) > 3) else None)
     y, _ = linear_fwd(a, W2, P["b2"], L.ACT_NONE, None, res=x, alpha=alpha, drop=d2, ln_next=lnn, ln_post=post, wparam=P["W2"])
     post, post2 = (post[0] if post else None), (post[1] if len(post) > 1 else None)
     ret = lambda b: ((y, b, post, post2) if ln_pair is not None else (y, b, post)) if ln_next is not None else (y, b)
@@ -1236,12 +1248,7 @@ def ffn_module_fwd(x, P, act, need_bwd, dtype, alpha=0.5, p=0.0, pre_ln=None, ln
         else:
             dz1, _ = linear_bwd(dy, a, W2, None, L.ACT_NONE, None, alpha, gacc(P["W2"]), gacc(P["b2"]), drop=d2,
                                 up=(z1, act, None, 1.0, d1, None), wparam=P["W2"])
-        if ln_fusable(ln_b.spec, h.shape[0], h.shape[1], dtype, W1.shape[0], W1):     # the LayerNorm backward rides in the dgrad epilogue
-            out, _ = linear_bwd(dz1, h, W1, z1, act, None, 1.0, gacc(P["W1"]), gacc(P["b1"]), dz_ready=True, res_grad=dy,
-                                ln=ln_b.spec, ln_second=second)
-            return out
-        dh, _ = linear_bwd(dz1, h, W1, z1, act, None, 1.0, gacc(P["W1"]), gacc(P["b1"]), dz_ready=True, wparam=P["W1"], slabs_ok=True)
-        return ln_b(dh, res=dy, second=second)
+        return dgrad_ln_bwd(ln_b, dz1, h, W1, P["W1"], P["b1"], z1, act, res=dy, second=second, dz_ready=True)
     bwd.pre = (alpha, None, d2)          # what this block does first to its incoming gradient: alpha * D2(dy)
     return ret(bwd)
 
@@ -1263,29 +1270,19 @@ def conv_module_fwd(x, P, act, mask, B, T, need_bwd, dtype, chunk=0, residual=Tr
     Wo = wcast(P["Wo"], dtype)
     dr = (p, ops.new_dropout_seed()) if p > 0.0 else None   # Linear -> Dropout -> * mask (+ x): one epilogue
     post = []
-    lnn = (ln_next[0], ln_next[1], ln_next[2], L.ACT_NONE, need_bwd) if (ln_next is not None and ln_next_ok(a, Wo.shape[0], ln_next, Wo, x if residual else None, need_bwd, wparam=P["Wo"])) else None
+    lnn = None if ln_next is None else LnNext(ln_next[0], ln_next[1], ln_next[2], need_bwd)
     y, _ = linear_fwd(a, Wo, P["bo"], L.ACT_NONE, mask, res=x if residual else None, drop=dr, ln_next=lnn, ln_post=post, wparam=P["Wo"])
     post = post[0] if post else None
     if not need_bwd:
         return (y, None, post) if ln_next is not None else (y, None)
 
     def bwd(dy, dz_in=None, second=None):
-        fuse2 = ln_fusable(ln2_b.spec, a.shape[0], d, dtype, Wo.shape[0], Wo)     # LN2 (+ activation) backward in the out-projection's dgrad
-        kw = dict(ln=ln2_b.spec) if fuse2 else {}
-        if dz_in is not None:
-            da, _ = linear_bwd(dz_in, a, Wo, None, L.ACT_NONE, None, 1.0, gacc(P["Wo"]), gacc(P["bo"]), dz_ready=True, **kw)
-        else:
-            da, _ = linear_bwd(dy, a, Wo, None, L.ACT_NONE, mask, 1.0, gacc(P["Wo"]), gacc(P["bo"]), drop=dr, **kw)
-        dc = da if fuse2 else ln2_b(da)
+        dc = (dgrad_ln_bwd(ln2_b, dz_in, a, Wo, P["Wo"], P["bo"], packed=False, dz_ready=True) if dz_in is not None else
+              dgrad_ln_bwd(ln2_b, dy, a, Wo, P["Wo"], P["bo"], mask=mask, packed=False, drop=dr))
         gwd = gacc(P["wd"])
         dp, _ = dwconv_bwd_deferred(dc, p_, wd, P["bd"].detach() if P["bd"] is not None else None, gwd.view(d, k),
                                     gacc(P["bd"]), B, T, d, k, True, L.PAD_ZERO, chunk)
-        if ln_fusable(ln1_b.spec, h.shape[0], d, dtype, 2 * d, Wp):
-            out, _ = linear_bwd(dp, h, Wp, None, L.ACT_NONE, None, 1.0, gacc(P["Wp"]).view(2 * d, d), gacc(P["bp"]),
-                                res_grad=dy if residual else None, ln=ln1_b.spec, ln_second=second)
-            return out
-        dh, _ = linear_bwd(dp, h, Wp, None, L.ACT_NONE, None, 1.0, gacc(P["Wp"]).view(2 * d, d), gacc(P["bp"]), wparam=P["Wp"], slabs_ok=True)
-        return ln1_b(dh, res=dy if residual else None, second=second)
+        return dgrad_ln_bwd(ln1_b, dp, h, Wp, P["Wp"], P["bp"], res=dy if residual else None, second=second)
     # what this block does first to its incoming gradient: D(dy) * mask (nothing to precompute without mask and dropout)
     bwd.pre = (1.0, mask, dr) if (mask is not None or dr is not None) else None
     bwd.ln1_fused = ln_fusable(ln1_b.spec, h.shape[0], d, dtype, 2 * d, Wp)   # then `second` may carry (.., z, act) of the consumer
