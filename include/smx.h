@@ -88,7 +88,7 @@ typedef struct smx_epilogue {
   const void* ln_x;    int64_t ln_ldx;                    /* the LayerNorm input (N, M), dtype T                       */
   const float* ln_stats; const float* ln_gamma;           /* (N, 2) mean | rstd of the forward; [M]                    */
   float* ln_partial;                                      /* [ceil(N/smx_gemm_ln_tile_rows())][2][M] per-tile dgamma | dbeta partial rows */
-  void* ln_dx2;        int64_t ln_lddx2;                  /* optional second output (see smx_layernorm_bwd2) or NULL   */
+  void* ln_dx2;        int64_t ln_lddx2;                  /* optional second output (see smx_layernorm_bwd: dX2) or NULL */
   const uint8_t* ln_mask2; float ln_alpha2; float ln_drop_p2; uint64_t ln_drop_seed2;
   /* SMX_EPI_LN_FWD: a LayerNorm of the (row-complete) output: lnf_y = act(LN(C)), lnf_stats = (mean, rstd) per row */
   const float* lnf_gamma; const float* lnf_beta; void* lnf_y; int64_t lnf_ldy; float* lnf_stats; float lnf_eps; int32_t lnf_act;
@@ -320,59 +320,78 @@ int smx_expdecay_mean_fwd(int dtype, const void* S, int64_t lds, void* out, int6
                           void* workspace, void* stream);
 int smx_expdecay_mean_bwd(int dtype, const void* dOut, int64_t ldo, void* dS, int64_t lds, int B, int T, int D, float decay,
                           void* workspace, void* stream);
-/* (smx_layernorm_bwd with dgamma == dbeta == NULL leaves its partial rows [smx_layernorm_bwd_blocks(N)][2][D] in the
- *  workspace for smx_reduce_jobs: two jobs, src = ws (dgamma) and ws + D (dbeta), src_stride 2*D, rows 1, cols D.) */
-int smx_layernorm_bwd_blocks(int N);
 /* LayerNorm over the last dim with an optional fused activation: Y = act(LN(X))
  * (torch.nn.LayerNorm; Conformer.py:146,152-153,475-476,738).  stats (N,2) fp32 = (mean, rstd), optional in fwd.
- * bwd: dX = R + LNbwd(dY * act'(LN(X))) (R optional residual-gradient, dtype T; LN(X) is recomputed from the
- * stats); dgamma/dbeta += per-block partial sums (in `workspace`, smx_layernorm_bwd_workspace bytes) reduced in a
- * fixed order: bit-reproducible, no atomics. */
-int smx_layernorm_fwd(int dtype, const void* X, int64_t ldx, const float* gamma, const float* beta, void* Y,
-                      int64_t ldy, float* stats, int N, int D, float eps, int act, void* stream);
-/* The same with a float32 input X and an output of dtype `dtype` (fp32 residual stream -> bf16 GEMM input), and the
- * backward with a float32 X (dY, R, dX, dX2 dtype `dtype`): torch.nn.LayerNorm under autocast. */
-int smx_layernorm_fwd_x32(int dtype, const float* X, int64_t ldx, const float* gamma, const float* beta, void* Y,
-                          int64_t ldy, float* stats, int N, int D, float eps, int act, void* stream);
-/* Two LayerNorms in ONE pass over the float32 residual stream: Y1 = LN1(X) (float32: the layer-final norm2, Conformer.py:536 -
- * the next layer's stream input) and Y2 = LN2(Y1) (dtype2: the LayerNorm of the next layer's first feed-forward module,
- * Conformer.py:458-459,507); stats1 / stats2 (N,2) = (mean, rstd), optional.  Equal to smx_layernorm_fwd (fp32) followed by
- * smx_layernorm_fwd_x32 to an ulp; Y1 is not re-read and is stored with the non-temporal hint.  D % 4 == 0, D <= 2048, 16-byte aligned rows (SMX_EUNSUPPORTED otherwise). */
-int smx_layernorm_fwd_pair_x32(int dtype2, const float* X, int64_t ldx, const float* gamma1, const float* beta1, float eps1,
-                               float* Y1, int64_t ldy1, float* stats1, const float* gamma2, const float* beta2, float eps2,
-                               void* Y2, int64_t ldy2, float* stats2, int N, int D, void* stream);
+ *
+ * Forward: smx_layernorm_fwd(&a, stream).  X and Y have dtype `dtype` unless x_f32 = 1: X is then float32 and Y of dtype
+ * `dtype` (fp32 residual stream -> bf16 GEMM input: torch.nn.LayerNorm under autocast; bf16 Y needs D % 4 == 0, D <= 2048
+ * and aligned rows, else SMX_EUNSUPPORTED).
+ * Y2 != NULL: two LayerNorms in ONE pass over the float32 residual stream: Y = LN(X) (float32: `dtype` SMX_F32, `act` none -
+ * the layer-final norm2, Conformer.py:536, the next layer's stream input) and Y2 = LN2(Y) (dtype2: the LayerNorm of the next
+ * layer's first feed-forward module, Conformer.py:458-459,507) with gamma2 / beta2 / eps2 / stats2.  Equal to the fp32 forward
+ * followed by the x_f32 forward to an ulp; Y is not re-read and is stored with the non-temporal hint.  D % 4 == 0, D <= 2048,
+ * 16-byte aligned rows (SMX_EUNSUPPORTED otherwise). */
+typedef struct smx_ln_fwd {
+  int32_t dtype;       int32_t x_f32;        /* dtype of Y (and of X unless x_f32)                                          */
+  const void* X;       int64_t ldx;
+  const float* gamma;  const float* beta;
+  void* Y;             int64_t ldy;
+  float* stats;                              /* (N, 2) or NULL                                                              */
+  float eps;           int32_t act;
+  int32_t N;           int32_t D;
+  /* optional second LayerNorm of Y (NULL Y2 = off) */
+  const float* gamma2; const float* beta2;
+  void* Y2;            int64_t ldy2;
+  float* stats2;
+  float eps2;          int32_t dtype2;
+} smx_ln_fwd;
+int smx_layernorm_fwd(const smx_ln_fwd* a, void* stream);
+
+/* Backward: smx_layernorm_bwd(&a, stream).
+ *   dX = R + LNbwd(dY * act'(LN(X)))   (R optional residual-gradient, dtype T; LN(X) is recomputed from the stats);
+ * dgamma/dbeta += per-block partial sums (in `workspace`, smx_layernorm_bwd_workspace bytes) reduced in a fixed order:
+ * bit-reproducible, no atomics.  With dgamma == dbeta == NULL the partial rows [smx_layernorm_bwd_blocks(N)][2][D] stay in the
+ * workspace for smx_reduce_jobs: two jobs, src = ws (dgamma) and ws + D (dbeta), src_stride 2*D, rows 1, cols D.
+ * dY, R, dX, dX2 have dtype `dtype`; X too unless x_f32 = 1 (float32 X next to bf16 gradients: torch.nn.LayerNorm under
+ * autocast; D % 4 == 0, D <= 2048 and aligned rows, else SMX_EUNSUPPORTED).
+ * Optional, each from the registers that hold dX:
+ *  - dX2 != NULL: a second output  dX2 = alpha2 * Dropout(dX; drop_p2, drop_seed2, index n*D + c) * row_mask2[n]  (D <= 2048)
+ *    - the first thing the next backward block does to this gradient (Conformer.py:507,536: the FFN module's 1/2 * dropout;
+ *    :146-152,327-331: the conv module's dropout and padding mask), so that block needs no elementwise pass of its own.
+ *  - slabs != NULL (instead of dY): the incoming gradient is the sum of `nslab` (1..16) float32 split-K slabs ((N, D) each,
+ *    slab_stride elements apart; added in slab order) - the dgrad of the Linear behind the LayerNorm computed by
+ *    smx_gemm_panel_slabs: reducer and LayerNorm backward in one launch.  bf16, dgamma = dbeta = NULL (partial rows stay in
+ *    `workspace` for smx_reduce_jobs), D <= 2048 and aligned rows.
+ *  - Z != NULL: backward THROUGH the activation that produced the LayerNorm's input, X = zact(Z) (Z the saved pre-activation):
+ *      dX = zact'(Z) * LNbwd(dY)   (act must be SMX_ACT_NONE: a LayerNorm without a fused activation of its own; no R, no dX2)
+ *    - the CSGU of the Branchformer's cgMLP normalises the gate half of GELU(channel_proj1(x)) (Branchformer.py:84-96 via the
+ *    upstream ConvolutionalSpatialGatingUnit), so the gradient of that half reaches channel_proj1's dZ without the separate
+ *    activation-backward pass over it.  bf16, D <= 2048, D % 8 == 0, 16-byte aligned rows (else SMX_EUNSUPPORTED: run the plain
+ *    backward + smx_act_mask_bwd). */
+typedef struct smx_ln_bwd {
+  int32_t dtype;       int32_t x_f32;
+  const void* dY;      int64_t lddy;         /* the incoming gradient, or NULL with slabs                                  */
+  const float* slabs;  int64_t slab_stride;
+  int32_t nslab;       int32_t act;
+  const void* X;       int64_t ldx;
+  const float* gamma;  const float* beta;
+  const float* stats;                        /* (N, 2) mean | rstd of the forward                                          */
+  const void* R;       int64_t ldr;          /* or NULL                                                                     */
+  void* dX;            int64_t lddx;
+  float* dgamma;       float* dbeta;         /* [D] or both NULL                                                            */
+  void* workspace;
+  void* dX2;           int64_t lddx2;        /* second output or NULL                                                       */
+  const uint8_t* row_mask2;                  /* [N] or NULL                                                                 */
+  float alpha2;        float drop_p2;
+  uint64_t drop_seed2;
+  const uint64_t* epoch;                     /* device step counter mixed into drop_seed2 (smx_step_counter_add), or NULL  */
+  const void* Z;       int64_t ldz;          /* pre-activation or NULL                                                      */
+  int32_t zact;        int32_t N;
+  int32_t D;           int32_t pad_;
+} smx_ln_bwd;
+int smx_layernorm_bwd(const smx_ln_bwd* a, void* stream);
+int smx_layernorm_bwd_blocks(int N);
 size_t smx_layernorm_bwd_workspace(int N, int D);
-int smx_layernorm_bwd(int dtype, const void* dY, int64_t lddy, const void* X, int64_t ldx, const float* gamma,
-                      const float* beta, int act, const float* stats, const void* R, int64_t ldr, void* dX,
-                      int64_t lddx, float* dgamma, float* dbeta, int N, int D, void* workspace, void* stream);
-/* The same with a second output written from the registers that hold dX:
- *   dX2 = alpha2 * Dropout(dX; drop_p2, drop_seed2, index n*D + c) * row_mask2[n]        (D <= 2048)
- * - the first thing the next backward block does to this gradient (Conformer.py:507,536: the FFN module's 1/2 * dropout;
- * :146-152,327-331: the conv module's dropout and padding mask), so that block needs no elementwise pass of its own. */
-int smx_layernorm_bwd2(int dtype, const void* dY, int64_t lddy, const void* X, int64_t ldx, const float* gamma,
-                       const float* beta, int act, const float* stats, const void* R, int64_t ldr, void* dX,
-                       int64_t lddx, float* dgamma, float* dbeta, int N, int D, void* workspace, void* dX2, int64_t lddx2,
-                       float alpha2, const uint8_t* row_mask2, float drop_p2, uint64_t drop_seed2, const uint64_t* epoch, void* stream);
-int smx_layernorm_bwd2_x32(int dtype, const void* dY, int64_t lddy, const float* X, int64_t ldx, const float* gamma,
-                           const float* beta, int act, const float* stats, const void* R, int64_t ldr, void* dX,
-                           int64_t lddx, float* dgamma, float* dbeta, int N, int D, void* workspace, void* dX2, int64_t lddx2,
-                           float alpha2, const uint8_t* row_mask2, float drop_p2, uint64_t drop_seed2, const uint64_t* epoch, void* stream);
-/* The same with the incoming gradient given as `nslab` float32 split-K slabs ((N, D) each, slab_stride elements apart; added in slab
- * order) - the dgrad of the Linear behind the LayerNorm computed by smx_gemm_panel_slabs: reducer and LayerNorm backward in one launch.
- * x_f32: X is the float32 residual stream.  dgamma / dbeta partial rows stay in `workspace` (smx_reduce_jobs). */
-int smx_layernorm_bwd2_slabs(int dtype, const float* slabs, int nslab, int64_t slab_stride, const void* X, int64_t ldx, int x_f32,
-                             const float* gamma, const float* beta, int act, const float* stats, const void* R, int64_t ldr, void* dX,
-                             int64_t lddx, int N, int D, void* workspace, void* dX2, int64_t lddx2, float alpha2, const uint8_t* row_mask2,
-                             float drop_p2, uint64_t drop_seed2, const uint64_t* epoch, void* stream);
-/* LayerNorm backward THROUGH the activation that produced the LayerNorm's input: X = zact(Z) (Z the saved pre-activation),
- *   dZ = zact'(Z) * LNbwd(dY)                      (act must be SMX_ACT_NONE: a LayerNorm without a fused activation of its own)
- * - the CSGU of the Branchformer's cgMLP normalises the gate half of GELU(channel_proj1(x)) (Branchformer.py:84-96 via the
- * upstream ConvolutionalSpatialGatingUnit), so the gradient of that half reaches channel_proj1's dZ without the separate
- * activation-backward pass over it.  bf16, D <= 2048, D % 8 == 0, 16-byte aligned rows (else SMX_EUNSUPPORTED: run
- * smx_layernorm_bwd + smx_act_mask_bwd).  dgamma / dbeta as in smx_layernorm_bwd (NULL: partial rows stay in `workspace`). */
-int smx_layernorm_bwd_preact(int dtype, const void* dY, int64_t lddy, const void* X, int64_t ldx, const float* gamma,
-                             const float* beta, int act, const float* stats, const void* Z, int64_t ldz, int zact,
-                             void* dX, int64_t lddx, float* dgamma, float* dbeta, int N, int D, void* workspace, void* stream);
 
 /* Fused GLU + depthwise Conv1d over time (Conformer.py:131-145,317-325):
  *   u[b,t,c] = P[b,t,c] * sigmoid(P[b,t,D+c]);  Y[b,t,c] = bias[c] + sum_j w[c,j] u[b,t+j-(k-1)/2,c]
@@ -548,7 +567,7 @@ int smx_expdecay_mean_sharded(int dtype, const void* S, int64_t lds, void* out, 
                               int t_off, int T_glob, int phase, float* ends, void* workspace, void* stream);
 
 /* Device step counter (one uint64 in device memory) - an explicit ARGUMENT of every call that uses it, never library
- * state: `epoch` of smx_dropout / smx_masked_mean_bwd(_act) / smx_act_mask_bwd / smx_layernorm_bwd2 /
+ * state: `epoch` of smx_dropout / smx_masked_mean_bwd(_act) / smx_act_mask_bwd / smx_layernorm_bwd (dX2) /
  * smx_dwconv1d_glu_fwd_drop, smx_epilogue.epoch of the GEMMs, `step_dev` of smx_adamw_step.  With a non-NULL counter a
  * fused / standalone dropout mixes the counter's current value into its seed and smx_adamw_step with step <= 0 takes its
  * bias-correction step from it: a whole training step can then be captured ONCE in a hipGraph (all kernel arguments

@@ -77,6 +77,24 @@ class PackJob(ctypes.Structure):
                 ("transposed", ctypes.c_int32), ("block_start", ctypes.c_int32)]
 
 
+class LnFwd(ctypes.Structure):
+    """smx_ln_fwd of include/smx.h."""
+    _fields_ = [("dtype", ctypes.c_int32), ("x_f32", ctypes.c_int32), ("X", c_vp), ("ldx", c_i64), ("gamma", c_vp), ("beta", c_vp),
+                ("Y", c_vp), ("ldy", c_i64), ("stats", c_vp), ("eps", c_f), ("act", ctypes.c_int32), ("N", ctypes.c_int32),
+                ("D", ctypes.c_int32), ("gamma2", c_vp), ("beta2", c_vp), ("Y2", c_vp), ("ldy2", c_i64), ("stats2", c_vp),
+                ("eps2", c_f), ("dtype2", ctypes.c_int32)]
+
+
+class LnBwd(ctypes.Structure):
+    """smx_ln_bwd of include/smx.h."""
+    _fields_ = [("dtype", ctypes.c_int32), ("x_f32", ctypes.c_int32), ("dY", c_vp), ("lddy", c_i64), ("slabs", c_vp),
+                ("slab_stride", c_i64), ("nslab", ctypes.c_int32), ("act", ctypes.c_int32), ("X", c_vp), ("ldx", c_i64),
+                ("gamma", c_vp), ("beta", c_vp), ("stats", c_vp), ("R", c_vp), ("ldr", c_i64), ("dX", c_vp), ("lddx", c_i64),
+                ("dgamma", c_vp), ("dbeta", c_vp), ("workspace", c_vp), ("dX2", c_vp), ("lddx2", c_i64), ("row_mask2", c_vp),
+                ("alpha2", c_f), ("drop_p2", c_f), ("drop_seed2", ctypes.c_uint64), ("epoch", c_vp), ("Z", c_vp), ("ldz", c_i64),
+                ("zact", ctypes.c_int32), ("N", ctypes.c_int32), ("D", ctypes.c_int32), ("pad_", ctypes.c_int32)]
+
+
 # name -> (restype, argtypes); mirrors include/smx.h one to one (tests/test_abi.py checks the export list)
 SIGNATURES = {
     "smx_version": (c_i, []),
@@ -123,18 +141,9 @@ SIGNATURES = {
     "smx_expdecay_mean_workspace": (c_sz, [c_i, c_i, c_i]),
     "smx_expdecay_mean_fwd": (c_i, [c_i, c_vp, c_i64, c_vp, c_i64, c_i, c_i, c_i, c_f, c_vp, c_vp]),
     "smx_expdecay_mean_bwd": (c_i, [c_i, c_vp, c_i64, c_vp, c_i64, c_i, c_i, c_i, c_f, c_vp, c_vp]),
-    "smx_layernorm_fwd": (c_i, [c_i, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i, c_i, c_f, c_i, c_vp]),
-    "smx_layernorm_fwd_x32": (c_i, [c_i, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i, c_i, c_f, c_i, c_vp]),
-    "smx_layernorm_fwd_pair_x32": (c_i, [c_i, c_vp, c_i64, c_vp, c_vp, c_f, c_vp, c_i64, c_vp, c_vp, c_vp, c_f, c_vp, c_i64, c_vp, c_i, c_i, c_vp]),
-    "smx_layernorm_bwd2_x32": (c_i, [c_i, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp,
-                                     c_vp, c_i, c_i, c_vp, c_vp, c_i64, c_f, c_vp, c_f, ctypes.c_uint64, c_vp, c_vp]),
-    "smx_layernorm_bwd_preact": (c_i, [c_i, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i, c_vp, c_vp, c_i64, c_i, c_vp, c_i64,
-                                       c_vp, c_vp, c_i, c_i, c_vp, c_vp]),
+    "smx_layernorm_fwd": (c_i, [ctypes.POINTER(LnFwd), c_vp]),
     "smx_layernorm_bwd_workspace": (c_sz, [c_i, c_i]),
-    "smx_layernorm_bwd": (c_i, [c_i, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp,
-                                c_vp, c_i, c_i, c_vp, c_vp]),
-    "smx_layernorm_bwd2": (c_i, [c_i, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp,
-                                 c_vp, c_i, c_i, c_vp, c_vp, c_i64, c_f, c_vp, c_f, ctypes.c_uint64, c_vp, c_vp]),
+    "smx_layernorm_bwd": (c_i, [ctypes.POINTER(LnBwd), c_vp]),
     "smx_dwconv1d_glu_fwd": (c_i, [c_i, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i, c_i, c_i, c_i, c_i,
                                    c_i, c_i, c_vp]),
     "smx_dwconv1d_glu_fwd_drop": (c_i, [c_i, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i, c_i, c_i, c_i, c_i,
@@ -183,8 +192,6 @@ SIGNATURES = {
     "smx_expdecay_mean_sharded": (c_i, [c_i, c_vp, c_i64, c_vp, c_i64, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_vp, c_vp, c_vp]),
     "smx_wgrad_group_direct_ok": (c_i, [c_i, c_i, c_i]),
     "smx_wgrad_group_direct": (c_i, [c_i, c_i, ctypes.POINTER(WgradDirectItem), c_i, c_vp]),
-    "smx_layernorm_bwd2_slabs": (c_i, [c_i, c_vp, c_i, c_i64, c_vp, c_i64, c_i, c_vp, c_vp, c_i, c_vp, c_vp, c_i64, c_vp, c_i64, c_i, c_i, c_vp,
-                                       c_vp, c_i64, c_f, c_vp, c_f, ctypes.c_uint64, c_vp, c_vp]),
     "smx_gemm_panel_rows": (c_i, [c_i, c_i]),
     "smx_step_counter_add": (c_i, [c_vp, ctypes.c_uint64, c_vp]),
     "smx_stream_capture_id": (c_i, [c_vp, ctypes.POINTER(ctypes.c_uint64)]),

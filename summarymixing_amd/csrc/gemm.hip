@@ -409,7 +409,7 @@ static int gemm_impl(int layout, int dtype, const void* A, int64_t lda, int64_t 
   p.nt = 1 | (((long)N * M * (long)cs * batch >= nt_bytes) ? 2 : 0);
   // With a LayerNorm appended (SMX_EPI_LN_FWD) the next kernel reads the LayerNorm output, not C: C (the float32 stream tensor, or
   // the pre-norm tensor the backward pass wants) is streamed whatever its size, so that it does not push the LayerNorm output out
-  // of the Infinity Cache (the same finding as smx_layernorm_fwd_pair_x32, rowwise.hip).
+  // of the Infinity Cache (the same finding as the pair form of smx_layernorm_fwd, layernorm.hip).
   if (p.e.flags & SMX_EPI_LN_FWD) p.nt |= 2;
   // epilogue instantiation: 1 = no element-wise side input, 2 = one (residual / saved pre-activation), 0 = general (C0 rows, column sums)
   p.epi_simple = (p.e.c0 || p.e.colsum) ? 0 : ((p.e.res || (p.e.flags & SMX_EPI_ACT_GRAD)) ? 2 : 1);

@@ -1,6 +1,6 @@
 // rowwise.hip — HBM-bound row-wise kernels of the SummaryMixing path (gfx950, wave64):
 //   masked mean over time (split-T, fixed-order combine) + broadcast backward, DynChunk window mean,
-//   LayerNorm fwd/bwd, activation/mask backward with fused bias / per-utterance column sums,
+//   activation/mask backward with fused bias / per-utterance column sums,
 //   axpby, casts, fused AdamW, sum of squares, clip factor.
 // Every kernel moves 8-16 bytes per lane per access along the feature dim (coalesced 512 B - 1 KiB per
 // wave instruction) and accumulates in fp32.
@@ -445,795 +445,6 @@ __global__ __launch_bounds__(256) void expdecay_apply_kernel(const T* __restrict
       }
       store4<T>(Y + ((long)b * T_ + t) * ldy + col, o);
     }
-  }
-}
-
-// =================================================================================================
-// LayerNorm.  One wave per row, 4 rows per block; lane owns 4-element vectors at columns lane*4 + 256*i.
-// =================================================================================================
-template <typename T, bool VEC>
-__global__ __launch_bounds__(256) void layernorm_fwd_kernel(const T* X, long ldx, const float* gamma, const float* beta,
-                                                            T* Y, long ldy, float* stats, int N_, int D, float eps,
-                                                            int act) {
-  const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= N_) return;
-  const T* x = X + (long)row * ldx;
-  T* y = Y + (long)row * ldy;
-  float s = 0.f;
-  if (VEC) {
-    for (int c = lane * 4; c < D; c += 256) { float f[4]; load4<T>(x + c, f); s += (f[0] + f[1]) + (f[2] + f[3]); }
-  } else {
-    for (int c = lane; c < D; c += 64) s += to_f32(x[c]);
-  }
-  const float mean = wave_sum(s) / (float)D;
-  float q = 0.f;
-  if (VEC) {
-    for (int c = lane * 4; c < D; c += 256) {
-      float f[4]; load4<T>(x + c, f);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) { float d = f[i] - mean; q += d * d; }
-    }
-  } else {
-    for (int c = lane; c < D; c += 64) { float d = to_f32(x[c]) - mean; q += d * d; }
-  }
-  const float rstd = rsqrtf(wave_sum(q) / (float)D + eps);
-  if (stats && lane == 0) { stats[2 * (long)row] = mean; stats[2 * (long)row + 1] = rstd; }
-  if (VEC) {
-    for (int c = lane * 4; c < D; c += 256) {
-      float f[4]; load4<T>(x + c, f);
-      float4 g4 = *reinterpret_cast<const float4*>(gamma + c), b4 = *reinterpret_cast<const float4*>(beta + c);
-      float o[4] = {(f[0] - mean) * rstd * g4.x + b4.x, (f[1] - mean) * rstd * g4.y + b4.y,
-                    (f[2] - mean) * rstd * g4.z + b4.z, (f[3] - mean) * rstd * g4.w + b4.w};
-      if (act == SMX_ACT_SWISH) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) o[i] = act_fwd_c<SMX_ACT_SWISH>(o[i]);
-      } else if (act == SMX_ACT_GELU) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) o[i] = act_fwd_c<SMX_ACT_GELU>(o[i]);
-      } else if (act != SMX_ACT_NONE) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) o[i] = act_fwd(act, o[i]);
-      }
-      store4<T>(y + c, o);
-    }
-  } else {
-    for (int c = lane; c < D; c += 64) y[c] = from_f32<T>(act_fwd(act, (to_f32(x[c]) - mean) * rstd * gamma[c] + beta[c]));
-  }
-}
-
-// Single-read forward for D <= 256 * CH (D % 4 == 0, aligned rows): the row lives in registers (one 4-element vector
-// per lane and chunk), U rows are in flight per wave (all their loads issued before the first reduction), workgroups
-// stride over the rows.  The generic kernel above re-reads the row three times behind three dependent latencies.
-// TX: element type of the input (float for the fp32 residual stream: LayerNorm(fp32 x) -> dtype T, smx_layernorm_fwd_x32)
-template <typename T, int CH, int U, typename TX = T>
-__global__ __launch_bounds__(256) void layernorm_fwd_fast(const TX* __restrict__ X, long ldx, const float* __restrict__ gamma,
-                                                          const float* __restrict__ beta, T* __restrict__ Y, long ldy,
-                                                          float* __restrict__ stats, int N_, int D, float eps, int act) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  float gam[CH][4], bet[CH][4];
-#pragma unroll
-  for (int i = 0; i < CH; ++i) {
-    const int c = (lane + 64 * i) * 4;
-    if (c < D) {
-      const float4 g4 = *reinterpret_cast<const float4*>(gamma + c), b4 = *reinterpret_cast<const float4*>(beta + c);
-      gam[i][0] = g4.x; gam[i][1] = g4.y; gam[i][2] = g4.z; gam[i][3] = g4.w;
-      bet[i][0] = b4.x; bet[i][1] = b4.y; bet[i][2] = b4.z; bet[i][3] = b4.w;
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) gam[i][j] = bet[i][j] = 0.f;
-    }
-  }
-  const float invD = 1.f / (float)D;
-  dispatch_act(act, [&](auto act_tag) {
-    constexpr int ACT = decltype(act_tag)::value;
-    for (int row0 = (blockIdx.x * 4 + w) * U; row0 < N_; row0 += gridDim.x * 4 * U) {
-      float f[U][CH][4], s[U], q[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int row = min(row0 + u, N_ - 1);
-#pragma unroll
-        for (int i = 0; i < CH; ++i) {
-          const int c = (lane + 64 * i) * 4;
-          if (c < D) load4<TX>(X + (long)row * ldx + c, f[u][i]);
-          else f[u][i][0] = f[u][i][1] = f[u][i][2] = f[u][i][3] = 0.f;
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        s[u] = 0.f;
-#pragma unroll
-        for (int i = 0; i < CH; ++i) s[u] += (f[u][i][0] + f[u][i][1]) + (f[u][i][2] + f[u][i][3]);
-      }
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-        for (int u = 0; u < U; ++u) s[u] += __shfl_xor(s[u], off, 64);
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        s[u] *= invD;                                      // mean
-        q[u] = 0.f;
-#pragma unroll
-        for (int i = 0; i < CH; ++i) {
-          if ((lane + 64 * i) * 4 < D) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { const float d = f[u][i][j] - s[u]; q[u] += d * d; }
-          }
-        }
-      }
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-        for (int u = 0; u < U; ++u) q[u] += __shfl_xor(q[u], off, 64);
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int row = row0 + u;
-        if (row >= N_) break;
-        const float rstd = rsqrtf(q[u] * invD + eps);
-        if (stats && lane == 0) *reinterpret_cast<float2*>(stats + 2 * (long)row) = make_float2(s[u], rstd);
-#pragma unroll
-        for (int i = 0; i < CH; ++i) {
-          const int c = (lane + 64 * i) * 4;
-          if (c < D) {
-            float o[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) o[j] = act_fwd_c<ACT>((f[u][i][j] - s[u]) * rstd * gam[i][j] + bet[i][j]);
-            store4<T>(Y + (long)row * ldy + c, o);
-          }
-        }
-      }
-    }
-  });
-}
-
-// Two LayerNorms in one pass over the float32 residual stream (round 4): y1 = LN1(x) (float32: the layer-final norm2 of
-// a Conformer layer, Conformer.py:536 = the next layer's stream input) and y2 = LN2(y1) (dtype T2: the LayerNorm in front of
-// the next layer's first feed-forward module, Conformer.py:458-459,507).  y1 never comes back from memory for the second
-// statistics.  Same lane / chunk layout and the same reduction trees as layernorm_fwd_fast, so both outputs equal those of
-// two separate launches to an ulp.
-template <typename T2, int CH, int U>
-__global__ __launch_bounds__(256) void layernorm_fwd_pair_fast(const float* __restrict__ X, long ldx, const float* __restrict__ gamma1,
-                                                               const float* __restrict__ beta1, float eps1, float* __restrict__ Y1,
-                                                               long ldy1, float* __restrict__ stats1,
-                                                               const float* __restrict__ gamma2, const float* __restrict__ beta2,
-                                                               float eps2, T2* __restrict__ Y2, long ldy2, float* __restrict__ stats2,
-                                                               int N_, int D) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  float g1[CH][4], b1[CH][4], g2[CH][4], b2[CH][4];
-#pragma unroll
-  for (int i = 0; i < CH; ++i) {
-    const int c = (lane + 64 * i) * 4;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) g1[i][j] = b1[i][j] = g2[i][j] = b2[i][j] = 0.f;
-    if (c < D) {
-      load4<float>(gamma1 + c, g1[i]); load4<float>(beta1 + c, b1[i]);
-      load4<float>(gamma2 + c, g2[i]); load4<float>(beta2 + c, b2[i]);
-    }
-  }
-  const float invD = 1.f / (float)D;
-  auto row_sum = [&](float (&v)[U]) __attribute__((always_inline)) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-      for (int u = 0; u < U; ++u) v[u] += __shfl_xor(v[u], off, 64);
-  };
-  for (int row0 = (blockIdx.x * 4 + w) * U; row0 < N_; row0 += gridDim.x * 4 * U) {
-    float f[U][CH][4], s[U], q[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int row = min(row0 + u, N_ - 1);
-#pragma unroll
-      for (int i = 0; i < CH; ++i) {
-        const int c = (lane + 64 * i) * 4;
-        if (c < D) load4<float>(X + (long)row * ldx + c, f[u][i]);
-        else f[u][i][0] = f[u][i][1] = f[u][i][2] = f[u][i][3] = 0.f;
-      }
-    }
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {               // pass 0: LN1 (f <- y1, stored), pass 1: LN2 of the registers
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        s[u] = 0.f;
-#pragma unroll
-        for (int i = 0; i < CH; ++i) s[u] += (f[u][i][0] + f[u][i][1]) + (f[u][i][2] + f[u][i][3]);
-      }
-      row_sum(s);
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        s[u] *= invD;
-        q[u] = 0.f;
-#pragma unroll
-        for (int i = 0; i < CH; ++i) {
-          if ((lane + 64 * i) * 4 < D) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { const float d = f[u][i][j] - s[u]; q[u] += d * d; }
-          }
-        }
-      }
-      row_sum(q);
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int row = row0 + u;
-        const bool live = row < N_;
-        const float rstd = rsqrtf(q[u] * invD + (pass == 0 ? eps1 : eps2));
-        float* st = pass == 0 ? stats1 : stats2;
-        if (live && st && lane == 0) *reinterpret_cast<float2*>(st + 2 * (long)row) = make_float2(s[u], rstd);
-#pragma unroll
-        for (int i = 0; i < CH; ++i) {
-          const int c = (lane + 64 * i) * 4;
-          if (c < D) {
-            float o[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-              o[j] = (f[u][i][j] - s[u]) * rstd * (pass == 0 ? g1[i][j] : g2[i][j]) + (pass == 0 ? b1[i][j] : b2[i][j]);
-            if (pass == 0) {
-              if (live) {
-                // non-temporal: the stream tensor is next read by a residual epilogue several kernels later, Y2 by the very next
-                // GEMM - with an ordinary store the 131 MB of Y1 pushed Y2 out of the 256 MB Infinity Cache at 64000 x 512
-                // (that GEMM 220 -> 257 us, the C2a step +0.35 ms; with the hint -0.35 ms against two launches)
-                typedef uint32_t u32x4n __attribute__((ext_vector_type(4)));
-                u32x4n uu = {__float_as_uint(o[0]), __float_as_uint(o[1]), __float_as_uint(o[2]), __float_as_uint(o[3])};
-                __builtin_nontemporal_store(uu, reinterpret_cast<u32x4n*>(Y1 + (long)row * ldy1 + c));
-              }
-#pragma unroll
-              for (int j = 0; j < 4; ++j) f[u][i][j] = o[j];
-            } else if (live) {
-              store4<T2>(Y2 + (long)row * ldy2 + c, o);
-            }
-          }
-        }
-      }
-    }
-  }
-}
-
-// bwd: dx = R + rstd * (g - mean(g) - xhat * mean(g*xhat)), g = dy*act'(LN(x))*gamma.  Blocks stride over rows;
-// gamma/beta of the lane's columns live in registers for the whole kernel, U rows are in flight per wave (all
-// their loads issued before any reduction), dgamma/dbeta partial sums stay in registers until one atomic flush.
-// Optional second output of the LayerNorm backward: dX2 = alpha * Dropout(dX; seed) * row_mask - the first thing the
-// NEXT backward block does to this gradient (FFN: 1/2 * D(dy), conv module: D(dy) * mask).  Written from the registers
-// that hold dX anyway, it replaces a separate elementwise pass (one more read and one more launch per module).
-struct LnSecond {
-  void* dX2; long ld; float alpha; const uint8_t* mask; uint32_t thresh; float scale; uint64_t seed; const uint64_t* epoch;
-  // round 6 (split-K dgrads of a small batch, smx_gemm_panel_slabs): the incoming gradient dY = the sum of `nslab` float32 slabs
-  // ((N, D) each, `slab_stride` elements apart, added in slab order) instead of a dtype-T tensor; null: dY as given
-  const float* slabs; int nslab; long slab_stride;
-};
-
-template <typename T, int VW, int CH, int U, typename TX = T>
-__global__ __launch_bounds__(256) void layernorm_bwd_kernel(const T* __restrict__ dY, long lddy, const TX* __restrict__ X,
-                                                            long ldx, const float* __restrict__ gamma,
-                                                            const float* __restrict__ beta, int act,
-                                                            const float* __restrict__ stats, const T* __restrict__ R,
-                                                            long ldr, T* __restrict__ dX, long lddx,
-                                                            float* __restrict__ partial, int N_, int D, LnSecond sec) {
-  const uint64_t sseed = sec.dX2 ? epoch_seed(sec.seed, sec.epoch) : 0;
-  __shared__ float red[3][64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  float gam[CH][VW], bet[CH][VW], dg[CH][VW], db[CH][VW];
-#pragma unroll
-  for (int i = 0; i < CH; ++i)
-#pragma unroll
-    for (int j = 0; j < VW; ++j) {
-      const int c = (lane + 64 * i) * VW + j;
-      gam[i][j] = c < D ? gamma[c] : 0.f;
-      bet[i][j] = (c < D && act != SMX_ACT_NONE) ? beta[c] : 0.f;
-      dg[i][j] = db[i][j] = 0.f;
-    }
-  dispatch_act(act, [&](auto act_tag) {
-    constexpr int ACT = decltype(act_tag)::value;
-    for (int row0 = (blockIdx.x * 4 + w) * U; row0 < N_; row0 += gridDim.x * 4 * U) {
-      float fdy[U][CH][VW], fx[U][CH][VW], fr[U][CH][VW == 4 ? 4 : 1], mean[U], rstd[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int row = min(row0 + u, N_ - 1);           // tail rows re-read the last row (results discarded)
-        mean[u] = stats[2 * (long)row];
-        rstd[u] = stats[2 * (long)row + 1];
-#pragma unroll
-        for (int i = 0; i < CH; ++i) {
-          const int c = (lane + 64 * i) * VW;
-          const int cc = c < D ? c : 0;                  // idle lanes re-read column 0
-          if constexpr (VW == 4) {
-            if (sec.slabs) {                               // (uniform)
-              const float* sp = sec.slabs + (long)row * D + cc;
-              fdy[u][i][0] = fdy[u][i][1] = fdy[u][i][2] = fdy[u][i][3] = 0.f;
-              for (int s0 = 0; s0 < sec.nslab; s0 += 4) {  // four slabs in flight, summed in slab order
-                float4 a4[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) a4[k] = *reinterpret_cast<const float4*>(sp + (long)min(s0 + k, sec.nslab - 1) * sec.slab_stride);
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                  if (s0 + k < sec.nslab) { fdy[u][i][0] += a4[k].x; fdy[u][i][1] += a4[k].y; fdy[u][i][2] += a4[k].z; fdy[u][i][3] += a4[k].w; }
-              }
-            } else {
-              load4<T>(dY + (long)row * lddy + cc, fdy[u][i]);
-            }
-            load4<TX>(X + (long)row * ldx + cc, fx[u][i]);
-          }
-          else { fdy[u][i][0] = to_f32(dY[(long)row * lddy + cc]); fx[u][i][0] = to_f32(X[(long)row * ldx + cc]); }
-          // the residual gradient is requested with the operands: loaded after the reductions it was a second dependent
-          // round trip per row group
-          if constexpr (VW == 4) {
-            if (R) load4<T>(R + (long)row * ldr + cc, fr[u][i]);
-            else fr[u][i][0] = fr[u][i][1] = fr[u][i][2] = fr[u][i][3] = 0.f;
-          }
-        }
-      }
-      float s1[U], s2[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const bool rok = row0 + u < N_;
-        s1[u] = s2[u] = 0.f;
-#pragma unroll
-        for (int i = 0; i < CH; ++i) {
-          const bool cok = (lane + 64 * i) * VW < D;
-#pragma unroll
-          for (int j = 0; j < VW; ++j) {
-            const float xhat = (fx[u][i][j] - mean[u]) * rstd[u];
-            float dyn = (cok && rok) ? fdy[u][i][j] : 0.f;
-            if constexpr (ACT != SMX_ACT_NONE) dyn *= act_grad_c<ACT>(xhat * gam[i][j] + bet[i][j]);
-            const float g = dyn * gam[i][j];
-            fx[u][i][j] = xhat;          // reuse registers: fx <- xhat, fdy <- g
-            fdy[u][i][j] = g;
-            s1[u] += g;
-            s2[u] += g * xhat;
-            dg[i][j] += dyn * xhat;
-            db[i][j] += dyn;
-          }
-        }
-      }
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) { s1[u] += __shfl_xor(s1[u], off, 64); s2[u] += __shfl_xor(s2[u], off, 64); }
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int row = row0 + u;
-        if (row >= N_) continue;
-        const float m1 = s1[u] / (float)D, m2 = s2[u] / (float)D;
-#pragma unroll
-        for (int i = 0; i < CH; ++i) {
-          const int c = (lane + 64 * i) * VW;
-          if (c < D) {
-            float o[VW];
-#pragma unroll
-            for (int j = 0; j < VW; ++j) o[j] = rstd[u] * (fdy[u][i][j] - m1 - fx[u][i][j] * m2);
-            if constexpr (VW == 4) {
-#pragma unroll
-              for (int j = 0; j < 4; ++j) o[j] += fr[u][i][j];
-            } else {
-              if (R) o[0] += to_f32(R[(long)row * ldr + c]);
-            }
-            if constexpr (VW == 4) store4<T>(dX + (long)row * lddx + c, o);
-            else dX[(long)row * lddx + c] = from_f32<T>(o[0]);
-            if (sec.dX2) {                               // (uniform)
-              const float mk = (sec.mask ? (sec.mask[row] ? 1.f : 0.f) : 1.f) * sec.alpha;
-              if (sec.thresh) dropout_apply_any<VW>(o, sseed, (uint64_t)row * D + c, sec.thresh, sec.scale);
-#pragma unroll
-              for (int j = 0; j < VW; ++j) o[j] *= mk;
-              T* d2 = reinterpret_cast<T*>(sec.dX2);
-              if constexpr (VW == 4) store4<T>(d2 + (long)row * sec.ld + c, o);
-              else d2[(long)row * sec.ld + c] = from_f32<T>(o[0]);
-            }
-          }
-        }
-      }
-    }
-  });
-  // flush dgamma / dbeta: reduce the 4 waves through LDS and write ONE partial row per block (no atomics: with a
-  // few thousand blocks adding into the same D addresses the L2 atomic unit serialised, 200 us per call).
-#pragma unroll
-  for (int pass = 0; pass < 2; ++pass) {
-#pragma unroll
-    for (int i = 0; i < CH; ++i)
-#pragma unroll
-      for (int j = 0; j < VW; ++j) {
-        float v = pass == 0 ? dg[i][j] : db[i][j];
-        __syncthreads();
-        if (w > 0) red[w - 1][lane] = v;
-        __syncthreads();
-        if (w == 0) {
-          v = ((v + red[0][lane]) + red[1][lane]) + red[2][lane];
-          const int c = (lane + 64 * i) * VW + j;
-          if (c < D) partial[((long)blockIdx.x * 2 + pass) * D + c] = v;
-        }
-      }
-  }
-}
-
-#ifndef SMX_LN_WG8_UF
-#define SMX_LN_WG8_UF 2        // rows in flight per workgroup, forward
-#endif
-#ifndef SMX_LN_WG8_FBLOCKS
-#define SMX_LN_WG8_FBLOCKS 2048
-#endif
-#ifndef SMX_LN_WG8_FROM
-#define SMX_LN_WG8_FROM 1024   // rows wider than this (and <= 2048, bf16) take the workgroup-per-row kernels
-#endif
-// ---- mid-width rows (1024 < D <= 2048, bf16; the CSGU LayerNorm over 1536 channels of the Branchformer's cgMLP) ----------------
-// One WORKGROUP per row, thread t owns the 8 consecutive columns 8 t (one 16-byte access per tensor and row), U rows in flight
-// per iteration, workgroups stride over the rows; gamma / beta (and the dgamma / dbeta partial sums) of the thread's columns live
-// in registers for the whole kernel.  The wave-per-row kernels above need 8 chunks of 4 columns per lane at this width: 128
-// parameter registers per lane (backward: 256 VGPRs = ONE wave per SIMD with one 9 KB row in flight: 2.45 TB/s; forward: every
-// one of the 8192 waves fetched its own 12 KB of gamma / beta for ~4 rows of 3 KB: 2.2 TB/s; tools/step_records.py c4).
-__device__ __forceinline__ void ld8_bf16(const bf16_t* p, float (&f)[8]) {
-  const uint4 u = *reinterpret_cast<const uint4*>(p);
-  const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) { f[2 * i] = __uint_as_float(w[i] << 16); f[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u); }
-}
-__device__ __forceinline__ void st8_bf16(bf16_t* p, const float (&f)[8]) {
-  *reinterpret_cast<uint4*>(p) = make_uint4(pack_bf16x2(f[0], f[1]), pack_bf16x2(f[2], f[3]), pack_bf16x2(f[4], f[5]), pack_bf16x2(f[6], f[7]));
-}
-__device__ __forceinline__ void ld8_f32(const float* p, float (&f)[8]) {
-  const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
-  f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
-}
-// sums of U values per thread over the workgroup (4 waves): wave shuffles, then 4 partials per value through LDS
-template <int U>
-__device__ __forceinline__ void wg_sum(float (&v)[U], float (*red)[4], int lane, int w) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-    for (int u = 0; u < U; ++u) v[u] += __shfl_xor(v[u], off, 64);
-  if (lane == 0) {
-#pragma unroll
-    for (int u = 0; u < U; ++u) red[u][w] = v[u];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int u = 0; u < U; ++u) v[u] = (red[u][0] + red[u][1]) + (red[u][2] + red[u][3]);
-}
-
-template <int U>
-__global__ __launch_bounds__(256) void layernorm_fwd_wg8_kernel(const bf16_t* __restrict__ X, long ldx, const float* __restrict__ gamma,
-                                                                const float* __restrict__ beta, bf16_t* __restrict__ Y, long ldy,
-                                                                float* __restrict__ stats, int N_, int D, float eps, int act) {
-  __shared__ float red[2][U][4];
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6, c = t * 8;
-  const bool in = c < D;
-  float gam[8], bet[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { gam[j] = in ? gamma[c + j] : 0.f; bet[j] = in ? beta[c + j] : 0.f; }
-  const float invD = 1.f / (float)D;
-  dispatch_act(act, [&](auto act_tag) {
-    constexpr int ACT = decltype(act_tag)::value;
-    for (int row0 = blockIdx.x * U; row0 < N_; row0 += gridDim.x * U) {
-      float f[U][8], s[U], q[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int row = min(row0 + u, N_ - 1);            // tail rows re-read the last row (results discarded)
-        if (in) ld8_bf16(X + (long)row * ldx + c, f[u]);
-        else {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) f[u][j] = 0.f;
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) s[u] = ((f[u][0] + f[u][1]) + (f[u][2] + f[u][3])) + ((f[u][4] + f[u][5]) + (f[u][6] + f[u][7]));
-      wg_sum<U>(s, red[0], lane, w);
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        s[u] *= invD;                                      // mean
-        q[u] = 0.f;
-        if (in) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) { const float d = f[u][j] - s[u]; q[u] += d * d; }
-        }
-      }
-      wg_sum<U>(q, red[1], lane, w);                       // (red[0] is rewritten only after this barrier: no race)
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int row = row0 + u;
-        if (row >= N_) break;
-        const float rstd = rsqrtf(q[u] * invD + eps);
-        if (stats && t == 0) *reinterpret_cast<float2*>(stats + 2 * (long)row) = make_float2(s[u], rstd);
-        if (in) {
-          float o[8];
-#pragma unroll
-          for (int j = 0; j < 8; ++j) o[j] = act_fwd_c<ACT>((f[u][j] - s[u]) * rstd * gam[j] + bet[j]);
-          st8_bf16(Y + (long)row * ldy + c, o);
-        }
-      }
-    }
-  });
-}
-
-// backward (see layernorm_bwd_kernel for the formulas); TX = float: the LayerNorm input is the fp32 residual stream.
-// Software-pipelined over the rows of the workgroup: the operands of row i + 1 are requested before row i is reduced, and stay
-// PACKED (the 16 bytes as loaded) until they are consumed - 4 registers per bf16 tensor and row instead of 8, unpacked once for
-// the row sums and once more for the outputs.  With one row in flight and nothing prefetched the kernel ran at the latency
-// bound of 4 workgroups x 9 KB per CU (4.7 TB/s plain, 3.6 TB/s with the extra Z stream of PRE).
-// PRE (smx_layernorm_bwd_preact): the LayerNorm input is X = zact(Z); the kernel then emits the gradient w.r.t. Z,
-// dX * zact'(Z), from the registers that hold dX - the consumer's activation-backward pass over this tensor is gone.
-template <typename TX>
-struct LnRaw {
-  uint4 dy, r, z;
-  uint4 x0, x1;                                            // (bf16 x: x0 only)
-  float mean, rstd;
-};
-__device__ __forceinline__ void unpack8(const uint4& u, float (&f)[8]) {
-  const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) { f[2 * i] = __uint_as_float(w[i] << 16); f[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u); }
-}
-template <bool PRE, typename TX>
-__global__ __launch_bounds__(256, 4) void layernorm_bwd_wg8_kernel(const bf16_t* __restrict__ dY, long lddy, const TX* __restrict__ X, long ldx,
-                                                                   const float* __restrict__ gamma, const float* __restrict__ beta, int act,
-                                                                   const float* __restrict__ stats, const bf16_t* __restrict__ R, long ldr,
-                                                                   bf16_t* __restrict__ dX, long lddx, float* __restrict__ partial, int N_, int D,
-                                                                   const bf16_t* __restrict__ Zp, long ldz, int zact) {
-  __shared__ float red[2][2][4];
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6, c = t * 8;
-  const bool in = c < D;
-  const int cc = in ? c : 0;                               // (idle threads re-read column 0; their results are masked)
-  float gam[8], bet[8], dg[8], db[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    gam[j] = in ? gamma[c + j] : 0.f;
-    bet[j] = (in && act != SMX_ACT_NONE) ? beta[c + j] : 0.f;
-    dg[j] = db[j] = 0.f;
-  }
-  const float invD = 1.f / (float)D;
-  auto fetch = [&](int row, LnRaw<TX>& q) {
-    q.mean = stats[2 * (long)row];
-    q.rstd = stats[2 * (long)row + 1];
-    q.dy = *reinterpret_cast<const uint4*>(dY + (long)row * lddy + cc);
-    if constexpr (sizeof(TX) == 4) {
-      const float* xp = reinterpret_cast<const float*>(X) + (long)row * ldx + cc;
-      q.x0 = *reinterpret_cast<const uint4*>(xp);
-      q.x1 = *reinterpret_cast<const uint4*>(xp + 4);
-    } else {
-      q.x0 = *reinterpret_cast<const uint4*>(reinterpret_cast<const bf16_t*>(X) + (long)row * ldx + cc);
-    }
-    if constexpr (!PRE) {
-      if (R) q.r = *reinterpret_cast<const uint4*>(R + (long)row * ldr + cc);   // (uniform; the PRE variant has no residual gradient)
-    }
-    if constexpr (PRE) q.z = *reinterpret_cast<const uint4*>(Zp + (long)row * ldz + cc);
-  };
-  auto xhat8 = [&](const LnRaw<TX>& q, float (&xh)[8]) {
-    if constexpr (sizeof(TX) == 4) {
-      const uint32_t wv[8] = {q.x0.x, q.x0.y, q.x0.z, q.x0.w, q.x1.x, q.x1.y, q.x1.z, q.x1.w};
-#pragma unroll
-      for (int j = 0; j < 8; ++j) xh[j] = (__uint_as_float(wv[j]) - q.mean) * q.rstd;
-    } else {
-      unpack8(q.x0, xh);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) xh[j] = (xh[j] - q.mean) * q.rstd;
-    }
-  };
-  auto body = [&](auto act_tag) {
-    constexpr int ACT = decltype(act_tag)::value;
-    LnRaw<TX> cur, nxt;
-    int row = blockIdx.x, it = 0;
-    if (row < N_) fetch(row, cur);
-    for (; row < N_; row += gridDim.x, ++it) {
-      const int rn = row + gridDim.x;
-      if (rn < N_) fetch(rn, nxt);                         // the next row is in flight while this one is reduced
-      float g[8], xh[8];
-      unpack8(cur.dy, g);
-      xhat8(cur, xh);
-      float ss[2] = {0.f, 0.f};
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        float dyn = in ? g[j] : 0.f;
-        if constexpr (ACT != SMX_ACT_NONE) dyn *= act_grad_c<ACT>(xh[j] * gam[j] + bet[j]);
-        const float xq = in ? xh[j] : 0.f;
-        const float gg = dyn * gam[j];
-        ss[0] += gg;
-        ss[1] += gg * xq;
-        dg[j] += dyn * xq;
-        db[j] += dyn;
-      }
-      wg_sum<2>(ss, red[it & 1], lane, w);                 // (alternating buffers: ONE barrier per row)
-      if (in) {
-        const float m1 = ss[0] * invD, m2 = ss[1] * invD;
-        float o[8];
-        unpack8(cur.dy, g);                                // (unpacked again instead of kept: 16 registers less across the barrier)
-        xhat8(cur, xh);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          float dyn = g[j];
-          if constexpr (ACT != SMX_ACT_NONE) dyn *= act_grad_c<ACT>(xh[j] * gam[j] + bet[j]);
-          o[j] = cur.rstd * (dyn * gam[j] - m1 - xh[j] * m2);
-        }
-        if constexpr (!PRE) {
-          if (R) {
-            float rr[8];
-            unpack8(cur.r, rr);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) o[j] += rr[j];
-          }
-        }
-        if constexpr (PRE) {
-          float zz[8];
-          unpack8(cur.z, zz);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) o[j] *= act_grad(zact, zz[j]);
-        }
-        st8_bf16(dX + (long)row * lddx + c, o);
-      }
-      cur = nxt;
-    }
-  };
-  if constexpr (PRE) body(ActTag<SMX_ACT_NONE>{});           // (the PRE entry point takes a plain LayerNorm only: one instantiation, no spills)
-  else dispatch_act(act, body);
-  if (in) {                                                // ONE partial row pair per workgroup (fixed-order reduction downstream)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      partial[((long)blockIdx.x * 2) * D + c + j] = dg[j];
-      partial[((long)blockIdx.x * 2 + 1) * D + c + j] = db[j];
-    }
-  }
-}
-
-// wide rows (2048 < D <= 4096, e.g. the (F,C) = 40x64 LayerNorm of the conv front-end): one WORKGROUP per row at a
-// time, thread t owns columns t + 256*i; row statistics through an LDS reduction; same partial-row flush as above.
-template <typename T, int CH>
-__global__ __launch_bounds__(256) void layernorm_bwd_wide_kernel(const T* __restrict__ dY, long lddy, const T* __restrict__ X,
-                                                                 long ldx, const float* __restrict__ gamma,
-                                                                 const float* __restrict__ beta, int act,
-                                                                 const float* __restrict__ stats, const T* __restrict__ R,
-                                                                 long ldr, T* __restrict__ dX, long lddx,
-                                                                 float* __restrict__ partial, int N_, int D) {
-  __shared__ float red[2][4];
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  float gam[CH], bet[CH], dg[CH], db[CH];
-#pragma unroll
-  for (int i = 0; i < CH; ++i) {
-    const int c = t + 256 * i;
-    gam[i] = c < D ? gamma[c] : 0.f;
-    bet[i] = (c < D && act != SMX_ACT_NONE) ? beta[c] : 0.f;
-    dg[i] = db[i] = 0.f;
-  }
-  for (int row = blockIdx.x; row < N_; row += gridDim.x) {
-    const float mean = stats[2 * (long)row], rstd = stats[2 * (long)row + 1];
-    float g[CH], xh[CH], s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < CH; ++i) {
-      const int c = t + 256 * i;
-      g[i] = xh[i] = 0.f;
-      if (c < D) {
-        const float xhat = (to_f32(X[(long)row * ldx + c]) - mean) * rstd;
-        float dyn = to_f32(dY[(long)row * lddy + c]);
-        if (act != SMX_ACT_NONE) dyn *= act_grad(act, xhat * gam[i] + bet[i]);
-        g[i] = dyn * gam[i]; xh[i] = xhat;
-        s1 += g[i]; s2 += g[i] * xhat;
-        dg[i] += dyn * xhat; db[i] += dyn;
-      }
-    }
-    s1 = wave_sum(s1); s2 = wave_sum(s2);
-    __syncthreads();
-    if (lane == 0) { red[0][w] = s1; red[1][w] = s2; }
-    __syncthreads();
-    const float m1 = ((red[0][0] + red[0][1]) + (red[0][2] + red[0][3])) / (float)D;
-    const float m2 = ((red[1][0] + red[1][1]) + (red[1][2] + red[1][3])) / (float)D;
-#pragma unroll
-    for (int i = 0; i < CH; ++i) {
-      const int c = t + 256 * i;
-      if (c < D) {
-        float o = rstd * (g[i] - m1 - xh[i] * m2);
-        if (R) o += to_f32(R[(long)row * ldr + c]);
-        dX[(long)row * lddx + c] = from_f32<T>(o);
-      }
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < CH; ++i) {
-    const int c = t + 256 * i;
-    if (c < D) { partial[((long)blockIdx.x * 2) * D + c] = dg[i]; partial[((long)blockIdx.x * 2 + 1) * D + c] = db[i]; }
-  }
-}
-
-// the same with 4 consecutive columns per thread (8-byte accesses in bf16): thread t owns columns (t + 256 i) * 4 .. + 3.
-// The 2-byte accesses of the kernel above cap it at the vector-memory issue rate (1.58 ms for the 2 GB of the front-end's
-// (128128, 2560) LayerNorm backward = 1.3 TB/s).
-template <typename T, int CH>
-__global__ __launch_bounds__(256) void layernorm_bwd_wide4_kernel(const T* __restrict__ dY, long lddy, const T* __restrict__ X,
-                                                                  long ldx, const float* __restrict__ gamma,
-                                                                  const float* __restrict__ beta, int act,
-                                                                  const float* __restrict__ stats, const T* __restrict__ R,
-                                                                  long ldr, T* __restrict__ dX, long lddx,
-                                                                  float* __restrict__ partial, int N_, int D) {
-  __shared__ float red[2][4];
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  float gam[CH][4], bet[CH][4], dg[CH][4], db[CH][4];
-#pragma unroll
-  for (int i = 0; i < CH; ++i) {
-    const int c = (t + 256 * i) * 4;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      gam[i][q] = c < D ? gamma[c + q] : 0.f;
-      bet[i][q] = (c < D && act != SMX_ACT_NONE) ? beta[c + q] : 0.f;
-      dg[i][q] = db[i][q] = 0.f;
-    }
-  }
-  for (int row = blockIdx.x; row < N_; row += gridDim.x) {
-    const float mean = stats[2 * (long)row], rstd = stats[2 * (long)row + 1];
-    float g[CH][4], xh[CH][4], s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < CH; ++i) {
-      const int c = (t + 256 * i) * 4;
-      if (c < D) {
-        load4<T>(X + (long)row * ldx + c, xh[i]);
-        load4<T>(dY + (long)row * lddy + c, g[i]);
-      } else {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) g[i][q] = xh[i][q] = 0.f;
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < CH; ++i)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float xhat = (xh[i][q] - mean) * rstd;
-        float dyn = g[i][q];
-        if (act != SMX_ACT_NONE) dyn *= act_grad(act, xhat * gam[i][q] + bet[i][q]);
-        const bool in = (t + 256 * i) * 4 < D;
-        xh[i][q] = in ? xhat : 0.f;
-        dyn = in ? dyn : 0.f;
-        g[i][q] = dyn * gam[i][q];
-        s1 += g[i][q]; s2 += g[i][q] * xh[i][q];
-        dg[i][q] += dyn * xh[i][q]; db[i][q] += dyn;
-      }
-    s1 = wave_sum(s1); s2 = wave_sum(s2);
-    __syncthreads();
-    if (lane == 0) { red[0][w] = s1; red[1][w] = s2; }
-    __syncthreads();
-    const float m1 = ((red[0][0] + red[0][1]) + (red[0][2] + red[0][3])) / (float)D;
-    const float m2 = ((red[1][0] + red[1][1]) + (red[1][2] + red[1][3])) / (float)D;
-#pragma unroll
-    for (int i = 0; i < CH; ++i) {
-      const int c = (t + 256 * i) * 4;
-      if (c < D) {
-        float o[4], rr[4] = {0.f, 0.f, 0.f, 0.f};
-        if (R) load4<T>(R + (long)row * ldr + c, rr);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) o[q] = rstd * (g[i][q] - m1 - xh[i][q] * m2) + rr[q];
-        store4<T>(dX + (long)row * lddx + c, o);
-      }
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < CH; ++i) {
-    const int c = (t + 256 * i) * 4;
-    if (c < D) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        partial[((long)blockIdx.x * 2) * D + c + q] = dg[i][q];
-        partial[((long)blockIdx.x * 2 + 1) * D + c + q] = db[i][q];
-      }
-    }
-  }
-}
-
-// dgamma[c] += sum_b partial[b][0][c]; dbeta[c] += sum_b partial[b][1][c]   (fixed order => bit-reproducible)
-// block = 32 columns x 8 row groups; every thread sums nblocks/8 partial rows with 4 independent accumulators.
-__global__ __launch_bounds__(256) void ln_param_reduce_kernel(const float* __restrict__ partial, int nblocks, int D,
-                                                              float* dgamma, float* dbeta) {
-  __shared__ float red[16][16];
-  const int cx = threadIdx.x & 15, ry = threadIdx.x >> 4;
-  const int c = blockIdx.x * 16 + cx;                 // index into the concatenated [dgamma | dbeta] row of 2*D
-  const bool ok = c < 2 * D;
-  const int pass = ok ? c / D : 0, col = ok ? c % D : 0;
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-  int b = ry;
-  for (; b + 48 < nblocks; b += 64) {
-    s0 += partial[((long)b * 2 + pass) * D + col];
-    s1 += partial[((long)(b + 16) * 2 + pass) * D + col];
-    s2 += partial[((long)(b + 32) * 2 + pass) * D + col];
-    s3 += partial[((long)(b + 48) * 2 + pass) * D + col];
-  }
-  for (; b < nblocks; b += 16) s0 += partial[((long)b * 2 + pass) * D + col];
-  red[ry][cx] = (s0 + s1) + (s2 + s3);
-  __syncthreads();
-  if (ry == 0 && ok) {
-    float tot = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) tot += red[r][cx];
-    float* dst = pass == 0 ? dgamma : dbeta;
-    dst[col] += tot;
   }
 }
 
@@ -1903,256 +1114,6 @@ extern "C" int smx_expdecay_mean_sharded(int dtype, const void* S, int64_t lds, 
   if (dtype == SMX_BF16) return expdecay_impl<bf16_t>(S, lds, out, ldo, B, T, D, decay, mode, workspace, STREAM, phase, t_off, T_glob, ends);
   return expdecay_impl<float>(S, lds, out, ldo, B, T, D, decay, mode, workspace, STREAM, phase, t_off, T_glob, ends);
 }
-
-
-extern "C" int smx_layernorm_fwd(int dtype, const void* X, int64_t ldx, const float* gamma, const float* beta, void* Y,
-                                 int64_t ldy, float* stats, int N, int D, float eps, int act, void* stream) {
-  SMX_REQUIRE(X && Y && gamma && beta && N >= 0 && D > 0, "smx_layernorm_fwd: bad arguments");
-  if (N == 0) return SMX_OK;
-  const size_t es = dtype == SMX_BF16 ? 2 : 4;
-  auto ok = [&](const void* p, int64_t ld) { return (reinterpret_cast<uintptr_t>(p) % (4 * es)) == 0 && ld % 4 == 0; };
-  const bool vec = D % 4 == 0 && ok(X, ldx) && ok(Y, ldy) && aligned16(gamma) && aligned16(beta);
-  if (vec && dtype == SMX_BF16 && D > SMX_LN_WG8_FROM && D <= 2048 && D % 8 == 0 && aligned16(X) && aligned16(Y) && ldx % 8 == 0 && ldy % 8 == 0) {
-    // mid-width rows: one workgroup per row, 16-byte accesses (layernorm_fwd_wg8_kernel)
-    int blocks = (N + SMX_LN_WG8_UF - 1) / SMX_LN_WG8_UF;
-    if (blocks > SMX_LN_WG8_FBLOCKS) blocks = SMX_LN_WG8_FBLOCKS;
-    hipLaunchKernelGGL((layernorm_fwd_wg8_kernel<SMX_LN_WG8_UF>), dim3(blocks), dim3(256), 0, STREAM, (const bf16_t*)X, ldx, gamma, beta, (bf16_t*)Y, ldy, stats, N, D, eps, act);
-    return check_launch("smx_layernorm_fwd");
-  }
-  if (vec && D <= 2048) {
-    const int ch = (D + 255) / 256;
-    const int U = ch <= 1 ? 4 : (ch <= 2 ? 2 : 1);
-    int blocks = (N + 4 * U - 1) / (4 * U);
-    if (blocks > 2048) blocks = 2048;
-#define LN_FWD(TT, CH_, U_) hipLaunchKernelGGL((layernorm_fwd_fast<TT, CH_, U_>), dim3(blocks), dim3(256), 0, STREAM, (const TT*)X, ldx, gamma, beta, (TT*)Y, ldy, stats, N, D, eps, act)
-#define LN_FWD_T(TT) do { if (ch <= 1) LN_FWD(TT, 1, 4); else if (ch <= 2) LN_FWD(TT, 2, 2); else if (ch <= 4) LN_FWD(TT, 4, 1); else LN_FWD(TT, 8, 1); } while (0)
-    if (dtype == SMX_BF16) LN_FWD_T(bf16_t); else LN_FWD_T(float);
-#undef LN_FWD_T
-#undef LN_FWD
-    return check_launch("smx_layernorm_fwd");
-  }
-  dim3 grid((N + 3) / 4);
-  if (dtype == SMX_BF16) {
-    if (vec) hipLaunchKernelGGL((layernorm_fwd_kernel<bf16_t, true>), grid, dim3(256), 0, STREAM, (const bf16_t*)X, ldx, gamma, beta, (bf16_t*)Y, ldy, stats, N, D, eps, act);
-    else hipLaunchKernelGGL((layernorm_fwd_kernel<bf16_t, false>), grid, dim3(256), 0, STREAM, (const bf16_t*)X, ldx, gamma, beta, (bf16_t*)Y, ldy, stats, N, D, eps, act);
-  } else {
-    if (vec) hipLaunchKernelGGL((layernorm_fwd_kernel<float, true>), grid, dim3(256), 0, STREAM, (const float*)X, ldx, gamma, beta, (float*)Y, ldy, stats, N, D, eps, act);
-    else hipLaunchKernelGGL((layernorm_fwd_kernel<float, false>), grid, dim3(256), 0, STREAM, (const float*)X, ldx, gamma, beta, (float*)Y, ldy, stats, N, D, eps, act);
-  }
-  return check_launch("smx_layernorm_fwd");
-}
-
-extern "C" int smx_layernorm_fwd_x32(int dtype, const float* X, int64_t ldx, const float* gamma, const float* beta, void* Y,
-                                     int64_t ldy, float* stats, int N, int D, float eps, int act, void* stream) {
-  SMX_REQUIRE(X && Y && gamma && beta && N >= 0 && D > 0, "smx_layernorm_fwd_x32: bad arguments");
-  if (dtype == SMX_F32) return smx_layernorm_fwd(dtype, X, ldx, gamma, beta, Y, ldy, stats, N, D, eps, act, stream);
-  SMX_REQUIRE(dtype == SMX_BF16, "smx_layernorm_fwd_x32: bad dtype");
-  if (N == 0) return SMX_OK;
-  const bool vec = D % 4 == 0 && D <= 2048 && aligned16(X) && ldx % 4 == 0 && aligned8(Y) && ldy % 4 == 0 && aligned16(gamma) && aligned16(beta);
-  if (!vec) return fail(SMX_EUNSUPPORTED, "smx_layernorm_fwd_x32: needs D %% 4 == 0, D <= 2048 and aligned rows");
-  const int ch = (D + 255) / 256;
-  const int U = ch <= 1 ? 4 : (ch <= 2 ? 2 : 1);
-  int blocks = (N + 4 * U - 1) / (4 * U);
-  if (blocks > 2048) blocks = 2048;
-#define LN_FWDX(CH_, U_) hipLaunchKernelGGL((layernorm_fwd_fast<bf16_t, CH_, U_, float>), dim3(blocks), dim3(256), 0, STREAM, X, ldx, gamma, beta, (bf16_t*)Y, ldy, stats, N, D, eps, act)
-  if (ch <= 1) LN_FWDX(1, 4); else if (ch <= 2) LN_FWDX(2, 2); else if (ch <= 4) LN_FWDX(4, 1); else LN_FWDX(8, 1);
-#undef LN_FWDX
-  return check_launch("smx_layernorm_fwd_x32");
-}
-
-extern "C" int smx_layernorm_fwd_pair_x32(int dtype2, const float* X, int64_t ldx, const float* gamma1, const float* beta1, float eps1,
-                                          float* Y1, int64_t ldy1, float* stats1, const float* gamma2, const float* beta2,
-                                          float eps2, void* Y2, int64_t ldy2, float* stats2, int N, int D, void* stream) {
-  SMX_REQUIRE(X && Y1 && Y2 && gamma1 && beta1 && gamma2 && beta2 && N >= 0 && D > 0, "smx_layernorm_fwd_pair_x32: bad arguments");
-  SMX_REQUIRE(dtype2 == SMX_BF16 || dtype2 == SMX_F32, "smx_layernorm_fwd_pair_x32: bad dtype");
-  if (N == 0) return SMX_OK;
-  const bool vec = D % 4 == 0 && D <= 2048 && aligned16(X) && ldx % 4 == 0 && aligned16(Y1) && ldy1 % 4 == 0 &&
-                   (dtype2 == SMX_BF16 ? aligned8(Y2) : aligned16(Y2)) && ldy2 % 4 == 0 && aligned16(gamma1) && aligned16(beta1) &&
-                   aligned16(gamma2) && aligned16(beta2);
-  if (!vec) return fail(SMX_EUNSUPPORTED, "smx_layernorm_fwd_pair_x32: needs D %% 4 == 0, D <= 2048 and aligned rows");
-  const int ch = (D + 255) / 256;
-  const int U = ch <= 1 ? 4 : (ch <= 2 ? 2 : 1);          // (the launch geometry of layernorm_fwd_fast: bit-identical sums)
-  int blocks = (N + 4 * U - 1) / (4 * U);
-  if (blocks > 2048) blocks = 2048;
-#define LN_PAIR(TT, CH_, U_) hipLaunchKernelGGL((layernorm_fwd_pair_fast<TT, CH_, U_>), dim3(blocks), dim3(256), 0, STREAM, X, ldx, gamma1, beta1, eps1, Y1, ldy1, stats1, gamma2, beta2, eps2, (TT*)Y2, ldy2, stats2, N, D)
-#define LN_PAIR_T(TT) do { if (ch <= 1) LN_PAIR(TT, 1, 4); else if (ch <= 2) LN_PAIR(TT, 2, 2); else if (ch <= 4) LN_PAIR(TT, 4, 1); else LN_PAIR(TT, 8, 1); } while (0)
-  if (dtype2 == SMX_BF16) LN_PAIR_T(bf16_t); else LN_PAIR_T(float);
-#undef LN_PAIR_T
-#undef LN_PAIR
-  return check_launch("smx_layernorm_fwd_pair_x32");
-}
-
-#ifndef SMX_LNB_BLOCKS
-#define SMX_LNB_BLOCKS 1024
-#endif
-static int ln_bwd_blocks(int N) {
-  int blocks = (N + 3) / 4;                              // one row per wave and pass when the rows allow it (D <= 512 keeps ONE row in flight)
-  return blocks > SMX_LNB_BLOCKS ? SMX_LNB_BLOCKS : (blocks < 1 ? 1 : blocks);
-}
-
-#ifndef SMX_LNB_U1
-#define SMX_LNB_U1 2      // rows in flight per wave for D <= 256
-#endif
-#ifndef SMX_LNB_U2
-#define SMX_LNB_U2 1      // ... for 256 < D <= 512 (104 registers = 4 waves per SIMD = the whole 1024-block grid resident; two rows in flight: 75 -> 62 us at 64000 x 512, tools/rowkernels_bench.py)
-#endif
-template <typename T>
-static int ln_bwd_impl(const void* dY, int64_t lddy, const void* X, int64_t ldx, const float* gamma, const float* beta,
-                       int act, const float* stats,
-                       const void* R, int64_t ldr, void* dX, int64_t lddx, float* dgamma, float* dbeta, int N, int D,
-                       float* partial, hipStream_t s, LnSecond sec) {
-  auto ok = [&](const void* p, int64_t ld) { return p == nullptr || ((reinterpret_cast<uintptr_t>(p) % (4 * sizeof(T))) == 0 && ld % 4 == 0); };
-  const bool vec = D % 4 == 0 && ok(dY, lddy) && ok(X, ldx) && ok(R, ldr) && ok(dX, lddx) && ok(sec.dX2, sec.ld);
-  if (sec.dX2 && D > 2048) return fail(SMX_EUNSUPPORTED, "smx_layernorm_bwd2: the second output needs D <= 2048");
-  const int blocks = ln_bwd_blocks(N);
-  dim3 grid(blocks);
-  if constexpr (sizeof(T) == 2) {
-    auto ok16 = [&](const void* p, int64_t ld) { return p == nullptr || ((reinterpret_cast<uintptr_t>(p) % 16) == 0 && ld % 8 == 0); };
-    if (vec && !sec.dX2 && D > SMX_LN_WG8_FROM && D <= 2048 && D % 8 == 0 && ok16(dY, lddy) && ok16(X, ldx) && ok16(R, ldr) && ok16(dX, lddx)) {
-      hipLaunchKernelGGL((layernorm_bwd_wg8_kernel<false, bf16_t>), grid, dim3(256), 0, s, (const bf16_t*)dY, lddy, (const bf16_t*)X, ldx, gamma, beta, act, stats,
-                         (const bf16_t*)R, ldr, (bf16_t*)dX, lddx, partial, N, D, (const bf16_t*)nullptr, 0, SMX_ACT_NONE);
-      if (dgamma) hipLaunchKernelGGL(ln_param_reduce_kernel, dim3((2 * D + 15) / 16), dim3(256), 0, s, partial, blocks, D, dgamma, dbeta);
-      return check_launch("smx_layernorm_bwd");
-    }
-  }
-#define LN_BWD(VW, CH) hipLaunchKernelGGL((layernorm_bwd_kernel<T, VW, CH, (VW == 4 && CH == 1 ? SMX_LNB_U1 : (CH <= 2 ? SMX_LNB_U2 : 1))>), grid, dim3(256), 0, s, (const T*)dY, lddy, (const T*)X, ldx, gamma, beta, act, stats, (const T*)R, ldr, (T*)dX, lddx, partial, N, D, sec)
-  if (vec) {
-    if (D <= 256) LN_BWD(4, 1);
-    else if (D <= 512) LN_BWD(4, 2);
-    else if (D <= 1024) LN_BWD(4, 4);
-    else if (D <= 2048) LN_BWD(4, 8);
-    else if (D <= 3072) hipLaunchKernelGGL((layernorm_bwd_wide4_kernel<T, 3>), grid, dim3(256), 0, s, (const T*)dY, lddy, (const T*)X, ldx, gamma, beta, act, stats, (const T*)R, ldr, (T*)dX, lddx, partial, N, D);
-    else if (D <= 4096) hipLaunchKernelGGL((layernorm_bwd_wide4_kernel<T, 4>), grid, dim3(256), 0, s, (const T*)dY, lddy, (const T*)X, ldx, gamma, beta, act, stats, (const T*)R, ldr, (T*)dX, lddx, partial, N, D);
-    else if (D <= 4096) hipLaunchKernelGGL((layernorm_bwd_wide_kernel<T, 16>), grid, dim3(256), 0, s, (const T*)dY, lddy, (const T*)X, ldx, gamma, beta, act, stats, (const T*)R, ldr, (T*)dX, lddx, partial, N, D);
-    else return fail(SMX_EUNSUPPORTED, "smx_layernorm_bwd: D=%d > 4096", D);
-  } else {
-    if (D <= 256) LN_BWD(1, 4);
-    else if (D <= 1024) LN_BWD(1, 16);
-    else if (D <= 2048) LN_BWD(1, 32);
-    else if (D <= 4096) hipLaunchKernelGGL((layernorm_bwd_wide_kernel<T, 16>), grid, dim3(256), 0, s, (const T*)dY, lddy, (const T*)X, ldx, gamma, beta, act, stats, (const T*)R, ldr, (T*)dX, lddx, partial, N, D);
-    else return fail(SMX_EUNSUPPORTED, "smx_layernorm_bwd: D=%d > 4096", D);
-  }
-#undef LN_BWD
-  if (dgamma)   // (NULL dgamma/dbeta: the partial rows stay in the workspace for a deferred smx_reduce_jobs)
-    hipLaunchKernelGGL(ln_param_reduce_kernel, dim3((2 * D + 15) / 16), dim3(256), 0, s, partial, blocks, D, dgamma, dbeta);
-  return check_launch("smx_layernorm_bwd");
-}
-
-extern "C" int smx_layernorm_bwd2(int dtype, const void* dY, int64_t lddy, const void* X, int64_t ldx, const float* gamma,
-                                  const float* beta, int act, const float* stats, const void* R, int64_t ldr, void* dX, int64_t lddx, float* dgamma,
-                                  float* dbeta, int N, int D, void* workspace, void* dX2, int64_t lddx2, float alpha2,
-                                  const uint8_t* row_mask2, float drop_p2, uint64_t drop_seed2, const uint64_t* epoch, void* stream) {
-  SMX_REQUIRE(dY && X && gamma && beta && stats && dX && workspace && D > 0 && ((dgamma == nullptr) == (dbeta == nullptr)),
-              "smx_layernorm_bwd: bad arguments");
-  SMX_REQUIRE(drop_p2 >= 0.f && drop_p2 < 1.f, "smx_layernorm_bwd2: 0 <= drop_p < 1");
-  if (N == 0) return SMX_OK;
-  LnSecond sec;
-  sec.slabs = nullptr; sec.nslab = 0; sec.slab_stride = 0;
-  sec.dX2 = dX2; sec.ld = lddx2; sec.alpha = alpha2; sec.mask = row_mask2;
-  sec.thresh = (uint32_t)((double)drop_p2 * 4294967296.0); sec.scale = 1.f / (1.f - drop_p2); sec.seed = drop_seed2; sec.epoch = epoch;
-  if (dtype == SMX_BF16) return ln_bwd_impl<bf16_t>(dY, lddy, X, ldx, gamma, beta, act, stats, R, ldr, dX, lddx, dgamma, dbeta, N, D, (float*)workspace, STREAM, sec);
-  return ln_bwd_impl<float>(dY, lddy, X, ldx, gamma, beta, act, stats, R, ldr, dX, lddx, dgamma, dbeta, N, D, (float*)workspace, STREAM, sec);
-}
-extern "C" int smx_layernorm_bwd2_x32(int dtype, const void* dY, int64_t lddy, const float* X, int64_t ldx, const float* gamma,
-                                      const float* beta, int act, const float* stats, const void* R, int64_t ldr, void* dX, int64_t lddx,
-                                      float* dgamma, float* dbeta, int N, int D, void* workspace, void* dX2, int64_t lddx2, float alpha2,
-                                      const uint8_t* row_mask2, float drop_p2, uint64_t drop_seed2, const uint64_t* epoch, void* stream) {
-  if (dtype == SMX_F32)
-    return smx_layernorm_bwd2(dtype, dY, lddy, X, ldx, gamma, beta, act, stats, R, ldr, dX, lddx, dgamma, dbeta, N, D, workspace, dX2, lddx2,
-                              alpha2, row_mask2, drop_p2, drop_seed2, epoch, stream);
-  SMX_REQUIRE(dtype == SMX_BF16 && dY && X && gamma && beta && stats && dX && workspace && D > 0 && ((dgamma == nullptr) == (dbeta == nullptr)),
-              "smx_layernorm_bwd2_x32: bad arguments");
-  SMX_REQUIRE(drop_p2 >= 0.f && drop_p2 < 1.f, "smx_layernorm_bwd2_x32: 0 <= drop_p < 1");
-  if (N == 0) return SMX_OK;
-  typedef bf16_t T;
-  auto ok = [&](const void* p, int64_t ld) { return p == nullptr || ((reinterpret_cast<uintptr_t>(p) % 8) == 0 && ld % 4 == 0); };
-  const bool vec = D % 4 == 0 && D <= 2048 && ok(dY, lddy) && aligned16(X) && ldx % 4 == 0 && ok(R, ldr) && ok(dX, lddx) && ok(dX2, lddx2);
-  if (!vec) return fail(SMX_EUNSUPPORTED, "smx_layernorm_bwd2_x32: needs D %% 4 == 0, D <= 2048 and aligned rows");
-  LnSecond sec;
-  sec.slabs = nullptr; sec.nslab = 0; sec.slab_stride = 0;
-  sec.dX2 = dX2; sec.ld = lddx2; sec.alpha = alpha2; sec.mask = row_mask2;
-  sec.thresh = (uint32_t)((double)drop_p2 * 4294967296.0); sec.scale = 1.f / (1.f - drop_p2); sec.seed = drop_seed2; sec.epoch = epoch;
-  const int blocks = ln_bwd_blocks(N);
-  dim3 grid(blocks);
-  float* partial = reinterpret_cast<float*>(workspace);
-  hipStream_t s = STREAM;
-  {
-    auto ok16 = [&](const void* p, int64_t ld) { return p == nullptr || ((reinterpret_cast<uintptr_t>(p) % 16) == 0 && ld % 8 == 0); };
-    if (!dX2 && D > SMX_LN_WG8_FROM && D % 8 == 0 && ok16(dY, lddy) && ldx % 8 == 0 && ok16(R, ldr) && ok16(dX, lddx)) {
-      hipLaunchKernelGGL((layernorm_bwd_wg8_kernel<false, float>), grid, dim3(256), 0, s, (const bf16_t*)dY, lddy, X, ldx, gamma, beta, act, stats,
-                         (const bf16_t*)R, ldr, (bf16_t*)dX, lddx, partial, N, D, (const bf16_t*)nullptr, 0, SMX_ACT_NONE);
-      if (dgamma) hipLaunchKernelGGL(ln_param_reduce_kernel, dim3((2 * D + 15) / 16), dim3(256), 0, s, partial, blocks, D, dgamma, dbeta);
-      return check_launch("smx_layernorm_bwd2_x32");
-    }
-  }
-#define LN_BWDX(CH) hipLaunchKernelGGL((layernorm_bwd_kernel<T, 4, CH, (CH == 1 ? SMX_LNB_U1 : (CH <= 2 ? SMX_LNB_U2 : 1)), float>), grid, dim3(256), 0, s, (const T*)dY, lddy, X, ldx, gamma, beta, act, stats, (const T*)R, ldr, (T*)dX, lddx, partial, N, D, sec)
-  if (D <= 256) LN_BWDX(1); else if (D <= 512) LN_BWDX(2); else if (D <= 1024) LN_BWDX(4); else LN_BWDX(8);
-#undef LN_BWDX
-  if (dgamma) hipLaunchKernelGGL(ln_param_reduce_kernel, dim3((2 * D + 15) / 16), dim3(256), 0, s, partial, blocks, D, dgamma, dbeta);
-  return check_launch("smx_layernorm_bwd2_x32");
-}
-extern "C" int smx_layernorm_bwd(int dtype, const void* dY, int64_t lddy, const void* X, int64_t ldx, const float* gamma,
-                                 const float* beta, int act, const float* stats, const void* R, int64_t ldr, void* dX, int64_t lddx, float* dgamma,
-                                 float* dbeta, int N, int D, void* workspace, void* stream) {
-  return smx_layernorm_bwd2(dtype, dY, lddy, X, ldx, gamma, beta, act, stats, R, ldr, dX, lddx, dgamma, dbeta, N, D, workspace, nullptr, 0,
-                            1.f, nullptr, 0.f, 0, nullptr, stream);
-}
-
-// The LayerNorm backward whose incoming gradient is the SUM of float32 split-K slabs (smx_gemm_panel_slabs: the dgrad of the Linear
-// behind the LayerNorm, K cut into nslab slices): one launch instead of reducer + LayerNorm backward.  x_f32: the LayerNorm input is
-// the float32 residual stream (else dtype T).  Everything else as smx_layernorm_bwd2 (res, second output, fused activation).
-extern "C" int smx_layernorm_bwd2_slabs(int dtype, const float* slabs, int nslab, int64_t slab_stride, const void* X, int64_t ldx, int x_f32,
-                                        const float* gamma, const float* beta, int act, const float* stats, const void* R, int64_t ldr,
-                                        void* dX, int64_t lddx, int N, int D, void* workspace, void* dX2, int64_t lddx2, float alpha2,
-                                        const uint8_t* row_mask2, float drop_p2, uint64_t drop_seed2, const uint64_t* epoch, void* stream) {
-  SMX_REQUIRE(dtype == SMX_BF16 && slabs && nslab >= 1 && nslab <= 16 && X && gamma && beta && stats && dX && workspace && D > 0,
-              "smx_layernorm_bwd2_slabs: bad arguments");
-  SMX_REQUIRE(drop_p2 >= 0.f && drop_p2 < 1.f, "smx_layernorm_bwd2_slabs: 0 <= drop_p < 1");
-  if (N == 0) return SMX_OK;
-  typedef bf16_t T;
-  auto ok = [&](const void* p, int64_t ld) { return p == nullptr || ((reinterpret_cast<uintptr_t>(p) % 8) == 0 && ld % 4 == 0); };
-  const bool vec = D % 4 == 0 && D <= 2048 && aligned16(slabs) && slab_stride % 4 == 0 && (x_f32 ? aligned16(X) : ok(X, ldx)) && ldx % 4 == 0 &&
-                   ok(R, ldr) && ok(dX, lddx) && ok(dX2, lddx2);
-  if (!vec) return fail(SMX_EUNSUPPORTED, "smx_layernorm_bwd2_slabs: needs D %% 4 == 0, D <= 2048 and aligned rows");
-  LnSecond sec;
-  sec.slabs = slabs; sec.nslab = nslab; sec.slab_stride = slab_stride;
-  sec.dX2 = dX2; sec.ld = lddx2; sec.alpha = alpha2; sec.mask = row_mask2;
-  sec.thresh = (uint32_t)((double)drop_p2 * 4294967296.0); sec.scale = 1.f / (1.f - drop_p2); sec.seed = drop_seed2; sec.epoch = epoch;
-  const int blocks = ln_bwd_blocks(N);
-  dim3 grid(blocks);
-  float* partial = reinterpret_cast<float*>(workspace);
-  hipStream_t s = STREAM;
-#define LN_BWDS(CH, TXX) hipLaunchKernelGGL((layernorm_bwd_kernel<T, 4, CH, 1, TXX>), grid, dim3(256), 0, s, (const T*)nullptr, 0, (const TXX*)X, ldx, gamma, beta, act, stats, (const T*)R, ldr, (T*)dX, lddx, partial, N, D, sec)
-  if (x_f32) { if (D <= 256) LN_BWDS(1, float); else if (D <= 512) LN_BWDS(2, float); else if (D <= 1024) LN_BWDS(4, float); else LN_BWDS(8, float); }
-  else { if (D <= 256) LN_BWDS(1, T); else if (D <= 512) LN_BWDS(2, T); else if (D <= 1024) LN_BWDS(4, T); else LN_BWDS(8, T); }
-#undef LN_BWDS
-  return check_launch("smx_layernorm_bwd2_slabs");
-}
-
-// dZ = zact'(Z) * (LayerNorm backward of dY), for a LayerNorm whose input is X = zact(Z) (the CSGU norm of the cgMLP: X = the gate
-// half of GELU(channel_proj1(.)), Branchformer.py:84-96 of the reference's ConvolutionBranch).  bf16, D <= 2048, D % 8 == 0,
-// 16-byte aligned rows; dgamma / dbeta NULL = the partial rows stay in the workspace (smx_layernorm_bwd_workspace bytes).
-extern "C" int smx_layernorm_bwd_preact(int dtype, const void* dY, int64_t lddy, const void* X, int64_t ldx, const float* gamma,
-                                        const float* beta, int act, const float* stats, const void* Z, int64_t ldz, int zact,
-                                        void* dX, int64_t lddx, float* dgamma, float* dbeta, int N, int D, void* workspace, void* stream) {
-  SMX_REQUIRE(dY && X && gamma && beta && stats && Z && dX && workspace && D > 0 && ((dgamma == nullptr) == (dbeta == nullptr)),
-              "smx_layernorm_bwd_preact: bad arguments");
-  if (N == 0) return SMX_OK;
-  auto ok16 = [&](const void* p, int64_t ld) { return (reinterpret_cast<uintptr_t>(p) % 16) == 0 && ld % 8 == 0; };
-  if (act != SMX_ACT_NONE) return fail(SMX_EUNSUPPORTED, "smx_layernorm_bwd_preact: a LayerNorm without a fused activation of its own");
-  if (dtype != SMX_BF16 || D > 2048 || D % 8 != 0 || !ok16(dY, lddy) || !ok16(X, ldx) || !ok16(Z, ldz) || !ok16(dX, lddx))
-    return fail(SMX_EUNSUPPORTED, "smx_layernorm_bwd_preact: needs bf16, D <= 2048, D %% 8 == 0 and 16-byte aligned rows");
-  const int blocks = ln_bwd_blocks(N);
-  float* partial = reinterpret_cast<float*>(workspace);
-  hipStream_t s = STREAM;
-  hipLaunchKernelGGL((layernorm_bwd_wg8_kernel<true, bf16_t>), dim3(blocks), dim3(256), 0, s, (const bf16_t*)dY, lddy, (const bf16_t*)X, ldx, gamma, beta,
-                     act, stats, (const bf16_t*)nullptr, 0, (bf16_t*)dX, lddx, partial, N, D, (const bf16_t*)Z, ldz, zact);
-  if (dgamma) hipLaunchKernelGGL(ln_param_reduce_kernel, dim3((2 * D + 15) / 16), dim3(256), 0, s, partial, blocks, D, dgamma, dbeta);
-  return check_launch("smx_layernorm_bwd_preact");
-}
-
-extern "C" int smx_layernorm_bwd_blocks(int N) { return ln_bwd_blocks(N); }
-extern "C" size_t smx_layernorm_bwd_workspace(int N, int D) { return (size_t)ln_bwd_blocks(N) * 2 * D * sizeof(float); }
 
 static const int ACT_BWD_RS = 32;
 static const int ACT_BWD_YMAX = 512;   // row-strip workgroups per column block (= partial rows of the bias reduction)

@@ -10,7 +10,7 @@
 // LayerNorm-fused GEMM tile (128 whole rows per workgroup) would leave 7/8 of the chip idle.  Reference lines: the Linear +
 // dropout + residual + LayerNorm chains of Conformer.py:458-476,507,530-536 and summary_mixing.py:282-284.
 //
-// Lane / chunk layout and the reduction trees are those of layernorm_fwd_fast / layernorm_fwd_pair_fast (rowwise.hip): lane l of
+// Lane / chunk layout and the reduction trees are those of layernorm_fwd_fast / layernorm_fwd_pair_fast (layernorm.hip): lane l of
 // chunk i owns columns (l + 64 i) * 4 .. + 3; the statistics equal the standalone kernels' to an ulp.
 #include "smx_common.h"
 

@@ -34,7 +34,7 @@ from . import sequence_parallel as SP
 _PANEL = os.environ.get("SMX_PANEL", "1") != "0"
 _PANEL_MIN_ROWS = int(os.environ.get("SMX_PANEL_MIN_ROWS", "2048"))   # (round 6: 64- / 32-row panels below 12 288 rows, chosen by the library)
 
-# Split-K over workgroups for the Linears of a SMALL batch (smx_gemm_panel_slabs + smx_slab_epilogue / smx_layernorm_bwd2_slabs; round 6):
+# Split-K over workgroups for the Linears of a SMALL batch (smx_gemm_panel_slabs + smx_slab_epilogue / smx_layernorm_bwd from slabs; round 6):
 # panel-sized K-slices whose slabs the row kernel that follows the Linear anyway sums (its epilogue + the LayerNorm, or the LayerNorm
 # backward behind a dgrad).  Up to 2048 frames: at 3750 the slab traffic eats the gain (tools/experiments/r06_smalln/README.md, 4.).
 _SPLITK = os.environ.get("SMX_SPLITK", "1") != "0"
@@ -47,7 +47,7 @@ _LN_FUSE, _LN_FUSE_FWD, _LN_FUSE_BWD = (os.environ.get("SMX_LN_FUSE", "1").lower
 # serial chain (K loop, four epilogue phases) IS the kernel's duration.  Fused from 17 500 rows (was 36 864 before round 6; same-box
 # A/B of the steps: tools/experiments/r06_smalln/README.md - C2b B = 32 (16 000 rows) 7.66 | 8.28 ms separate | fused, B = 36 9.81 | 9.64).
 _LN_FUSE_MIN_ROWS = int(os.environ.get("SMX_LN_FUSE_MIN_ROWS", "17500"))
-# norm2 of a Conformer layer + the first LayerNorm of the next layer in ONE pass over the float32 stream (smx_layernorm_fwd_pair_x32;
+# norm2 of a Conformer layer + the first LayerNorm of the next layer in ONE pass over the float32 stream (smx_layernorm_fwd, pair form;
 # tests switch it off to compare with the two-launch path)
 _LN_PAIR = True
 
@@ -1164,31 +1164,21 @@ def ln_fwd(x, w, b, eps, need_bwd, act=L.ACT_NONE, wp=None, bp=None, pre=None, o
         preact = (z, zact): x = zact(z); return the gradient w.r.t. z (check ops.layernorm_bwd_preact_ok first)."""
         gw = gacc(wp).view(-1) if wp is not None else gacc(w)
         gb = gacc(bp).view(-1) if bp is not None else gacc(b)
-        if preact is not None:
-            assert res is None and second is None
-            N, D = x.shape
-            if _Deferred.enabled and gw is not None and gb is not None:
-                ws = deferred_ws(gw.data_ptr(), L.lib().smx_layernorm_bwd_workspace(N, D), x.device)
-                dz = ops.layernorm_bwd_preact(dy, x, w.detach(), b.detach(), stats, preact[0], preact[1], None, None, act, ws=ws, dx_out=out)
-                nb = L.lib().smx_layernorm_bwd_blocks(N)
-                defer(ws.data_ptr(), gw, 2 * D, nb, 1, D)
-                defer(ws.data_ptr() + 4 * D, gb, 2 * D, nb, 1, D)
-                return dz
-            return ops.layernorm_bwd_preact(dy, x, w.detach(), b.detach(), stats, preact[0], preact[1], gw, gb, act, dx_out=out)
+        assert preact is None or (res is None and second is None)
         wide2 = None
         if second is not None and x.shape[1] > 2048:       # the fused second output exists for D <= 2048: do it in separate
             wide2, second = second, None                   # passes, but ALWAYS return the pair the caller unpacks (ADVICE r02)
-        if isinstance(dy, ops.Slabs) and not (_Deferred.enabled and gw is not None and gb is not None and wide2 is None):
+        deferred = _Deferred.enabled and gw is not None and gb is not None
+        if isinstance(dy, ops.Slabs) and not (deferred and wide2 is None):
             dy = dy.sum(x.dtype if x.dtype != torch.float32 else torch.bfloat16)      # (not reached by the encoder layers: plain torch)
-        if _Deferred.enabled and gw is not None and gb is not None:
-            N, D = x.shape
-            ws = deferred_ws(gw.data_ptr(), L.lib().smx_layernorm_bwd_workspace(N, D), x.device)
-            dx = ops.layernorm_bwd(dy, x, w.detach(), b.detach(), stats, None, None, res, act, ws=ws, dx_out=out, second=second)
+        N, D = x.shape
+        ws = deferred_ws(gw.data_ptr(), L.lib().smx_layernorm_bwd_workspace(N, D), x.device) if deferred else None
+        dx = ops.layernorm_bwd(dy, x, w.detach(), b.detach(), stats, None if deferred else gw, None if deferred else gb, res, act, ws=ws,
+                               dx_out=out, second=second, preact=preact)
+        if deferred:
             nb = L.lib().smx_layernorm_bwd_blocks(N)
             defer(ws.data_ptr(), gw, 2 * D, nb, 1, D)
             defer(ws.data_ptr() + 4 * D, gb, 2 * D, nb, 1, D)
-        else:
-            dx = ops.layernorm_bwd(dy, x, w.detach(), b.detach(), stats, gw, gb, res, act, dx_out=out, second=second)
         if wide2 is not None:
             a2, m2, d2 = wide2[:3]
             dx2 = ops.dropout(dx, d2[0], d2[1]) if (d2 is not None and d2[0] > 0.0) else dx

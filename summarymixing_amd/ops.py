@@ -506,49 +506,44 @@ def expdecay_mean_sharded(x, out, B, T, decay, reverse, t_off, T_glob, phase, en
                                               _p(ends), _p(ws), _stream()), "smx_expdecay_mean_sharded")
 
 
-def layernorm_fwd(x, gamma, beta, eps, want_stats, act=L.ACT_NONE, out_dtype=None):
-    """out_dtype (default x.dtype): bf16 output of a float32 input = LayerNorm of the fp32 residual stream feeding a bf16 GEMM
-    (smx_layernorm_fwd_x32)."""
+def layernorm_fwd(x, gamma, beta, eps, want_stats, act=L.ACT_NONE, out_dtype=None, pair=None):
+    """y = act(LayerNorm(x)) (smx_layernorm_fwd).  out_dtype (default x.dtype): bf16 output of a float32 input = LayerNorm of the
+    fp32 residual stream feeding a bf16 GEMM.  pair = (gamma2, beta2, eps2): the float32 stream x through TWO LayerNorms in one pass
+    (the layer-final norm2 + the next layer's first LayerNorm; check layernorm_pair_ok first): y = LN(x) float32, y2 = LN2(y) in
+    out_dtype; returns (y, stats, y2, stats2)."""
     N, D = x.shape
     out_dtype = out_dtype or x.dtype
-    y = torch.empty((N, D), dtype=out_dtype, device=x.device)
+    y = torch.empty((N, D), dtype=torch.float32 if pair is not None else out_dtype, device=x.device)
     stats = torch.empty((N, 2), dtype=torch.float32, device=x.device) if want_stats else None
-    px, ldx = _mat(x)
-    tok = _pb(f"layernorm_fwd ({N}x{D})", N * D * (_es(x) + _es(y)))
-    if out_dtype != x.dtype:
-        assert x.dtype == torch.float32, "mixed LayerNorm: float32 in, compute dtype out"
-        L.check(L.lib().smx_layernorm_fwd_x32(dt(y), px, ldx, _p(gamma), _p(beta), _p(y), D, _p(stats), N, D, eps, act, _stream()),
-                "smx_layernorm_fwd_x32")
+    a = L.LnFwd(dtype=dt(y), x_f32=int(x.dtype == torch.float32), ldy=D, stats=_p(stats), eps=eps, act=act, N=N, D=D, gamma=_p(gamma),
+                beta=_p(beta), Y=_p(y))
+    a.X, a.ldx = _mat(x)
+    if pair is None:
+        assert out_dtype == x.dtype or x.dtype == torch.float32, "mixed LayerNorm: float32 in, compute dtype out"
+        tok = _pb(f"layernorm_fwd ({N}x{D})", N * D * (_es(x) + _es(y)))
     else:
-        L.check(L.lib().smx_layernorm_fwd(dt(x), px, ldx, _p(gamma), _p(beta), _p(y), D, _p(stats), N, D, eps, act, _stream()),
-                "smx_layernorm_fwd")
+        y2 = torch.empty((N, D), dtype=out_dtype, device=x.device)
+        st2 = torch.empty((N, 2), dtype=torch.float32, device=x.device) if want_stats else None
+        a.gamma2, a.beta2, a.eps2 = _p(pair[0]), _p(pair[1]), pair[2]
+        a.Y2, a.ldy2, a.stats2, a.dtype2 = _p(y2), D, _p(st2), dt(y2)
+        tok = _pb(f"layernorm_fwd_pair ({N}x{D})", N * D * (4 + 4 + _es(y2)))
+    L.check(L.lib().smx_layernorm_fwd(ctypes.byref(a), _stream()), "smx_layernorm_fwd")
     _pe(tok)
-    return y, stats
+    return (y, stats) if pair is None else (y, stats, y2, st2)
 
 
 def layernorm_pair_ok(x, out_dtype, *affine):
-    """Can smx_layernorm_fwd_pair_x32 take this float32 stream tensor - and these gamma / beta vectors?  The kernel reads all four
-    with 16-byte loads and returns SMX_EUNSUPPORTED for an unaligned one (a parameter that is a view at an odd offset of a flat
-    buffer): checked here so that the caller takes the two-launch path instead of failing."""
+    """Can smx_layernorm_fwd take this float32 stream tensor - and these gamma / beta vectors - in its pair form?  The kernel reads
+    all four with 16-byte loads and returns SMX_EUNSUPPORTED for an unaligned one (a parameter that is a view at an odd offset of a
+    flat buffer): checked here so that the caller takes the two-launch path instead of failing."""
     return (x.dtype == torch.float32 and x.is_cuda and x.shape[1] % 4 == 0 and x.shape[1] <= 2048 and x.stride(1) == 1
             and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0 and out_dtype in (torch.bfloat16, torch.float32)
             and all(v.is_contiguous() and v.data_ptr() % 16 == 0 for v in affine))
 
 
 def layernorm_fwd_pair(x, gamma1, beta1, eps1, gamma2, beta2, eps2, want_stats, out_dtype):
-    """(y1, stats1, y2, stats2): y1 = LN1(x) float32, y2 = LN2(y1) in out_dtype, one pass over the float32 stream x
-    (smx_layernorm_fwd_pair_x32: the layer-final norm2 + the next layer's first LayerNorm)."""
-    N, D = x.shape
-    y1 = torch.empty((N, D), dtype=torch.float32, device=x.device)
-    y2 = torch.empty((N, D), dtype=out_dtype, device=x.device)
-    st1 = torch.empty((N, 2), dtype=torch.float32, device=x.device) if want_stats else None
-    st2 = torch.empty((N, 2), dtype=torch.float32, device=x.device) if want_stats else None
-    px, ldx = _mat(x)
-    tok = _pb(f"layernorm_fwd_pair ({N}x{D})", N * D * (4 + 4 + _es(y2)))
-    L.check(L.lib().smx_layernorm_fwd_pair_x32(dt(y2), px, ldx, _p(gamma1), _p(beta1), eps1, _p(y1), D, _p(st1), _p(gamma2), _p(beta2),
-                                               eps2, _p(y2), D, _p(st2), N, D, _stream()), "smx_layernorm_fwd_pair_x32")
-    _pe(tok)
-    return y1, st1, y2, st2
+    """(y1, stats1, y2, stats2): layernorm_fwd's pair form (the layer-final norm2 + the next layer's first LayerNorm)."""
+    return layernorm_fwd(x, gamma1, beta1, eps1, want_stats, out_dtype=out_dtype, pair=(gamma2, beta2, eps2))
 
 
 class Slabs:
@@ -563,71 +558,64 @@ class Slabs:
         return self.t.sum(0).to(dtype)
 
 
-def layernorm_bwd(dy, x, gamma, beta, stats, dgamma, dbeta, res=None, act=L.ACT_NONE, ws=None, dx_out=None, second=None):
-    """ws: caller-owned workspace; with dgamma = dbeta = None the partial rows stay in it for a deferred reduce_jobs.
-    dx_out: optional (N, D) destination view (e.g. a column slice of a wider buffer).
-    second = (alpha, row_mask_u8 | None, (p, seed) | None): also return dx2 = alpha * D(dx) * mask (smx_layernorm_bwd2)."""
+def layernorm_bwd(dy, x, gamma, beta, stats, dgamma, dbeta, res=None, act=L.ACT_NONE, ws=None, dx_out=None, second=None, preact=None):
+    """dx = res + LayerNorm-backward(dy) (smx_layernorm_bwd).  ws: caller-owned workspace; with dgamma = dbeta = None the partial rows
+    stay in it for a deferred reduce_jobs.  dx_out: optional (N, D) destination view (e.g. a column slice of a wider buffer).
+    dy: a gradient tensor, or Slabs (the float32 split-K slabs of the dgrad behind the LayerNorm: reducer and LayerNorm backward
+    in one launch; dgamma = dbeta = None and ws required).
+    second = (alpha, row_mask_u8 | None, (p, seed) | None): also return dx2 = alpha * D(dx) * mask.
+    preact = (z, zact): x = zact(z); return the gradient w.r.t. z (check layernorm_bwd_preact_ok first)."""
     N, D = x.shape
     gdt = dy.dtype                                       # gradient dtype; x may be float32 next to bf16 gradients (fp32 residual stream)
+    assert x.dtype == gdt or x.dtype == torch.float32
     dx = dx_out if dx_out is not None else torch.empty((N, D), dtype=gdt, device=x.device)
-    if isinstance(dy, Slabs):
-        # the incoming gradient is the sum of float32 split-K slabs: reducer + LayerNorm backward in one launch (smx_layernorm_bwd2_slabs)
+    slabs = isinstance(dy, Slabs)
+    if slabs:
         assert dgamma is None and dbeta is None and ws is not None and dy.N == N and dy.M == D
-        px, ldx = _mat(x)
-        pr, ldr = (_mat(res) if res is not None else (None, 0))
-        dx2, a2, m2, dp2, ds2 = None, 1.0, None, 0.0, 0
-        if second is not None:
-            a2, m2, drop2 = second
-            dp2, ds2 = drop2 if (drop2 is not None and drop2[0] > 0.0) else (0.0, 0)
-            dx2 = torch.empty((N, D), dtype=gdt, device=x.device)
-        tok = _pb(f"layernorm_bwd from slabs ({N}x{D}) S={dy.S}{'+res' if res is not None else ''}{'+2nd' if second is not None else ''}",
-                  ((1 + (res is not None) + (second is not None)) * 2 + _es(x) + 4 * dy.S) * N * D)
-        L.check(L.lib().smx_layernorm_bwd2_slabs(L.BF16, _p(dy.t), dy.S, N * D, px, ldx, 1 if x.dtype == torch.float32 else 0, _p(gamma), _p(beta), act,
-                                                 _p(stats), pr, ldr, _p(dx), _mat(dx)[1], N, D, _p(ws), _p(dx2), D if dx2 is not None else 0, a2, _p(m2),
-                                                 dp2, ds2, _epoch(), _stream()), "smx_layernorm_bwd2_slabs")
-        _pe(tok)
-        return dx if second is None else (dx, dx2)
-    pdy, lddy = _mat(dy)
-    px, ldx = _mat(x)
-    pr, ldr = (_mat(res) if res is not None else (None, 0))
-    if ws is None:
+    elif ws is None:
         ws = _workspace(L.lib().smx_layernorm_bwd_workspace(N, D), x.device, slot=2)
+    a = L.LnBwd(dtype=L.BF16 if slabs else dt(dy), x_f32=int(x.dtype == torch.float32), act=act, gamma=_p(gamma), beta=_p(beta),
+                stats=_p(stats), dX=_p(dx), lddx=_mat(dx)[1], dgamma=_p(dgamma), dbeta=_p(dbeta), workspace=_p(ws), alpha2=1.0,
+                epoch=_epoch(), N=N, D=D)
+    a.X, a.ldx = _mat(x)
+    if slabs:
+        a.slabs, a.nslab, a.slab_stride = _p(dy.t), dy.S, N * D
+    else:
+        a.dY, a.lddy = _mat(dy)
+    if res is not None:
+        a.R, a.ldr = _mat(res)
     dx2 = None
-    a2, m2, dp2, ds2 = 1.0, None, 0.0, 0
     if second is not None:
         a2, m2, drop2 = second
-        dp2, ds2 = drop2 if (drop2 is not None and drop2[0] > 0.0) else (0.0, 0)
+        a.alpha2, a.row_mask2 = a2, _p(m2)
+        if drop2 is not None and drop2[0] > 0.0:
+            a.drop_p2, a.drop_seed2 = drop2
         dx2 = torch.empty((N, D), dtype=gdt, device=x.device)
-    tok = _pb(f"layernorm_bwd ({N}x{D}){'+res' if res is not None else ''}{'+2nd' if second is not None else ''}",
-              ((2 + (res is not None) + (second is not None)) * _es(dy) + _es(x)) * N * D)
-    fn = L.lib().smx_layernorm_bwd2 if x.dtype == gdt else L.lib().smx_layernorm_bwd2_x32
-    assert x.dtype == gdt or x.dtype == torch.float32
-    L.check(fn(dt(dy), pdy, lddy, px, ldx, _p(gamma), _p(beta), act, _p(stats), pr, ldr, _p(dx), _mat(dx)[1],
-               _p(dgamma), _p(dbeta), N, D, _p(ws), _p(dx2), D if dx2 is not None else 0, a2, _p(m2), dp2,
-               ds2, _epoch(), _stream()), "smx_layernorm_bwd")
+        a.dX2, a.lddx2 = _p(dx2), D
+    if preact is not None:
+        a.Z, a.ldz, a.zact = _p(preact[0]), _mat(preact[0])[1], preact[1]
+    sfx = f"{'+res' if res is not None else ''}{'+2nd' if second is not None else ''}"
+    if slabs:
+        tok = _pb(f"layernorm_bwd from slabs ({N}x{D}) S={dy.S}{sfx}", ((1 + (res is not None) + (second is not None)) * 2 + _es(x) + 4 * dy.S) * N * D)
+    elif preact is not None:
+        tok = _pb(f"layernorm_bwd+preact ({N}x{D})", 4 * _es(dy) * N * D)
+    else:
+        tok = _pb(f"layernorm_bwd ({N}x{D}){sfx}", ((2 + (res is not None) + (second is not None)) * _es(dy) + _es(x)) * N * D)
+    L.check(L.lib().smx_layernorm_bwd(ctypes.byref(a), _stream()), "smx_layernorm_bwd")
     _pe(tok)
     return dx if second is None else (dx, dx2)
 
 
 def layernorm_bwd_preact_ok(dy, x, z, dx):
-    """Can smx_layernorm_bwd_preact take these views?  (bf16, D <= 2048, D % 8 == 0, 16-byte aligned rows)"""
+    """Can smx_layernorm_bwd take these views in its pre-activation form?  (bf16, D <= 2048, D % 8 == 0, 16-byte aligned rows)"""
     D = x.shape[1]
     ok = lambda t: t.dtype == torch.bfloat16 and t.data_ptr() % 16 == 0 and t.stride(0) % 8 == 0 and t.stride(1) == 1
     return D <= 2048 and D % 8 == 0 and all(ok(t) for t in (dy, x, z, dx))
 
 
 def layernorm_bwd_preact(dy, x, gamma, beta, stats, z, zact, dgamma, dbeta, act=L.ACT_NONE, ws=None, dx_out=None):
-    """dZ = zact'(z) * LayerNorm-backward(dy) for a LayerNorm whose input is x = zact(z) (smx_layernorm_bwd_preact)."""
-    N, D = x.shape
-    dx = dx_out if dx_out is not None else torch.empty((N, D), dtype=dy.dtype, device=x.device)
-    if ws is None:
-        ws = _workspace(L.lib().smx_layernorm_bwd_workspace(N, D), x.device, slot=2)
-    tok = _pb(f"layernorm_bwd+preact ({N}x{D})", 4 * _es(dy) * N * D)
-    L.check(L.lib().smx_layernorm_bwd_preact(dt(dy), _p(dy), _mat(dy)[1], _p(x), _mat(x)[1], _p(gamma), _p(beta), act, _p(stats),
-                                             _p(z), _mat(z)[1], zact, _p(dx), _mat(dx)[1], _p(dgamma), _p(dbeta), N, D, _p(ws),
-                                             _stream()), "smx_layernorm_bwd_preact")
-    _pe(tok)
-    return dx
+    """dZ = zact'(z) * LayerNorm-backward(dy) for a LayerNorm whose input is x = zact(z): layernorm_bwd's pre-activation form."""
+    return layernorm_bwd(dy, x, gamma, beta, stats, dgamma, dbeta, act=act, ws=ws, dx_out=dx_out, preact=(z, zact))
 
 
 def dwconv_fwd(p, w, bias, B, T, D, k, glu, pad_mode=L.PAD_ZERO, chunk=0, gate=None, drop=None):

@@ -54,6 +54,104 @@ def test_epilogue_struct_layout_matches_header():
     assert _lib.Epilogue.io_flags.offset == 256 and _lib.Epilogue.epoch.offset == 264 and _lib.Epilogue.lnf2_eps.offset == 312
 
 
+def test_layernorm_descriptor_layouts_match_header():
+    from summarymixing_amd import _lib
+    F, B = _lib.LnFwd, _lib.LnBwd
+    assert ctypes.sizeof(F) == 128 and ctypes.sizeof(B) == 224    # see include/smx.h smx_ln_fwd / smx_ln_bwd
+    assert F.X.offset == 8 and F.eps.offset == 64 and F.N.offset == 72 and F.gamma2.offset == 80 and F.Y2.offset == 96
+    assert F.eps2.offset == 120 and F.dtype2.offset == 124
+    assert B.dY.offset == 8 and B.slabs.offset == 24 and B.nslab.offset == 40 and B.X.offset == 48 and B.R.offset == 88
+    assert B.dgamma.offset == 120 and B.workspace.offset == 136 and B.dX2.offset == 144 and B.alpha2.offset == 168
+    assert B.drop_seed2.offset == 176 and B.epoch.offset == 184 and B.Z.offset == 192 and B.zact.offset == 208 and B.D.offset == 216
+
+
+# Inputs the library refuses, with the code it returns.  The pointers are fake (never dereferenced: every case is refused on the
+# host before any launch); BASE is 4 KiB aligned, BASE + 4 / + 8 are the misaligned variants.
+_BASE = 1 << 40
+
+
+def _ln_fwd_args(**kw):
+    from summarymixing_amd import _lib
+    a = _lib.LnFwd(dtype=_lib.BF16, X=_BASE, ldx=512, gamma=_BASE + 0x100000, beta=_BASE + 0x200000, Y=_BASE + 0x300000, ldy=512,
+                   eps=1e-5, N=8, D=512)
+    for k, v in kw.items():
+        setattr(a, k, v)
+    return a
+
+
+def _ln_bwd_args(**kw):
+    from summarymixing_amd import _lib
+    a = _lib.LnBwd(dtype=_lib.BF16, dY=_BASE, lddy=512, X=_BASE + 0x100000, ldx=512, gamma=_BASE + 0x200000, beta=_BASE + 0x300000,
+                   stats=_BASE + 0x400000, dX=_BASE + 0x500000, lddx=512, workspace=_BASE + 0x600000, alpha2=1.0, N=8, D=512)
+    for k, v in kw.items():
+        setattr(a, k, v)
+    return a
+
+
+_PAIR = dict(dtype=0, x_f32=1, gamma2=_BASE + 0x400000, beta2=_BASE + 0x500000, Y2=_BASE + 0x600000, ldy2=512, dtype2=1)
+_SLABS = dict(dY=None, lddy=0, slabs=_BASE + 0x700000, nslab=4, slab_stride=8 * 512)
+_EINVAL, _EUNSUPPORTED = -1, -2
+_LN_FWD_REFUSED = [
+    ("no X", dict(X=None), _EINVAL),
+    ("N < 0", dict(N=-1), _EINVAL),
+    ("D = 0", dict(D=0), _EINVAL),
+    ("x_f32, unknown dtype", dict(x_f32=1, dtype=5), _EINVAL),
+    ("x_f32, D = 2049", dict(x_f32=1, D=2049, ldx=2052, ldy=2052), _EUNSUPPORTED),
+    ("x_f32, D = 2052", dict(x_f32=1, D=2052, ldx=2052, ldy=2052), _EUNSUPPORTED),
+    ("x_f32, X 8-byte aligned", dict(x_f32=1, X=_BASE + 8), _EUNSUPPORTED),
+    ("x_f32, Y 4-byte aligned", dict(x_f32=1, Y=_BASE + 0x300004), _EUNSUPPORTED),
+    ("x_f32, ldx % 4", dict(x_f32=1, ldx=514), _EUNSUPPORTED),
+    ("pair, no gamma2", dict(_PAIR, gamma2=None), _EINVAL),
+    ("pair, unknown dtype2", dict(_PAIR, dtype2=7), _EINVAL),
+    ("pair, bf16 first output", dict(_PAIR, dtype=1), _EINVAL),
+    ("pair, activation", dict(_PAIR, act=2), _EINVAL),
+    ("pair, D = 2052", dict(_PAIR, D=2052, ldx=2052, ldy=2052, ldy2=2052), _EUNSUPPORTED),
+    ("pair, bf16 Y2 4-byte aligned", dict(_PAIR, Y2=_BASE + 0x600004), _EUNSUPPORTED),
+    ("pair, float32 Y2 8-byte aligned", dict(_PAIR, dtype2=0, Y2=_BASE + 0x600008), _EUNSUPPORTED),
+    ("pair, beta2 8-byte aligned", dict(_PAIR, beta2=_BASE + 0x500008), _EUNSUPPORTED),
+]
+_LN_BWD_REFUSED = [
+    ("no dY and no slabs", dict(dY=None), _EINVAL),
+    ("dY and slabs", dict(slabs=_BASE + 0x700000, nslab=4), _EINVAL),
+    ("no workspace", dict(workspace=None), _EINVAL),
+    ("dgamma without dbeta", dict(dgamma=_BASE + 0x800000), _EINVAL),
+    ("drop_p2 = 1", dict(drop_p2=1.0), _EINVAL),
+    ("dX2, D = 3072", dict(dX2=_BASE + 0x800000, lddx2=3072, D=3072, lddy=3072, ldx=3072, lddx=3072), _EUNSUPPORTED),
+    ("D = 4100", dict(D=4100, lddy=4100, ldx=4100, lddx=4100), _EUNSUPPORTED),
+    ("float32 D = 4100, unaligned", dict(dtype=0, D=4100, lddy=4101, ldx=4101, lddx=4101), _EUNSUPPORTED),
+    ("x_f32, unknown dtype", dict(x_f32=1, dtype=5), _EINVAL),
+    ("x_f32, D = 2049", dict(x_f32=1, D=2049, lddy=2052, ldx=2052, lddx=2052), _EUNSUPPORTED),
+    ("x_f32, D = 2052", dict(x_f32=1, D=2052, lddy=2052, ldx=2052, lddx=2052), _EUNSUPPORTED),
+    ("x_f32, X 8-byte aligned", dict(x_f32=1, X=_BASE + 0x100008), _EUNSUPPORTED),
+    ("slabs, nslab = 17", dict(_SLABS, nslab=17), _EINVAL),
+    ("slabs, nslab = 0", dict(_SLABS, nslab=0), _EINVAL),
+    ("slabs, float32", dict(_SLABS, dtype=0), _EINVAL),
+    ("slabs, dgamma", dict(_SLABS, dgamma=_BASE + 0x800000, dbeta=_BASE + 0x900000), _EINVAL),
+    ("slabs, D = 2052", dict(_SLABS, D=2052, ldx=2052, lddx=2052), _EUNSUPPORTED),
+    ("slabs, slabs 8-byte aligned", dict(_SLABS, slabs=_BASE + 0x700008), _EUNSUPPORTED),
+    ("slabs, x_f32, X 8-byte aligned", dict(_SLABS, x_f32=1, X=_BASE + 0x100008), _EUNSUPPORTED),
+    ("preact, activation", dict(Z=_BASE + 0x800000, ldz=512, act=2), _EUNSUPPORTED),
+    ("preact, D % 8", dict(Z=_BASE + 0x800000, ldz=516, D=516, lddy=516, ldx=516, lddx=516), _EUNSUPPORTED),
+    ("preact, D = 2056", dict(Z=_BASE + 0x800000, ldz=2056, D=2056, lddy=2056, ldx=2056, lddx=2056), _EUNSUPPORTED),
+    ("preact, float32", dict(Z=_BASE + 0x800000, ldz=512, dtype=0), _EUNSUPPORTED),
+    ("preact, Z 8-byte aligned", dict(Z=_BASE + 0x800008, ldz=512), _EUNSUPPORTED),
+    ("preact, R", dict(Z=_BASE + 0x800000, ldz=512, R=_BASE + 0x900000, ldr=512), _EINVAL),
+    ("preact, dX2", dict(Z=_BASE + 0x800000, ldz=512, dX2=_BASE + 0x900000, lddx2=512), _EINVAL),
+]
+
+
+@pytest.mark.parametrize("case,kw,code", _LN_FWD_REFUSED, ids=[c[0] for c in _LN_FWD_REFUSED])
+def test_layernorm_fwd_refuses_what_it_cannot_run(case, kw, code):
+    from summarymixing_amd import _lib
+    assert _lib.lib().smx_layernorm_fwd(ctypes.byref(_ln_fwd_args(**kw)), None) == code, case
+
+
+@pytest.mark.parametrize("case,kw,code", _LN_BWD_REFUSED, ids=[c[0] for c in _LN_BWD_REFUSED])
+def test_layernorm_bwd_refuses_what_it_cannot_run(case, kw, code):
+    from summarymixing_amd import _lib
+    assert _lib.lib().smx_layernorm_bwd(ctypes.byref(_ln_bwd_args(**kw)), None) == code, case
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason="checks the no-GPU behaviour")
 def test_no_cpu_fallback():
     from summarymixing_amd.nnet.summary_mixing import SummaryMixing

@@ -409,7 +409,7 @@ def test_recipe_batch_path_every_parameter_gradient_vs_oracle(monkeypatch):
 @pytest.mark.parametrize("d", [144, 512])
 def test_layernorm_pair_in_the_stack_equals_two_launches(d, monkeypatch, ln_fuse_mode):
     """ConformerEncoder on the float32 stream: norm2 + the next layer's first LayerNorm in one launch (functional._LN_PAIR,
-    smx_layernorm_fwd_pair_x32) against the two-launch path - outputs, dL/dx and every parameter gradient (the two paths differ
+    smx_layernorm_fwd's pair form) against the two-launch path - outputs, dL/dx and every parameter gradient (the two paths differ
     by an ulp of the LayerNorm outputs).  Where norm2 rides in the FFN's down-projection GEMM (d_model = 512 with the fusion forced
     on: the row-complete 128 x 512 tile, round 5) the pair kernel has nothing left to do."""
     from summarymixing_amd import functional as F
@@ -453,7 +453,7 @@ def test_layernorm_pair_in_the_stack_equals_two_launches(d, monkeypatch, ln_fuse
 def test_small_batch_split_k_path_every_parameter_gradient_vs_oracle(B, T, d, f, monkeypatch):
     """Round 6, the dispatch of a batch below 2048 frames (one utterance of 500 frames at d_model 256; two recipe utterances at d_model
     512): the long reductions as split-K slabs whose reducer applies the Linear's epilogue and the LayerNorm behind it (smx_gemm_panel_slabs
-    + smx_slab_epilogue), the LayerNorm backward fed from the slabs of the dgrad behind it (smx_layernorm_bwd2_slabs), the weight
+    + smx_slab_epilogue), the LayerNorm backward fed from the slabs of the dgrad behind it (smx_layernorm_bwd from slabs), the weight
     gradients of a layer in one slab-free launch (smx_wgrad_group_direct), 32-row panels.  Output, dL/dx and EVERY parameter gradient of
     two layers against the fp64 oracle's autograd (Conformer.py:479-537), and the record that those kernels really ran."""
     from oracle import smx_oracle as O

@@ -111,7 +111,7 @@ def test_layernorm_fwd_bwd(D, dtype, tol):
 @pytest.mark.parametrize("D,ld", [(1536, 3072), (512, 512), (2048, 2056), (40, 48)])
 @pytest.mark.parametrize("zact", ["gelu", "swish"])
 def test_layernorm_backward_through_the_producing_activation(D, ld, zact):
-    """smx_layernorm_bwd_preact: x = act(z) feeds a LayerNorm; the kernel returns dL/dz = act'(z) * LNbwd(dy) (strided views:
+    """smx_layernorm_bwd with a pre-activation (smx_ln_bwd.Z): x = act(z) feeds a LayerNorm; the kernel returns dL/dz = act'(z) * LNbwd(dy) (strided views:
     the gate half of the cgMLP's (N, 3072) tensors), dgamma / dbeta as the plain backward."""
     L, ops = _ops()
     torch.manual_seed(D + ld)
@@ -151,7 +151,7 @@ def test_layernorm_backward_through_the_producing_activation(D, ld, zact):
 @pytest.mark.parametrize("D", [256, 512, 1536, 2048, 200])
 def test_layernorm_of_the_float32_stream(D):
     """LayerNorm(float32 row) -> bf16 output, and its backward with bf16 gradients next to the float32 input
-    (smx_layernorm_fwd_x32 / smx_layernorm_bwd2_x32: the fp32 residual stream of a bf16 model), every row-width class."""
+    (smx_ln_fwd.x_f32 / smx_ln_bwd.x_f32: the fp32 residual stream of a bf16 model), every row-width class."""
     L, ops = _ops()
     torch.manual_seed(D)
     N = 1001
@@ -847,8 +847,8 @@ def test_chunked_dwconv_backward_is_bit_reproducible(chunk, D, k):
 @pytest.mark.parametrize("N,D", [(1, 64), (37, 144), (1000, 256), (3750, 512), (513, 1024), (70, 2048)])
 @pytest.mark.parametrize("out_dtype", [torch.bfloat16, torch.float32])
 def test_layernorm_pair_equals_two_launches(N, D, out_dtype):
-    """smx_layernorm_fwd_pair_x32 (norm2 of a Conformer layer + the next layer's first LayerNorm, Conformer.py:536 + :458-459, in one
-    pass over the float32 stream) against smx_layernorm_fwd followed by smx_layernorm_fwd_x32 (outputs and statistics to an ulp)
+    """The pair form of smx_layernorm_fwd (norm2 of a Conformer layer + the next layer's first LayerNorm, Conformer.py:536 + :458-459,
+    in one pass over the float32 stream) against the plain forward followed by the float32-X forward (outputs and statistics to an ulp)
     and against torch's LayerNorm."""
     from summarymixing_amd import ops
     torch.manual_seed(N + D)

@@ -109,8 +109,8 @@ def test_slab_epilogue_equals_the_gemm_epilogue(N, M, K, ks, variant):
 @pytest.mark.parametrize("xf32", [True, False])
 @pytest.mark.parametrize("N,D,K,ks", [(500, 256, 1024, 256), (1000 + 37, 512, 2048, 512), (333, 256, 512, 256)])
 def test_layernorm_bwd_from_slabs_equals_the_two_launch_path(N, D, K, ks, xf32):
-    """smx_layernorm_bwd2_slabs: the LayerNorm backward with its incoming gradient given as the split-K slabs of the dgrad behind it,
-    against (tiled dgrad GEMM -> bf16 gradient -> smx_layernorm_bwd2): dX, the second output (alpha * D(dX) * mask, same keep
+    """smx_layernorm_bwd from slabs: the LayerNorm backward with its incoming gradient given as the split-K slabs of the dgrad behind it,
+    against (tiled dgrad GEMM -> bf16 gradient -> smx_layernorm_bwd): dX, the second output (alpha * D(dX) * mask, same keep
     decisions), the dgamma / dbeta partial rows.  The slab path never rounds the gradient to bf16, so it is compared at bf16 tolerance
     with the two-launch path and at float32 tolerance with float64 math."""
     g = torch.Generator(device="cuda").manual_seed(N + D)
