@@ -590,6 +590,32 @@ int smx_sumsq(const float* x, int64_t n, float* out, void* workspace, void* stre
  * refresh) - the behaviour of SpeechBrain's Brain.check_gradients for non-finite gradients. */
 int smx_clip_factor(const float* sumsq, float max_norm, float inv_scale, float* out, void* stream);
 
+/* ---- Streaming inference (chunk by chunk) of a Dynamic-Chunk-trained Conformer encoder ---------------------------------------
+ * The full-utterance DynChunk forward (TransformerASR.py:85-110 summary mask, Conformer.py:190-313 convolution) computed one chunk
+ * of C_cur <= C frames per stream at a time, for B equal-length streams.  `counter` is a device step counter (uint64, the
+ * smx_step_counter_add convention) holding the index c of the chunk being run; no chunk index is passed by value, so a captured
+ * chunk step stays valid on replay.  smx_stream_advance ends a step.  All state buffers are caller-owned and zero-initialised.
+ * smx_stream_summary: S (B*C_cur, D) rows of the summary branch (summary_mixing.py:224-235).  out[b, t, :] = (sum of S over the
+ *   window of chunk c) / (frames in the window), the window being the chunks [c - left, c] (left = -1: all of [0, c]) and the frame
+ *   count min(c, left) * C + C_cur (smx_chunk_mean_fwd's denominator), broadcast to all C_cur rows of stream b.  The chunk's
+ *   float32 sums go into the state: ring (B, left, D) float32, slot c % left (left = -1: ring (B, D) is a running sum; left = 0:
+ *   ring unused, may be NULL).  Fixed summation order, no atomics.  dtype F32 | BF16, D % 8 == 0, 1 <= C_cur <= C <= 64,
+ *   -1 <= left <= 32.
+ * smx_dwconv1d_glu_stream: smx_dwconv1d_glu_fwd's u / Y (glu = 1, zero padding, bias) over one chunk with Dynamic Chunk Convolution.
+ *   P (B*C_cur, 2D) pre-GLU rows of the chunk; state (B, H, 2D), H = (k-1)/2, contiguous, compute dtype: the last H pre-GLU rows
+ *   before the chunk (zeros before the first: the full forward's zero padding at t < 0).  Y[b, t] reads X = [state; chunk] at
+ *   t .. t + k - 1, zero at and beyond the chunk's end.  The state is rewritten IN PLACE with the last H rows of [state; chunk]
+ *   (also when C_cur < H): one workgroup owns all H + C_cur rows of its (stream, 64-channel group) and reads them all before it
+ *   writes any.  P and Y must not overlap the state.  dtype F32 | BF16, D % 8 == 0, odd k <= 63, 1 <= C_cur <= 64.
+ * smx_stream_advance: counter += 1, then pe[r, :] = table[counter * C + r, :] for r < C (zero at and beyond `rows`), one launch:
+ *   the next chunk's rows of the positional table (TransformerASR.py:547-549) in a fixed (C, D) buffer. */
+int smx_stream_summary(int dtype, const void* S, int64_t lds, void* out, int64_t ldo, float* ring, const uint64_t* counter, int B,
+                       int C_cur, int C, int D, int left, void* stream);
+int smx_dwconv1d_glu_stream(int dtype, const void* P, int64_t ldp, const float* w, const float* bias, void* state, void* Y,
+                            int64_t ldy, int B, int C_cur, int D, int k, void* stream);
+int smx_stream_advance(int dtype, uint64_t* counter, const void* table, int64_t ldt, int rows, void* pe, int64_t ldpe, int C, int D,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

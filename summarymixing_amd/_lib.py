@@ -198,6 +198,9 @@ SIGNATURES = {
     "smx_sumsq_workspace": (c_sz, []),
     "smx_sumsq": (c_i, [c_vp, c_i64, c_vp, c_vp, c_vp]),
     "smx_clip_factor": (c_i, [c_vp, c_f, c_f, c_vp, c_vp]),
+    "smx_stream_summary": (c_i, [c_i, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_vp]),
+    "smx_dwconv1d_glu_stream": (c_i, [c_i, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_i, c_i, c_i, c_i, c_vp]),
+    "smx_stream_advance": (c_i, [c_i, c_vp, c_vp, c_i64, c_i, c_vp, c_i64, c_i, c_i, c_vp]),
 }
 
 _lib = None

@@ -1,0 +1,174 @@
+// stream.hip — chunk-by-chunk streaming inference of a Dynamic-Chunk-trained Conformer encoder (gfx950).
+//
+// A chunk step runs the encoder on one chunk of C_cur <= C frames per stream.  Two operators of a layer look at earlier chunks:
+// the DynChunk summary (window mean over the chunks [c - left, c]) and the depthwise convolution (the (k-1)/2 previous inputs).
+// Their state lives in caller-owned device buffers and is advanced by the kernels below; the chunk index c comes from a
+// device-resident counter (smx_step_counter_add convention), so a captured chunk step stays valid on replay.
+#include "smx_common.h"
+
+namespace smx {
+
+constexpr int ST_CMAX = 64;     // max frames per chunk
+constexpr int ST_KMAX = 63;     // max depthwise taps
+constexpr int ST_HMAX = (ST_KMAX - 1) / 2;
+constexpr int ST_COLS = 64;     // columns (channels) per workgroup
+
+// ---- summary: grid (ceil(D / 64), B), 256 threads = 64 columns x 4 waves -------------------------------------------------
+// lane = column, wave w sums the chunk rows w, w + 4, ...; the four partials fold in a fixed order, then the window sum
+// (ring slots of the earlier chunks, oldest first) is added and divided by the window's frame count.  Every thread reads the
+// ring slots of its own column before it writes the chunk's sum into slot c % left: nothing is shared between threads there.
+template <typename T>
+__global__ __launch_bounds__(256) void stream_summary_kernel(const T* __restrict__ S, long lds, T* __restrict__ out, long ldo,
+                                                             float* __restrict__ ring, const uint64_t* __restrict__ counter,
+                                                             int C_cur, int C, int D, int left) {
+  __shared__ float red[4][ST_COLS];
+  __shared__ float mean[ST_COLS];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, b = blockIdx.y;
+  const int col = blockIdx.x * ST_COLS + lane;
+  const bool ok = col < D;
+  const long c = (long)counter[0];
+  float acc = 0.f;
+  if (ok)
+    for (int t = w; t < C_cur; t += 4) acc += to_f32(S[((long)b * C_cur + t) * lds + col]);
+  red[w][lane] = acc;
+  __syncthreads();
+  if (w == 0) {
+    const float csum = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
+    float win = 0.f;
+    long frames;
+    if (left < 0) {                                       // unlimited: ring = one running (B, D) sum
+      float* r = ring + (long)b * D + col;
+      if (ok) { win = *r; *r = win + csum; }
+      frames = c * C + C_cur;
+    } else {
+      const long nprev = c < left ? c : left;
+      float* r = ring + (long)b * left * D + col;
+      if (ok) {
+        for (long j = c - nprev; j < c; ++j) win += r[(j % left) * D];
+        if (left > 0) r[(c % left) * D] = csum;           // (slot c % left held chunk c - left: read above when in the window)
+      }
+      frames = nprev * C + C_cur;
+    }
+    mean[lane] = (win + csum) / (float)frames;
+  }
+  __syncthreads();
+  if (!ok) return;
+  const T m = from_f32<T>(mean[lane]);
+  for (int t = w; t < C_cur; t += 4) out[((long)b * C_cur + t) * ldo + col] = m;
+}
+
+// ---- GLU + depthwise conv over one chunk: grid (ceil(D / 64), B), 256 threads = 64 channels x 4 waves ---------------------
+// Rows of X = [state (H rows); chunk (C_cur rows)], H = (k-1)/2.  Output frame t of the chunk is X-row H + t; tap j reads X-row
+// t + j and reads zero at and beyond H + C_cur (Dynamic Chunk Convolution: nothing past the chunk).  The workgroup reads every
+// row of its channels (the GLU'd values into LDS, the last H pre-GLU rows into LDS as well) before one barrier, then writes
+// Y and the new state = the last H pre-GLU rows of X: the in-place state update never races a read.
+template <typename T>
+__global__ __launch_bounds__(256) void dwconv_stream_kernel(const T* __restrict__ P, long ldp, const float* __restrict__ w,
+                                                            const float* __restrict__ bias, T* state, T* __restrict__ Y, long ldy,
+                                                            int C_cur, int D, int k) {
+  __shared__ float u[ST_HMAX + ST_CMAX][ST_COLS];
+  __shared__ float raw[ST_HMAX][2][ST_COLS];
+  __shared__ float wl[ST_KMAX][ST_COLS];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, b = blockIdx.y;
+  const int ch = blockIdx.x * ST_COLS + lane;
+  const bool ok = ch < D;
+  const int H = (k - 1) / 2, R = H + C_cur;
+  T* st = state + (long)b * H * 2 * D;
+  for (int i = wv; i < R; i += 4) {
+    float a = 0.f, g = 0.f;
+    if (ok) {
+      const T* row = i < H ? st + (long)i * 2 * D : P + ((long)b * C_cur + (i - H)) * ldp;
+      a = to_f32(row[ch]);
+      g = to_f32(row[D + ch]);
+    }
+    u[i][lane] = a * sigmoidf_(g);
+    if (i >= C_cur) { raw[i - C_cur][0][lane] = a; raw[i - C_cur][1][lane] = g; }
+  }
+  for (int j = wv; j < k; j += 4) wl[j][lane] = ok ? w[(long)ch * k + j] : 0.f;
+  __syncthreads();
+  if (!ok) return;
+  const float bs = bias ? bias[ch] : 0.f;
+  for (int t = wv; t < C_cur; t += 4) {
+    float acc = bs;
+    const int jmax = min(k, R - t);
+    for (int j = 0; j < jmax; ++j) acc += wl[j][lane] * u[t + j][lane];
+    Y[((long)b * C_cur + t) * ldy + ch] = from_f32<T>(acc);
+  }
+  for (int i = wv; i < H; i += 4) {
+    st[(long)i * 2 * D + ch] = from_f32<T>(raw[i][0][lane]);
+    st[(long)i * 2 * D + D + ch] = from_f32<T>(raw[i][1][lane]);
+  }
+}
+
+// ---- end of a chunk step: one workgroup.  c' = counter + 1; pe[r] = table[c' C + r] (zero past the table); counter = c' ----
+template <typename T>
+__global__ __launch_bounds__(256) void stream_advance_kernel(uint64_t* counter, const T* __restrict__ table, long ldt, int rows,
+                                                             T* __restrict__ pe, long ldpe, int C, int D) {
+  __shared__ uint64_t next;
+  if (threadIdx.x == 0) next = counter[0] + 1;
+  __syncthreads();
+  const long r0 = (long)next * C;
+  for (long i = threadIdx.x; i < (long)C * D; i += 256) {
+    const long r = i / D, col = i % D;
+    pe[r * ldpe + col] = r0 + r < rows ? table[(r0 + r) * ldt + col] : from_f32<T>(0.f);
+  }
+  if (threadIdx.x == 0) counter[0] = next;
+}
+
+}  // namespace smx
+
+using namespace smx;
+
+#define STREAM (reinterpret_cast<hipStream_t>(stream))
+
+extern "C" int smx_stream_summary(int dtype, const void* S, int64_t lds, void* out, int64_t ldo, float* ring,
+                                  const uint64_t* counter, int B, int C_cur, int C, int D, int left, void* stream) {
+  SMX_REQUIRE(dtype == SMX_F32 || dtype == SMX_BF16, "smx_stream_summary: bad dtype");
+  SMX_REQUIRE(S && out && counter && (ring || left == 0), "smx_stream_summary: null pointer");
+  SMX_REQUIRE(B > 0 && D > 0 && D % 8 == 0, "smx_stream_summary: B > 0 and D %% 8 == 0 (B=%d D=%d)", B, D);
+  SMX_REQUIRE(C >= 1 && C <= ST_CMAX && C_cur >= 1 && C_cur <= C, "smx_stream_summary: 1 <= C_cur <= C <= %d (C_cur=%d C=%d)",
+              ST_CMAX, C_cur, C);
+  SMX_REQUIRE(left >= -1 && left <= 32, "smx_stream_summary: left in {-1 (unlimited), 0 .. 32} (left=%d)", left);
+  SMX_REQUIRE(lds >= D && ldo >= D, "smx_stream_summary: row strides must be >= D");
+  dim3 grid((unsigned)((D + ST_COLS - 1) / ST_COLS), (unsigned)B);
+  if (dtype == SMX_BF16)
+    hipLaunchKernelGGL(stream_summary_kernel<bf16_t>, grid, dim3(256), 0, STREAM, (const bf16_t*)S, (long)lds, (bf16_t*)out, (long)ldo,
+                       ring, counter, C_cur, C, D, left);
+  else
+    hipLaunchKernelGGL(stream_summary_kernel<float>, grid, dim3(256), 0, STREAM, (const float*)S, (long)lds, (float*)out, (long)ldo,
+                       ring, counter, C_cur, C, D, left);
+  return check_launch("smx_stream_summary");
+}
+
+extern "C" int smx_dwconv1d_glu_stream(int dtype, const void* P, int64_t ldp, const float* w, const float* bias, void* state,
+                                       void* Y, int64_t ldy, int B, int C_cur, int D, int k, void* stream) {
+  SMX_REQUIRE(dtype == SMX_F32 || dtype == SMX_BF16, "smx_dwconv1d_glu_stream: bad dtype");
+  SMX_REQUIRE(P && w && Y && (state || k == 1), "smx_dwconv1d_glu_stream: null pointer");
+  SMX_REQUIRE(k >= 1 && k <= ST_KMAX && (k & 1), "smx_dwconv1d_glu_stream: k=%d must be odd and <= %d", k, ST_KMAX);
+  SMX_REQUIRE(B > 0 && D > 0 && D % 8 == 0, "smx_dwconv1d_glu_stream: B > 0 and D %% 8 == 0 (B=%d D=%d)", B, D);
+  SMX_REQUIRE(C_cur >= 1 && C_cur <= ST_CMAX, "smx_dwconv1d_glu_stream: 1 <= C_cur <= %d (C_cur=%d)", ST_CMAX, C_cur);
+  SMX_REQUIRE(ldp >= 2 * (int64_t)D && ldy >= D, "smx_dwconv1d_glu_stream: ldp >= 2 D and ldy >= D");
+  dim3 grid((unsigned)((D + ST_COLS - 1) / ST_COLS), (unsigned)B);
+  if (dtype == SMX_BF16)
+    hipLaunchKernelGGL(dwconv_stream_kernel<bf16_t>, grid, dim3(256), 0, STREAM, (const bf16_t*)P, (long)ldp, w, bias, (bf16_t*)state,
+                       (bf16_t*)Y, (long)ldy, C_cur, D, k);
+  else
+    hipLaunchKernelGGL(dwconv_stream_kernel<float>, grid, dim3(256), 0, STREAM, (const float*)P, (long)ldp, w, bias, (float*)state,
+                       (float*)Y, (long)ldy, C_cur, D, k);
+  return check_launch("smx_dwconv1d_glu_stream");
+}
+
+extern "C" int smx_stream_advance(int dtype, uint64_t* counter, const void* table, int64_t ldt, int rows, void* pe, int64_t ldpe,
+                                  int C, int D, void* stream) {
+  SMX_REQUIRE(dtype == SMX_F32 || dtype == SMX_BF16, "smx_stream_advance: bad dtype");
+  SMX_REQUIRE(counter && table && pe, "smx_stream_advance: null pointer");
+  SMX_REQUIRE(C >= 1 && C <= ST_CMAX && D > 0 && rows >= 0, "smx_stream_advance: 1 <= C <= %d, D > 0", ST_CMAX);
+  SMX_REQUIRE(ldt >= D && ldpe >= D, "smx_stream_advance: row strides must be >= D");
+  if (dtype == SMX_BF16)
+    hipLaunchKernelGGL(stream_advance_kernel<bf16_t>, dim3(1), dim3(256), 0, STREAM, counter, (const bf16_t*)table, (long)ldt, rows,
+                       (bf16_t*)pe, (long)ldpe, C, D);
+  else
+    hipLaunchKernelGGL(stream_advance_kernel<float>, dim3(1), dim3(256), 0, STREAM, counter, (const float*)table, (long)ldt, rows,
+                       (float*)pe, (long)ldpe, C, D);
+  return check_launch("smx_stream_advance");
+}

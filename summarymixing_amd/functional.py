@@ -731,6 +731,15 @@ class DynChunkMask:
         return m
 
 
+class DynChunkStream:
+    """One layer's summary state for streaming inference (the DynChunkMask of a chunk-by-chunk run): `ring` holds the float32 sums
+    of the last `left_context` chunks ((B, left, D); (B, D) running sums when left_context is None), `counter` is the context's
+    device chunk counter (int64 (1,), shared by all layers).  Passed as cell_run's sum_mask: the summary becomes smx_stream_summary."""
+
+    def __init__(self, ring, counter, chunk_size, left_context=None):
+        self.ring, self.counter, self.chunk_size, self.left_context = ring, counter, chunk_size, left_context
+
+
 def _chunk_mean_seqpar(x, out, B, T, chunk, left, reverse=False):
     """The Dynamic Chunk Training summary (chunk c averages the chunks [c - left, c], all earlier ones with left = None:
     summary_mixing.py:224-235 with the mask of TransformerASR.py:85-110) with the time axis sharded over the sequence group.
@@ -850,6 +859,10 @@ def cell_run(P, cfg, B, T, mask, sum_mask, p_drop=0.0):
             sm = None                                   # the lite branch ignores sum_mask (:286-310)
         if isinstance(sm, DynChunkMask):
             pool_kind = "chunk"
+        elif isinstance(sm, DynChunkStream):
+            if need_bwd or mode not in ("SummaryMixing", "SummaryMixing-fast"):
+                raise NotImplementedError("streaming summary: inference of the SummaryMixing / SummaryMixing-fast modes only")
+            pool_kind = "stream"
         elif sm is not None:
             pool_kind = "dense"
             w = sm.to(device=dev, dtype=torch.float32)
@@ -927,6 +940,9 @@ def cell_run(P, cfg, B, T, mask, sum_mask, p_drop=0.0):
         elif pool_kind == "chunk":
             sbar = torch.empty((N, sdim), dtype=dtype, device=dev)
             ops.chunk_mean(s, sbar, B, T, sm.chunk_size, sm.left_context)
+        elif pool_kind == "stream":
+            sbar = torch.empty((N, sdim), dtype=dtype, device=dev)
+            ops.stream_summary(s, sbar, B, T, sm.chunk_size, sm.left_context, sm.ring, sm.counter)
         elif pool_kind == "expdecay":
             sbar = torch.empty((N, sdim), dtype=dtype, device=dev)
             ops.expdecay_mean(s, sbar, B, T, decay)
@@ -1242,10 +1258,13 @@ def ffn_module_fwd(x, P, act, need_bwd, dtype, alpha=0.5, p=0.0, pre_ln=None, ln
     bwd.pre = (alpha, None, d2)          # what this block does first to its incoming gradient: alpha * D2(dy)
     return ret(bwd)
 
-def conv_module_fwd(x, P, act, mask, B, T, need_bwd, dtype, chunk=0, residual=True, p=0.0, pre_ln=None, ln_next=None):
+def conv_module_fwd(x, P, act, mask, B, T, need_bwd, dtype, chunk=0, residual=True, p=0.0, pre_ln=None, ln_next=None,
+                    conv_state=None):
     """y = [x +] mask * Linear(act(LN(dwconv(GLU(pw(LN(x)))))))   (Conformer.py:314-331,532-534).
     pre_ln / ln_next: as in ffn_module_fwd (the module's first LayerNorm done by the producer of x; the LayerNorm that
-    follows the module done in the out-projection's epilogue)."""
+    follows the module done in the out-projection's epilogue).
+    conv_state: streaming inference - x is one chunk of T frames of B streams, the depthwise conv reads its left context from
+    this (B, (k-1)/2, 2d) state and updates it (ops.dwconv_stream)."""
     d = x.shape[1]
     if SP.enabled():
         r = _conv_module_fwd_sp(x, P, act, mask, B, T, need_bwd, dtype, chunk, residual, p)
@@ -1255,7 +1274,12 @@ def conv_module_fwd(x, P, act, mask, B, T, need_bwd, dtype, chunk=0, residual=Tr
     p_, _ = linear_fwd(h, Wp, P["bp"], wparam=P["Wp"])
     k = P["wd"].shape[-1]
     wd = P["wd"].detach().reshape(d, k)
-    c = ops.dwconv_fwd(p_, wd, P["bd"].detach() if P["bd"] is not None else None, B, T, d, k, True, L.PAD_ZERO, chunk)
+    if conv_state is None:
+        c = ops.dwconv_fwd(p_, wd, P["bd"].detach() if P["bd"] is not None else None, B, T, d, k, True, L.PAD_ZERO, chunk)
+    else:
+        if need_bwd:
+            raise NotImplementedError("streaming convolution: inference only")
+        c = ops.dwconv_stream(p_, wd, P["bd"].detach() if P["bd"] is not None else None, conv_state, B, T, d, k)
     a, ln2_b = ln_fwd(c, P["ln2_w"], P["ln2_b"], 1e-5, need_bwd, act)      # LN + activation fused
     Wo = wcast(P["Wo"], dtype)
     dr = (p, ops.new_dropout_seed()) if p > 0.0 else None   # Linear -> Dropout -> * mask (+ x): one epilogue

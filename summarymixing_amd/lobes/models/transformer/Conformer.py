@@ -9,18 +9,97 @@ HOLDERS only (same names => same keys => reference checkpoints load); all arithm
              x2 = x1 + SummaryMixing(LN(x1))    cell with the skip fused as the merge-GEMM residual
              x3 = x2 + mask * ConvModule(x2)    LN -> GEMM -> fused GLU+dwconv -> LN+act -> GEMM(+mask,residual)
              y  = LN(x3 + 1/2 FFN2(x3))
-Attention types other than SummaryMixing, causal convolution and the streaming context are out of scope
- and raise NotImplementedError.
+Attention types other than SummaryMixing and causal convolution are out of scope and raise
+NotImplementedError.
+
+Streaming inference (forward_streaming / make_streaming_context, reference :539-633,788-857) runs a Dynamic-Chunk-trained
+encoder one chunk at a time and equals the masked full-utterance forward.  Unlike the reference, which keeps raw input frames as
+left context and recomputes them on every chunk (its own TODO), a layer here carries only what the next chunk reads: the float32
+per-chunk sums of the summary branch and the last (k-1)/2 pre-GLU rows of the convolution (functional.DynChunkStream, ops.dwconv_stream).
 """
-from typing import Optional
+from dataclasses import dataclass, field
+from typing import List, Optional
 
 import torch
 import torch.nn as nn
 
 from .... import functional as F
 from .... import ops
+from .... import sequence_parallel as SP
+from ....utils.dynamic_chunk_training import DynChunkTrainConfig
 from ....nnet.activations import Swish, act_code
 from ....nnet.summary_mixing import SummaryMixing
+
+
+@dataclass
+class ConformerEncoderLayerStreamingContext:
+    """Streaming state of one ConformerEncoderLayer (reference :31-59).  The reference keeps `mha_left_context` (the last raw input
+    frames, recomputed on every chunk) and `dcconv_left_context`; this layer keeps instead:
+      summary   - functional.DynChunkStream: the float32 sums of the summary branch over the last `left_context_size` chunks
+                  ((B, left, s); one (B, s) running sum for unlimited left context; none for left 0) and the device chunk counter;
+      dcconv_state - (B, (k-1)/2, 2 d) in the compute dtype: the last pre-GLU rows of the pointwise convolution (zeros at the start,
+                  the full forward's zero padding).
+    Both are allocated on the first chunk, which fixes the batch size, dtype and device."""
+    dynchunktrain_config: DynChunkTrainConfig
+    summary: Optional[F.DynChunkStream] = None
+    dcconv_state: Optional[torch.Tensor] = None
+    counter: Optional[torch.Tensor] = None          # device chunk counter (int64 (1,)), shared with the encoder's context
+    batch_size: Optional[int] = None
+    dtype: Optional[torch.dtype] = None
+    device: Optional[torch.device] = None
+    frames: int = 0                                 # host mirror of the frames consumed (never read back from the device)
+    closed: bool = False                            # a chunk shorter than chunk_size ended the stream
+
+
+@dataclass
+class ConformerEncoderStreamingContext:
+    """Streaming state of a ConformerEncoder (reference :62-70): the configuration, one context per layer and the state shared by
+    the layers (device chunk counter, host frame mirror).  pe_table / pe: set by TransformerASR on the first chunk - the
+    positional table and the fixed (C, d) buffer holding the current chunk's rows of it, advanced on device after every chunk."""
+    dynchunktrain_config: DynChunkTrainConfig
+    layers: List[ConformerEncoderLayerStreamingContext] = field(default_factory=list)
+    counter: Optional[torch.Tensor] = None
+    batch_size: Optional[int] = None
+    dtype: Optional[torch.dtype] = None
+    device: Optional[torch.device] = None
+    frames: int = 0
+    closed: bool = False
+    pe_table: Optional[torch.Tensor] = None
+    pe: Optional[torch.Tensor] = None
+
+
+def _stream_check(ctx, training, B, C_cur, dtype, device):
+    """Validate one chunk against the context (host only: no device read).  -> True when the state is still to be allocated."""
+    if training:
+        raise RuntimeError("streaming inference: call .eval() first (forward_streaming runs no backward)")
+    C = ctx.dynchunktrain_config.chunk_size
+    if ctx.closed:
+        raise ValueError("streaming: a chunk shorter than chunk_size ended this stream; make a new context")
+    if not 1 <= C_cur <= C:
+        raise ValueError(f"streaming: a chunk holds 1 .. {C} frames, got {C_cur}")
+    if ctx.batch_size is None:
+        return True
+    if (B, dtype, torch.device(device)) != (ctx.batch_size, ctx.dtype, ctx.device):
+        raise ValueError(f"streaming: the context was started with B={ctx.batch_size}, {ctx.dtype} on {ctx.device}; got B={B}, "
+                         f"{dtype} on {device}")
+    return False
+
+
+def _stream_commit(ctx, C_cur):
+    ctx.frames += C_cur
+    ctx.closed = C_cur < ctx.dynchunktrain_config.chunk_size
+
+
+def _stream_refuse(layer, cfg):
+    if layer.mode not in ("SummaryMixing", "SummaryMixing-fast"):
+        raise NotImplementedError(f"streaming: mode {layer.mode} is not causal under Dynamic Chunk Training (SummaryMixing-lite "
+                                  "ignores the chunk mask; expdecay weighs every frame) - use SummaryMixing or SummaryMixing-fast")
+    if SP.enabled():
+        raise NotImplementedError("streaming inference does not run in sequence-parallel mode")
+    if cfg is None or cfg.chunk_size < 1 or cfg.chunk_size > 64:
+        raise ValueError("streaming needs a DynChunkTrainConfig with 1 <= chunk_size <= 64")
+    if cfg.left_context_size is not None and not 0 <= cfg.left_context_size <= 32:
+        raise ValueError("streaming: left_context_size must be None or 0 .. 32 chunks")
 
 
 class _LayerNorm(nn.Module):
@@ -108,13 +187,15 @@ class ConformerEncoderLayer(nn.Module):
         self.norm2 = _LayerNorm(d_model)
         self.drop = nn.Dropout(dropout)
 
-    def make_run(self, B, T, m8, src_mask, chunk, compute_dtype=None, next_layer=None):
+    def make_run(self, B, T, m8, src_mask, chunk, compute_dtype=None, next_layer=None, conv_state=None):
         """compute_dtype: dtype of the GEMM operands when the incoming stream x3 is the float32 residual stream of a bf16
         model (functional.RESIDUAL_F32); None = everything in x3.dtype.
         next_layer: the layer that consumes this one's output inside an encoder stack.  Its first LayerNorm (ffn_module1's) then
         runs in the same pass as this layer's norm2 where the shapes allow (ops.layernorm_fwd_pair: one read of the float32 stream
         for both); run(..., with_post=True) then returns a third value, (LN(y), stats) | None, which the stack hands to the next
-        layer's run as `pre_ln`."""
+        layer's run as `pre_ln`.
+        Streaming inference (forward_streaming): src_mask is a functional.DynChunkStream and conv_state the layer's (B, (k-1)/2, 2d)
+        convolution state; T is then the frames of one chunk."""
         d_act = self.act
         P1, P2 = _ffn_params(self.ffn_module1), _ffn_params(self.ffn_module2)
         Pc = self.convolution_module.params()
@@ -136,7 +217,7 @@ class ConformerEncoderLayer(nn.Module):
             y2_3, bcell, post2 = cell(h.view(B, T, -1), need, res=y1, ln_next=(Pc["ln1_w"], Pc["ln1_b"], 1e-5))   # :512-530
             y2 = ops.rows2d(y2_3)
             y3, bconv, post3 = F.conv_module_fwd(y2, Pc, d_act, m8, B, T, need, dtype, chunk, p=pd, pre_ln=post2,
-                                                 ln_next=(P2["ln_w"], P2["ln_b"], 1e-5))                          # :532-534
+                                                 ln_next=(P2["ln_w"], P2["ln_b"], 1e-5), conv_state=conv_state)   # :532-534
             # (norm2's output is the layer output = the next layer's residual stream: stream dtype, 4th element of ln_next)
             # (inside a stack: where norm2 rides in the second FFN's down-projection, the NEXT layer's first LayerNorm can ride with it)
             y4, bf2, post4, post_next = F.ffn_module_fwd(y3, P2, d_act, need, dtype, p=pd, pre_ln=post3, ln_next=(n2.weight, n2.bias, n2.eps, True),
@@ -198,8 +279,44 @@ class ConformerEncoderLayer(nn.Module):
             return ops.cast(ops.rows2d(y), xin.dtype).view(B, T, d), b
         return F.block(x, run, list(self.parameters())), None
 
-    def forward_streaming(self, *a, **k):
-        raise NotImplementedError("streaming inference is broken for SummaryMixing in the reference (SURVEY §2 row 5)")
+    def make_streaming_context(self, dynchunktrain_config: DynChunkTrainConfig):
+        """A blank streaming context for this layer (reference :618-633 takes the left context in frames, because it keeps raw
+        frames; this layer keeps per-chunk sums and needs the chunk size as well, hence the whole configuration)."""
+        _stream_refuse(self, dynchunktrain_config)
+        return ConformerEncoderLayerStreamingContext(dynchunktrain_config=dynchunktrain_config)
+
+    def _stream_alloc(self, ctx, B, compute, device, counter):
+        d = self.norm1.norm.weight.shape[0]
+        sdim = self.mha_layer.local_proj_out_dim if self.mode == "SummaryMixing-fast" else self.mha_layer.summary_out_dim
+        left = ctx.dynchunktrain_config.left_context_size
+        ring = (torch.zeros((B, sdim), dtype=torch.float32, device=device) if left is None else
+                torch.zeros((B, left, sdim), dtype=torch.float32, device=device) if left > 0 else None)
+        ctx.summary = F.DynChunkStream(ring, counter, ctx.dynchunktrain_config.chunk_size, left)
+        H = (self.convolution_module.kernel_size - 1) // 2
+        ctx.dcconv_state = torch.zeros((B, H, 2 * d), dtype=compute, device=device)
+        ctx.counter, ctx.batch_size, ctx.dtype, ctx.device = counter, B, compute, torch.device(device)
+
+    def _stream_run(self, ctx, B, C_cur, compute_dtype=None, next_layer=None):
+        return self.make_run(B, C_cur, None, ctx.summary, 0, compute_dtype=compute_dtype, next_layer=next_layer,
+                             conv_state=ctx.dcconv_state)
+
+    def forward_streaming(self, x, context: ConformerEncoderLayerStreamingContext, pos_embs: torch.Tensor = None):
+        """One chunk (B, C_cur, d) of a stream through this layer (reference :539-616).  Returns (output, None); the context
+        carries the summary and convolution state to the next call."""
+        B, C_cur, d = x.shape
+        if _stream_check(context, self.training, B, C_cur, x.dtype, x.device):
+            self._stream_alloc(context, B, x.dtype, x.device, torch.zeros(1, dtype=torch.int64, device=x.device))
+        stream = F.stream_dtype(x.dtype)
+        with torch.no_grad():
+            if stream == x.dtype:
+                y, _ = self._stream_run(context, B, C_cur)(x, False)
+            else:                                   # (the float32 residual stream of a bf16 layer, as in forward)
+                run = self._stream_run(context, B, C_cur, compute_dtype=x.dtype)
+                y, _ = run(ops.cast(ops.rows2d(x), stream).view(B, C_cur, d), False)
+                y = ops.cast(ops.rows2d(y), x.dtype).view(B, C_cur, d)
+            ops.step_counter_add(context.counter, 1)
+        _stream_commit(context, C_cur)
+        return y, None
 
 
 class ConformerEncoder(nn.Module):
@@ -225,4 +342,44 @@ class ConformerEncoder(nn.Module):
         out = F.encoder_stack(src, list(self.layers),
                               lambda layer, compute, nxt=None: layer.make_run(B, T, m8, src_mask, chunk, compute_dtype=compute, next_layer=nxt),
                               self.norm.norm, list(self.parameters()), _compute_dtype, pair_next=True)
+        return out, [None] * len(self.layers)
+
+    def make_streaming_context(self, dynchunktrain_config: DynChunkTrainConfig):
+        """A blank streaming context for the whole stack (reference :840-857); state is allocated on the first chunk."""
+        for layer in self.layers:
+            _stream_refuse(layer, dynchunktrain_config)
+        return ConformerEncoderStreamingContext(dynchunktrain_config=dynchunktrain_config,
+                                                layers=[layer.make_streaming_context(dynchunktrain_config) for layer in self.layers])
+
+    def _stream_begin(self, context, B, C_cur, compute, device):
+        """Validate the chunk; allocate the state on the first one."""
+        if _stream_check(context, self.training, B, C_cur, compute, device):
+            counter = torch.zeros(1, dtype=torch.int64, device=device)
+            for layer, lc in zip(self.layers, context.layers):
+                layer._stream_alloc(lc, B, compute, device, counter)
+            context.counter, context.batch_size, context.dtype, context.device = counter, B, compute, torch.device(device)
+
+    def _stream_chunk(self, src, context, compute):
+        """The launches of one chunk step (no validation, no host bookkeeping - what a captured step records): the layers with the
+        LayerNorm pair fusion of `forward` (functional.encoder_stack), the final LayerNorm, then the counter (and PE) advance."""
+        B, C_cur, _ = src.shape
+        ctx_of = {id(layer): lc for layer, lc in zip(self.layers, context.layers)}
+        out = F.encoder_stack(src, list(self.layers),
+                              lambda layer, comp, nxt=None: layer._stream_run(ctx_of[id(layer)], B, C_cur, comp, nxt),
+                              self.norm.norm, list(self.parameters()), compute, pair_next=True)
+        if context.pe_table is not None:
+            ops.stream_advance(context.counter, context.pe_table, context.pe, context.dynchunktrain_config.chunk_size)
+        else:
+            ops.step_counter_add(context.counter, 1)
+        return out
+
+    def forward_streaming(self, src, context: ConformerEncoderStreamingContext, pos_embs: Optional[torch.Tensor] = None):
+        """One chunk (B, C_cur, d) of B streams through the stack (reference :788-838).  Fed the consecutive chunks of equal-length
+        utterances, the outputs concatenate to forward(src, dynchunktrain_config=cfg) of the whole utterances.  A chunk shorter than
+        chunk_size ends the stream.  Returns (output, [None] * layers)."""
+        B, C_cur, _ = src.shape
+        self._stream_begin(context, B, C_cur, src.dtype, src.device)
+        with torch.no_grad():
+            out = self._stream_chunk(src, context, src.dtype)
+        _stream_commit(context, C_cur)
         return out, [None] * len(self.layers)

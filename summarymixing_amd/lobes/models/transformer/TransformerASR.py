@@ -2,11 +2,17 @@
 
 Mirrors speechbrain/lobes/models/transformer/TransformerASR.py (:50-180 masks, :281-360 ctor, :501-560 encode,
 :687-741 EncoderWrapper) and Transformer.py:284-335 (PositionalEncoding), :201-259 (encoder dispatch) for
-attention_type="SummaryMixing" with encoder_module in {"conformer", "branchformer"}.  The MHA decoder, the
-vanilla-Transformer encoder (broken for SummaryMixing in the reference) and streaming are out of scope.
+attention_type="SummaryMixing" with encoder_module in {"conformer", "branchformer"}.  The MHA decoder and the
+vanilla-Transformer encoder (broken for SummaryMixing in the reference) are out of scope.
+
+Streaming (:562-685,731-741): make_streaming_context / encode_streaming run a Dynamic-Chunk-trained Conformer encoder one chunk at a
+time, from the encoder input on (the front-end is not streamed).  Chunk c gets rows [c C, c C + C_cur) of the positional table, as
+the full forward does; a fixed (C, d) buffer holds them and is advanced on device after each chunk, so a chunk step has one shape
+and no host-side state, and can be captured in a hipGraph (summarymixing_amd.streaming.CapturedStreamStep).
 """
 import math
-from typing import Optional
+from dataclasses import dataclass
+from typing import Any, Optional
 
 import torch
 from torch import nn
@@ -18,6 +24,14 @@ from ....utils.dynamic_chunk_training import DynChunkTrainConfig  # noqa: F401
 from ...models.VanillaNN import Linear
 from .Branchformer import BranchformerEncoder
 from .Conformer import ConformerEncoder
+
+
+@dataclass
+class TransformerASRStreamingContext:
+    """Streaming state of a TransformerASR (reference :36-47): the configuration and the encoder's context, which also holds the
+    positional-table buffer of the current chunk."""
+    dynchunktrain_config: DynChunkTrainConfig
+    encoder_context: Any
 
 
 def length_to_mask(length, max_len=None):
@@ -166,6 +180,57 @@ class TransformerASR(nn.Module):
         return out
 
 
+    def make_streaming_context(self, dynchunktrain_config: DynChunkTrainConfig, encoder_kwargs={}):
+        """A blank streaming context (reference :562-590).  Refused (NotImplementedError): the Branchformer, the SummaryMixing-lite
+        and -expdecay modes (their Dynamic Chunk Training forward is not causal) and sequence-parallel mode."""
+        if not isinstance(self.encoder, ConformerEncoder):
+            raise NotImplementedError("streaming inference runs the Conformer encoder only (the Branchformer refuses Dynamic "
+                                      "Chunk Training)")
+        enc = self.encoder.make_streaming_context(dynchunktrain_config, **encoder_kwargs)
+        return TransformerASRStreamingContext(dynchunktrain_config=dynchunktrain_config, encoder_context=enc)
+
+    def encode_streaming(self, src, context: TransformerASRStreamingContext):
+        """Encode one chunk (B, C_cur, F) (or (B, C_cur, ch1, ch2), reshaped as in encode) of B equal-length streams (reference
+        :592-685).  The chunks of an utterance, fed in order with one context, give encode(src, wav_len=1,
+        dynchunktrain_config=cfg) of the whole utterance; a chunk shorter than chunk_size ends the stream.  Running past
+        max_length raises ValueError."""
+        if src.dim() == 4:
+            bz, t, ch1, ch2 = src.shape
+            src = src.reshape(bz, t, ch1 * ch2)
+        ec = self._stream_begin(src, context)
+        with torch.no_grad():
+            out = self._stream_chunk(src, ec)
+        ec.frames += src.shape[1]
+        ec.closed = src.shape[1] < ec.dynchunktrain_config.chunk_size
+        return out
+
+    def _stream_begin(self, src, context):
+        """Validate the chunk (host only) and allocate the state on the first one; -> the encoder context."""
+        ec = context.encoder_context
+        B, C_cur, _ = src.shape
+        if self.positional_encoding_type == "fixed_abs_sine" and ec.frames + C_cur > self.positional_encoding.max_len:
+            raise ValueError(f"streaming: frame {ec.frames + C_cur} exceeds max_length {self.positional_encoding.max_len}")
+        first = ec.batch_size is None
+        self.encoder._stream_begin(ec, B, C_cur, src.dtype, src.device)
+        if first:
+            C, d = ec.dynchunktrain_config.chunk_size, self.custom_src_module.layers[0].w.weight.shape[0]
+            if self.positional_encoding_type == "fixed_abs_sine":
+                ec.pe_table = self.positional_encoding.pe[0]
+                ec.pe = torch.zeros((C, d), dtype=ec.pe_table.dtype, device=src.device)
+                n = min(C, ec.pe_table.shape[0])
+                ec.pe[:n] = ec.pe_table[:n]            # chunk 0's rows; smx_stream_advance writes the later ones
+            else:
+                ec.pe = torch.zeros((C, d), device=src.device)
+        return ec
+
+    def _stream_chunk(self, src, ec):
+        """The launches of one chunk step: input projection + the chunk's PE rows, the encoder, the counter / PE advance."""
+        C_cur = src.shape[1]
+        lin = self.custom_src_module.layers[0].w
+        x = F.input_proj_pe(src, lin.weight, lin.bias, ec.pe[:C_cur], C_cur, 0.0)
+        return self.encoder._stream_chunk(x, ec, src.dtype)
+
+
 class EncoderWrapper(nn.Module):
     """forward() = transformer.encode() (TransformerASR.py:715-729)."""
 
@@ -176,3 +241,11 @@ class EncoderWrapper(nn.Module):
     def forward(self, x, wav_lens=None, pad_idx=0, **kwargs):
         return self.transformer.encode(x, wav_lens, pad_idx, **kwargs,
                                        masked_false_or_true=self.transformer.masked_false_or_true)
+
+    def forward_streaming(self, x, context):
+        """transformer.encode_streaming (reference :731-736)."""
+        return self.transformer.encode_streaming(x, context)
+
+    def make_streaming_context(self, *args, **kwargs):
+        """transformer.make_streaming_context (reference :738-741)."""
+        return self.transformer.make_streaming_context(*args, **kwargs)

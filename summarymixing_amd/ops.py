@@ -475,6 +475,19 @@ def chunk_mean(s, out, B, T, chunk, left, reverse=False):
     return out
 
 
+def stream_summary(s, out, B, C_cur, C, left, ring, counter):
+    """Streaming DynChunk summary of one chunk (smx_stream_summary): out (B*C_cur, D) rows = the window mean of chunk `counter`;
+    the chunk's float32 sums go into `ring` ((B, left, D); (B, D) running sums for left = None; unused for left = 0)."""
+    D = s.shape[1]
+    ps, lds = _mat(s)
+    po, ldo = _mat(out)
+    tok = _pb(f"stream_summary ({B},{C_cur},{D})", 2 * B * C_cur * D * _es(s))
+    L.check(L.lib().smx_stream_summary(dt(s), ps, lds, po, ldo, _p(ring), _p(counter), B, C_cur, C, D, -1 if left is None else left,
+                                       _stream()), "smx_stream_summary")
+    _pe(tok)
+    return out
+
+
 def expdecay_mean(s, out, B, T, decay, reverse=False):
     """out = (M s)/rowsum(M) with M_ij = decay^|i-j| (reverse: the transposed operator M (s/rowsum(M))); O(T)."""
     D = s.shape[1]
@@ -636,6 +649,28 @@ def dwconv_fwd(p, w, bias, B, T, D, k, glu, pad_mode=L.PAD_ZERO, chunk=0, gate=N
     if drop is not None and drop[0] > 0.0 and not fused:
         dropout(y, drop[0], drop[1], out=y)
     return y
+
+
+def dwconv_stream(p, w, bias, state, B, C_cur, D, k):
+    """GLU + depthwise conv over one chunk of B streams (smx_dwconv1d_glu_stream): rows before the chunk come from `state`
+    ((B, (k-1)/2, 2D), compute dtype), which the kernel then replaces in place with the chunk's last (k-1)/2 pre-GLU rows."""
+    assert state.dtype == p.dtype and state.is_contiguous() and state.shape == (B, (k - 1) // 2, 2 * D)
+    y = torch.empty((B * C_cur, D), dtype=p.dtype, device=p.device)
+    pp, ldp = _mat(p)
+    tok = _pb(f"dwconv_stream ({B},{C_cur},{D}) k={k}", 3 * B * C_cur * D * _es(p))
+    L.check(L.lib().smx_dwconv1d_glu_stream(dt(p), pp, ldp, _p(w), _p(bias), _p(state), _p(y), D, B, C_cur, D, k, _stream()),
+            "smx_dwconv1d_glu_stream")
+    _pe(tok)
+    return y
+
+
+def stream_advance(counter, table, pe, C):
+    """End of a chunk step (smx_stream_advance): counter += 1 and pe (C, D) = the table's rows of the next chunk."""
+    assert table.dtype == pe.dtype
+    pt, ldt = _mat(table)
+    pp, ldpe = _mat(pe)
+    L.check(L.lib().smx_stream_advance(dt(pe), _p(counter), pt, ldt, table.shape[0], pp, ldpe, C, pe.shape[1], _stream()),
+            "smx_stream_advance")
 
 
 def dwconv_bwd(dy, p, w, bias, dw, dbias, B, T, D, k, glu, pad_mode=L.PAD_ZERO, chunk=0, gate=None, dgate_out=None, ws=None):
