@@ -616,6 +616,33 @@ int smx_dwconv1d_glu_stream(int dtype, const void* P, int64_t ldp, const float* 
 int smx_stream_advance(int dtype, uint64_t* counter, const void* table, int64_t ldt, int rows, void* pe, int64_t ldpe, int C, int D,
                        void* stream);
 
+/* ---- Slot streaming: B independent streams, one per batch slot, in one fixed step of B x C rows --------------------------------
+ * The lockstep calls above with per-slot state.  Row t of slot b is row b * C + t of every (B*C, .) operand.  counters (B,) int64
+ * holds each slot's chunk index c (shared by all layers); counter 0 means fresh state: chunk 0 reads no ring slot, no running sum
+ * and no convolution state, so a slot starts a new stream by counters[b] = 0 alone (smx_slot_begin) and no state buffer is
+ * cleared.  valid (B,) int32 holds the frames of slot b in this step, 0 .. C: C = a full chunk, 1 .. C-1 = the stream's last,
+ * 0 = the slot sits out (nothing of it is read or written, its state is untouched).  Rows at and beyond valid[b] are never loaded
+ * (they may hold NaN), and output rows at and beyond valid[b] are not written.  counters / valid / start are device arrays, so a
+ * captured step stays valid on replay.  A step is smx_slot_begin, the layers, smx_slot_advance.
+ * smx_slot_summary: smx_stream_summary per slot: window of chunk counters[b], frame count min(c, left) * C + valid[b]; for left = -1
+ *   the running sum is written, not added to, at chunk 0.  Same fixed summation order: a full chunk gives the bits of
+ *   smx_stream_summary on the same inputs.  dtype F32 | BF16, D % 8 == 0, 1 <= C <= 64, -1 <= left <= 32, B <= 65535.
+ * smx_dwconv1d_glu_slots: smx_dwconv1d_glu_stream per slot with C_cur = valid[b]: the state (B, H, 2D) reads as zero at chunk 0, and
+ *   is rewritten in place with the last H rows of [state; chunk[:valid[b]]] (not at all for valid[b] == 0).  dtype F32 | BF16,
+ *   D % 8 == 0, odd k <= 63, 1 <= C <= 64, B <= 65535.
+ * smx_slot_begin: the first launch of a step.  counters[b] = 0 where start[b] (uint8 (B,)), then pe[b * C + r, :] =
+ *   table[counters[b] * C + r, :] for r < C (zero at and beyond `rows`): each slot's rows of the positional table in a fixed (B*C, D)
+ *   buffer.  pe = NULL: counters only (table unused).  Grid (C, B), no per-element division.
+ * smx_slot_advance: the last launch of a step.  counters[b] += (valid[b] == C): a sat-out slot or a closing last chunk does not
+ *   advance. */
+int smx_slot_summary(int dtype, const void* S, int64_t lds, void* out, int64_t ldo, float* ring, const int64_t* counters,
+                     const int32_t* valid, int B, int C, int D, int left, void* stream);
+int smx_dwconv1d_glu_slots(int dtype, const void* P, int64_t ldp, const float* w, const float* bias, void* state, void* Y,
+                           int64_t ldy, const int32_t* valid, const int64_t* counters, int B, int C, int D, int k, void* stream);
+int smx_slot_begin(int dtype, int64_t* counters, const uint8_t* start, const void* table, int64_t ldt, int rows, void* pe,
+                   int64_t ldpe, int B, int C, int D, void* stream);
+int smx_slot_advance(int64_t* counters, const int32_t* valid, int B, int C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

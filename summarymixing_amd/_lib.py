@@ -201,6 +201,10 @@ SIGNATURES = {
     "smx_stream_summary": (c_i, [c_i, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_vp]),
     "smx_dwconv1d_glu_stream": (c_i, [c_i, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_i, c_i, c_i, c_i, c_vp]),
     "smx_stream_advance": (c_i, [c_i, c_vp, c_vp, c_i64, c_i, c_vp, c_i64, c_i, c_i, c_vp]),
+    "smx_slot_summary": (c_i, [c_i, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_vp]),
+    "smx_dwconv1d_glu_slots": (c_i, [c_i, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i, c_i, c_i, c_i, c_vp]),
+    "smx_slot_begin": (c_i, [c_i, c_vp, c_vp, c_vp, c_i64, c_i, c_vp, c_i64, c_i, c_i, c_i, c_vp]),
+    "smx_slot_advance": (c_i, [c_vp, c_vp, c_i, c_i, c_vp]),
 }
 
 _lib = None

@@ -4,6 +4,7 @@
 // the DynChunk summary (window mean over the chunks [c - left, c]) and the depthwise convolution (the (k-1)/2 previous inputs).
 // Their state lives in caller-owned device buffers and is advanced by the kernels below; the chunk index c comes from a
 // device-resident counter (smx_step_counter_add convention), so a captured chunk step stays valid on replay.
+// The slot kernels (second half) run B independent streams, one per batch slot, each with its own chunk counter and length.
 #include "smx_common.h"
 
 namespace smx {
@@ -115,6 +116,129 @@ __global__ __launch_bounds__(256) void stream_advance_kernel(uint64_t* counter, 
   if (threadIdx.x == 0) counter[0] = next;
 }
 
+// ==== slot streaming: B independent streams, one per batch slot ============================================================
+// counters (B,) int64: the chunk index of each slot's stream.  Counter 0 means fresh state: chunk 0 reads no ring slot, no
+// running sum and no convolution state (they are read as zero), so starting a slot is counters[b] = 0 and nothing else.
+// valid (B,) int32: the frames of slot b in this step (0 = the slot sits out: nothing of it is read or written).
+
+// ---- summary of one step: grid (ceil(D / 64), B), 256 threads.  stream_summary_kernel with a per-slot chunk index and length:
+// only the rows t < valid[b] are loaded; the fold order (4 wave partials, then the window oldest first) is the same, so a full
+// chunk gives the bits of stream_summary_kernel.
+template <typename T>
+__global__ __launch_bounds__(256) void slot_summary_kernel(const T* __restrict__ S, long lds, T* __restrict__ out, long ldo,
+                                                           float* __restrict__ ring, const int64_t* __restrict__ counters,
+                                                           const int32_t* __restrict__ valid, int C, int D, int left) {
+  __shared__ float red[4][ST_COLS];
+  __shared__ float mean[ST_COLS];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, b = blockIdx.y;
+  const int v = min(valid[b], C);                         // (clamped: a bad host value cannot index past the slot's rows)
+  if (v <= 0) return;                                     // (uniform over the workgroup: before any barrier)
+  const int col = blockIdx.x * ST_COLS + lane;
+  const bool ok = col < D;
+  const long c = (long)counters[b];
+  float acc = 0.f;
+  if (ok)
+    for (int t = w; t < v; t += 4) acc += to_f32(S[((long)b * C + t) * lds + col]);
+  red[w][lane] = acc;
+  __syncthreads();
+  if (w == 0) {
+    const float csum = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
+    float win = 0.f;
+    long frames;
+    if (left < 0) {                                       // unlimited: ring = one running (B, D) sum, not read at chunk 0
+      float* r = ring + (long)b * D + col;
+      if (ok) { if (c > 0) win = *r; *r = win + csum; }
+      frames = c * C + v;
+    } else {
+      const long nprev = c < left ? c : left;
+      float* r = ring + (long)b * left * D + col;
+      if (ok) {
+        for (long j = c - nprev; j < c; ++j) win += r[(j % left) * D];
+        if (left > 0) r[(c % left) * D] = csum;
+      }
+      frames = nprev * C + v;
+    }
+    mean[lane] = (win + csum) / (float)frames;
+  }
+  __syncthreads();
+  if (!ok) return;
+  const T m = from_f32<T>(mean[lane]);
+  for (int t = w; t < v; t += 4) out[((long)b * C + t) * ldo + col] = m;
+}
+
+// ---- GLU + depthwise conv of one step: grid (ceil(D / 64), B), 256 threads.  dwconv_stream_kernel with C_cur = valid[b] and the
+// state read as zero at chunk 0; chunk rows at and beyond valid[b] are never loaded.  valid[b] == 0: the workgroup returns
+// before it reads or writes anything.
+template <typename T>
+__global__ __launch_bounds__(256) void dwconv_slots_kernel(const T* __restrict__ P, long ldp, const float* __restrict__ w,
+                                                           const float* __restrict__ bias, T* state, T* __restrict__ Y, long ldy,
+                                                           const int32_t* __restrict__ valid, const int64_t* __restrict__ counters,
+                                                           int C, int D, int k) {
+  __shared__ float u[ST_HMAX + ST_CMAX][ST_COLS];
+  __shared__ float raw[ST_HMAX][2][ST_COLS];
+  __shared__ float wl[ST_KMAX][ST_COLS];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, b = blockIdx.y;
+  const int v = min(valid[b], C);                         // (clamped: a bad host value cannot index past the slot's rows)
+  if (v <= 0) return;                                     // (uniform over the workgroup: before any barrier)
+  const bool fresh = counters[b] == 0;
+  const int ch = blockIdx.x * ST_COLS + lane;
+  const bool ok = ch < D;
+  const int H = (k - 1) / 2, R = H + v;
+  T* st = state + (long)b * H * 2 * D;
+  for (int i = wv; i < R; i += 4) {
+    float a = 0.f, g = 0.f;
+    if (ok && !(i < H && fresh)) {
+      const T* row = i < H ? st + (long)i * 2 * D : P + ((long)b * C + (i - H)) * ldp;
+      a = to_f32(row[ch]);
+      g = to_f32(row[D + ch]);
+    }
+    u[i][lane] = a * sigmoidf_(g);
+    if (i >= v) { raw[i - v][0][lane] = a; raw[i - v][1][lane] = g; }
+  }
+  for (int j = wv; j < k; j += 4) wl[j][lane] = ok ? w[(long)ch * k + j] : 0.f;
+  __syncthreads();
+  if (!ok) return;
+  const float bs = bias ? bias[ch] : 0.f;
+  for (int t = wv; t < v; t += 4) {
+    float acc = bs;
+    const int jmax = min(k, R - t);
+    for (int j = 0; j < jmax; ++j) acc += wl[j][lane] * u[t + j][lane];
+    Y[((long)b * C + t) * ldy + ch] = from_f32<T>(acc);
+  }
+  for (int i = wv; i < H; i += 4) {
+    st[(long)i * 2 * D + ch] = from_f32<T>(raw[i][0][lane]);
+    st[(long)i * 2 * D + D + ch] = from_f32<T>(raw[i][1][lane]);
+  }
+}
+
+// ---- first launch of a step: grid (C, B) (pe == NULL: (1, B)), 256 threads.  Workgroup (r, b): c = start[b] ? 0 : counters[b],
+// pe[b, r] = table[c C + r] (zero past the table).  Only workgroup (0, b) writes counters[b] (to 0, where start[b]); the others
+// read it, but a started slot's value is never used, so the read needs no ordering.
+template <typename T>
+__global__ __launch_bounds__(256) void slot_begin_kernel(int64_t* counters, const uint8_t* __restrict__ start,
+                                                         const T* __restrict__ table, long ldt, int rows, T* __restrict__ pe, long ldpe,
+                                                         int C, int D) {
+  const int r = blockIdx.x, b = blockIdx.y;
+  const bool s = start[b] != 0;
+  if (pe) {
+    const long row = (s ? 0 : (long)counters[b]) * C + r;
+    T* dst = pe + ((long)b * C + r) * ldpe;
+    if (row < rows) {
+      const T* src = table + row * ldt;
+      for (int col = threadIdx.x; col < D; col += 256) dst[col] = src[col];
+    } else {
+      for (int col = threadIdx.x; col < D; col += 256) dst[col] = from_f32<T>(0.f);
+    }
+  }
+  if (s && r == 0 && threadIdx.x == 0) counters[b] = 0;
+}
+
+// ---- last launch of a step: counters[b] += (valid[b] == C), one thread per slot --------------------------------------------
+__global__ __launch_bounds__(256) void slot_advance_kernel(int64_t* counters, const int32_t* __restrict__ valid, int B, int C) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b < B && valid[b] == C) counters[b] = counters[b] + 1;
+}
+
 }  // namespace smx
 
 using namespace smx;
@@ -171,4 +295,66 @@ extern "C" int smx_stream_advance(int dtype, uint64_t* counter, const void* tabl
     hipLaunchKernelGGL(stream_advance_kernel<float>, dim3(1), dim3(256), 0, STREAM, counter, (const float*)table, (long)ldt, rows,
                        (float*)pe, (long)ldpe, C, D);
   return check_launch("smx_stream_advance");
+}
+
+extern "C" int smx_slot_summary(int dtype, const void* S, int64_t lds, void* out, int64_t ldo, float* ring, const int64_t* counters,
+                                const int32_t* valid, int B, int C, int D, int left, void* stream) {
+  SMX_REQUIRE(dtype == SMX_F32 || dtype == SMX_BF16, "smx_slot_summary: bad dtype");
+  SMX_REQUIRE(S && out && counters && valid && (ring || left == 0), "smx_slot_summary: null pointer");
+  SMX_REQUIRE(B > 0 && B <= 65535 && D > 0 && D % 8 == 0, "smx_slot_summary: 0 < B <= 65535 and D %% 8 == 0 (B=%d D=%d)", B, D);
+  SMX_REQUIRE(C >= 1 && C <= ST_CMAX, "smx_slot_summary: 1 <= C <= %d (C=%d)", ST_CMAX, C);
+  SMX_REQUIRE(left >= -1 && left <= 32, "smx_slot_summary: left in {-1 (unlimited), 0 .. 32} (left=%d)", left);
+  SMX_REQUIRE(lds >= D && ldo >= D, "smx_slot_summary: row strides must be >= D");
+  dim3 grid((unsigned)((D + ST_COLS - 1) / ST_COLS), (unsigned)B);
+  if (dtype == SMX_BF16)
+    hipLaunchKernelGGL(slot_summary_kernel<bf16_t>, grid, dim3(256), 0, STREAM, (const bf16_t*)S, (long)lds, (bf16_t*)out, (long)ldo,
+                       ring, counters, valid, C, D, left);
+  else
+    hipLaunchKernelGGL(slot_summary_kernel<float>, grid, dim3(256), 0, STREAM, (const float*)S, (long)lds, (float*)out, (long)ldo,
+                       ring, counters, valid, C, D, left);
+  return check_launch("smx_slot_summary");
+}
+
+extern "C" int smx_dwconv1d_glu_slots(int dtype, const void* P, int64_t ldp, const float* w, const float* bias, void* state, void* Y,
+                                      int64_t ldy, const int32_t* valid, const int64_t* counters, int B, int C, int D, int k,
+                                      void* stream) {
+  SMX_REQUIRE(dtype == SMX_F32 || dtype == SMX_BF16, "smx_dwconv1d_glu_slots: bad dtype");
+  SMX_REQUIRE(P && w && Y && valid && counters && (state || k == 1), "smx_dwconv1d_glu_slots: null pointer");
+  SMX_REQUIRE(k >= 1 && k <= ST_KMAX && (k & 1), "smx_dwconv1d_glu_slots: k=%d must be odd and <= %d", k, ST_KMAX);
+  SMX_REQUIRE(B > 0 && B <= 65535 && D > 0 && D % 8 == 0, "smx_dwconv1d_glu_slots: 0 < B <= 65535 and D %% 8 == 0 (B=%d D=%d)", B,
+              D);
+  SMX_REQUIRE(C >= 1 && C <= ST_CMAX, "smx_dwconv1d_glu_slots: 1 <= C <= %d (C=%d)", ST_CMAX, C);
+  SMX_REQUIRE(ldp >= 2 * (int64_t)D && ldy >= D, "smx_dwconv1d_glu_slots: ldp >= 2 D and ldy >= D");
+  dim3 grid((unsigned)((D + ST_COLS - 1) / ST_COLS), (unsigned)B);
+  if (dtype == SMX_BF16)
+    hipLaunchKernelGGL(dwconv_slots_kernel<bf16_t>, grid, dim3(256), 0, STREAM, (const bf16_t*)P, (long)ldp, w, bias, (bf16_t*)state,
+                       (bf16_t*)Y, (long)ldy, valid, counters, C, D, k);
+  else
+    hipLaunchKernelGGL(dwconv_slots_kernel<float>, grid, dim3(256), 0, STREAM, (const float*)P, (long)ldp, w, bias, (float*)state,
+                       (float*)Y, (long)ldy, valid, counters, C, D, k);
+  return check_launch("smx_dwconv1d_glu_slots");
+}
+
+extern "C" int smx_slot_begin(int dtype, int64_t* counters, const uint8_t* start, const void* table, int64_t ldt, int rows, void* pe,
+                              int64_t ldpe, int B, int C, int D, void* stream) {
+  SMX_REQUIRE(dtype == SMX_F32 || dtype == SMX_BF16, "smx_slot_begin: bad dtype");
+  SMX_REQUIRE(counters && start && (!pe || table), "smx_slot_begin: null pointer");
+  SMX_REQUIRE(B > 0 && B <= 65535 && C >= 1 && C <= ST_CMAX && D > 0 && rows >= 0,
+              "smx_slot_begin: 0 < B <= 65535, 1 <= C <= %d, D > 0 (B=%d C=%d D=%d)", ST_CMAX, B, C, D);
+  SMX_REQUIRE(!pe || (ldt >= D && ldpe >= D), "smx_slot_begin: row strides must be >= D");
+  dim3 grid(pe ? (unsigned)C : 1u, (unsigned)B);
+  if (dtype == SMX_BF16)
+    hipLaunchKernelGGL(slot_begin_kernel<bf16_t>, grid, dim3(256), 0, STREAM, counters, start, (const bf16_t*)table, (long)ldt, rows,
+                       (bf16_t*)pe, (long)ldpe, C, D);
+  else
+    hipLaunchKernelGGL(slot_begin_kernel<float>, grid, dim3(256), 0, STREAM, counters, start, (const float*)table, (long)ldt, rows,
+                       (float*)pe, (long)ldpe, C, D);
+  return check_launch("smx_slot_begin");
+}
+
+extern "C" int smx_slot_advance(int64_t* counters, const int32_t* valid, int B, int C, void* stream) {
+  SMX_REQUIRE(counters && valid, "smx_slot_advance: null pointer");
+  SMX_REQUIRE(B > 0 && C >= 1 && C <= ST_CMAX, "smx_slot_advance: B > 0 and 1 <= C <= %d (B=%d C=%d)", ST_CMAX, B, C);
+  hipLaunchKernelGGL(slot_advance_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, STREAM, counters, valid, B, C);
+  return check_launch("smx_slot_advance");
 }

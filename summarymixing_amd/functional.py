@@ -740,6 +740,16 @@ class DynChunkStream:
         self.ring, self.counter, self.chunk_size, self.left_context = ring, counter, chunk_size, left_context
 
 
+class DynChunkSlots:
+    """One layer's summary state for slot streaming (B independent streams, one per batch slot): `ring` as in DynChunkStream,
+    `counters` the context's per-slot device chunk counters (int64 (B,), shared by all layers), `valid` the device int32 (B,)
+    frames of each slot in this step.  Passed as cell_run's sum_mask: the summary becomes smx_slot_summary."""
+
+    def __init__(self, ring, counters, valid, chunk_size, left_context=None):
+        self.ring, self.counters, self.valid = ring, counters, valid
+        self.chunk_size, self.left_context = chunk_size, left_context
+
+
 def _chunk_mean_seqpar(x, out, B, T, chunk, left, reverse=False):
     """The Dynamic Chunk Training summary (chunk c averages the chunks [c - left, c], all earlier ones with left = None:
     summary_mixing.py:224-235 with the mask of TransformerASR.py:85-110) with the time axis sharded over the sequence group.
@@ -863,6 +873,10 @@ def cell_run(P, cfg, B, T, mask, sum_mask, p_drop=0.0):
             if need_bwd or mode not in ("SummaryMixing", "SummaryMixing-fast"):
                 raise NotImplementedError("streaming summary: inference of the SummaryMixing / SummaryMixing-fast modes only")
             pool_kind = "stream"
+        elif isinstance(sm, DynChunkSlots):
+            if need_bwd or mode not in ("SummaryMixing", "SummaryMixing-fast"):
+                raise NotImplementedError("slot streaming summary: inference of the SummaryMixing / SummaryMixing-fast modes only")
+            pool_kind = "slots"
         elif sm is not None:
             pool_kind = "dense"
             w = sm.to(device=dev, dtype=torch.float32)
@@ -943,6 +957,9 @@ def cell_run(P, cfg, B, T, mask, sum_mask, p_drop=0.0):
         elif pool_kind == "stream":
             sbar = torch.empty((N, sdim), dtype=dtype, device=dev)
             ops.stream_summary(s, sbar, B, T, sm.chunk_size, sm.left_context, sm.ring, sm.counter)
+        elif pool_kind == "slots":
+            sbar = torch.empty((N, sdim), dtype=dtype, device=dev)
+            ops.slot_summary(s, sbar, B, T, sm.left_context, sm.ring, sm.counters, sm.valid)
         elif pool_kind == "expdecay":
             sbar = torch.empty((N, sdim), dtype=dtype, device=dev)
             ops.expdecay_mean(s, sbar, B, T, decay)
@@ -1259,12 +1276,14 @@ def ffn_module_fwd(x, P, act, need_bwd, dtype, alpha=0.5, p=0.0, pre_ln=None, ln
     return ret(bwd)
 
 def conv_module_fwd(x, P, act, mask, B, T, need_bwd, dtype, chunk=0, residual=True, p=0.0, pre_ln=None, ln_next=None,
-                    conv_state=None):
+                    conv_state=None, conv_slots=None):
     """y = [x +] mask * Linear(act(LN(dwconv(GLU(pw(LN(x)))))))   (Conformer.py:314-331,532-534).
     pre_ln / ln_next: as in ffn_module_fwd (the module's first LayerNorm done by the producer of x; the LayerNorm that
     follows the module done in the out-projection's epilogue).
     conv_state: streaming inference - x is one chunk of T frames of B streams, the depthwise conv reads its left context from
-    this (B, (k-1)/2, 2d) state and updates it (ops.dwconv_stream)."""
+    this (B, (k-1)/2, 2d) state and updates it (ops.dwconv_stream).
+    conv_slots: slot streaming - (valid, counters), the device arrays of functional.DynChunkSlots: each of the B slots runs its own
+    stream at its own chunk (ops.dwconv_slots), T = C rows per slot of which valid[b] are real."""
     d = x.shape[1]
     if SP.enabled():
         r = _conv_module_fwd_sp(x, P, act, mask, B, T, need_bwd, dtype, chunk, residual, p)
@@ -1279,7 +1298,10 @@ def conv_module_fwd(x, P, act, mask, B, T, need_bwd, dtype, chunk=0, residual=Tr
     else:
         if need_bwd:
             raise NotImplementedError("streaming convolution: inference only")
-        c = ops.dwconv_stream(p_, wd, P["bd"].detach() if P["bd"] is not None else None, conv_state, B, T, d, k)
+        if conv_slots is None:
+            c = ops.dwconv_stream(p_, wd, P["bd"].detach() if P["bd"] is not None else None, conv_state, B, T, d, k)
+        else:
+            c = ops.dwconv_slots(p_, wd, P["bd"].detach() if P["bd"] is not None else None, conv_state, *conv_slots, B, T, d, k)
     a, ln2_b = ln_fwd(c, P["ln2_w"], P["ln2_b"], 1e-5, need_bwd, act)      # LN + activation fused
     Wo = wcast(P["Wo"], dtype)
     dr = (p, ops.new_dropout_seed()) if p > 0.0 else None   # Linear -> Dropout -> * mask (+ x): one epilogue

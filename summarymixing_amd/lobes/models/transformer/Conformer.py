@@ -16,10 +16,15 @@ Streaming inference (forward_streaming / make_streaming_context, reference :539-
 encoder one chunk at a time and equals the masked full-utterance forward.  Unlike the reference, which keeps raw input frames as
 left context and recomputes them on every chunk (its own TODO), a layer here carries only what the next chunk reads: the float32
 per-chunk sums of the summary branch and the last (k-1)/2 pre-GLU rows of the convolution (functional.DynChunkStream, ops.dwconv_stream).
+
+Slot streaming (forward_slots / make_slot_context) runs B independent streams, one per batch slot, in one fixed step of B x C
+frames: each slot has its own device chunk counter, its own frame count in the step (valid) and starts a new stream when told to
+(start).  Counter 0 means fresh state, so starting a slot clears no buffer (functional.DynChunkSlots, ops.dwconv_slots).
 """
 from dataclasses import dataclass, field
-from typing import List, Optional
+from typing import Any, List, Optional
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -88,6 +93,97 @@ def _stream_check(ctx, training, B, C_cur, dtype, device):
 def _stream_commit(ctx, C_cur):
     ctx.frames += C_cur
     ctx.closed = C_cur < ctx.dynchunktrain_config.chunk_size
+
+
+@dataclass
+class ConformerEncoderLayerSlotContext:
+    """Slot-streaming state of one ConformerEncoderLayer: the ConformerEncoderLayerStreamingContext buffers with one row per slot.
+      summary      - functional.DynChunkSlots: (B, left, s) / (B, s) float32 ring and the encoder's per-slot counters and valid;
+      dcconv_state - (B, (k-1)/2, 2 d) in the compute dtype.
+    Neither is ever cleared: a slot's counter 0 makes the kernels read its state as zero."""
+    dynchunktrain_config: DynChunkTrainConfig
+    summary: Optional[F.DynChunkSlots] = None
+    dcconv_state: Optional[torch.Tensor] = None
+
+
+@dataclass
+class ConformerEncoderSlotContext:
+    """Slot-streaming state of a ConformerEncoder: `slots` independent streams in one step of slots x chunk_size frames.
+    Device: `counters` (B,) int64 per-slot chunk index shared by the layers; `valid` (B,) int32 and `start` (B,) uint8, the step's
+    arguments, copied from the host in stream order before the step's launches (views of one byte buffer `io`).
+    Host mirrors (never read back from the device): `frames` the frames each slot's stream has consumed, `open` whether it can
+    take another chunk (started, and not ended by a short chunk).  pe_table / pe: set by TransformerASR - the positional table and
+    the fixed (B*C, d) buffer of each slot's current rows, written by smx_slot_begin at the start of every step."""
+    dynchunktrain_config: DynChunkTrainConfig
+    slots: int
+    layers: List[ConformerEncoderLayerSlotContext] = field(default_factory=list)
+    counters: Optional[torch.Tensor] = None
+    io: Optional[torch.Tensor] = None
+    valid: Optional[torch.Tensor] = None
+    start: Optional[torch.Tensor] = None
+    dtype: Optional[torch.dtype] = None
+    device: Optional[torch.device] = None
+    frames: List[int] = field(default_factory=list)
+    open: List[bool] = field(default_factory=list)
+    pe_table: Optional[torch.Tensor] = None
+    pe: Optional[torch.Tensor] = None
+    staging: Any = None
+
+
+class _SlotStaging:
+    """Pinned host buffers for the step arguments: a ring of them, each reused only after the copy that last read it has run
+    (its event), so a step never waits for the device and never races an earlier step's copy."""
+
+    def __init__(self, B, n=4):
+        self.host = [torch.empty(5 * B, dtype=torch.uint8, pin_memory=True) for _ in range(n)]
+        self.events = [None] * n
+        self.i, self.B = 0, B
+
+    def copy(self, io, valid, start):
+        i, B = self.i, self.B
+        self.i = (i + 1) % len(self.host)
+        if self.events[i] is not None:
+            self.events[i].synchronize()
+        h = self.host[i].numpy()
+        h[:4 * B].view(np.int32)[:] = valid
+        h[4 * B:] = start
+        io.copy_(self.host[i], non_blocking=True)
+        ev = self.events[i] = self.events[i] or torch.cuda.Event()
+        ev.record()
+
+
+def _slot_args(ctx, training, src_shape, dtype, device, valid, start):
+    """Validate one slot step against the context (host only: no device read).  -> (valid, start) as lists of ints and the
+    frames each slot's stream holds before the step (0 for a started slot)."""
+    if training:
+        raise RuntimeError("slot streaming: call .eval() first (forward_slots runs no backward)")
+    C, B = ctx.dynchunktrain_config.chunk_size, ctx.slots
+    if len(src_shape) != 3 or src_shape[0] != B or src_shape[1] != C:
+        raise ValueError(f"slot streaming: expected a ({B}, {C}, F) step for {B} slots of chunk_size {C}, got {tuple(src_shape)}")
+    valid, start = [int(v) for v in valid], [bool(s) for s in start]
+    if len(valid) != B or len(start) != B:
+        raise ValueError(f"slot streaming: valid and start need {B} entries, got {len(valid)} and {len(start)}")
+    if ctx.dtype is not None and (dtype, torch.device(device)) != (ctx.dtype, ctx.device):
+        raise ValueError(f"slot streaming: the context was started with {ctx.dtype} on {ctx.device}; got {dtype} on {device}")
+    base = []
+    for b, (v, s) in enumerate(zip(valid, start)):
+        if not 0 <= v <= C:
+            raise ValueError(f"slot streaming: valid[{b}] = {v} is outside 0 .. {C}")
+        if v > 0 and not s and not (ctx.open and ctx.open[b]):
+            raise ValueError(f"slot streaming: slot {b} holds no open stream (never started, or ended by a short chunk); "
+                             "set start for it")
+        base.append(0 if s else (ctx.frames[b] if ctx.frames else 0))
+    return valid, start, base
+
+
+def _slot_commit(ctx, valid, start, base):
+    C = ctx.dynchunktrain_config.chunk_size
+    for b, (v, s) in enumerate(zip(valid, start)):
+        ctx.frames[b] = base[b] + v
+        if s:
+            ctx.open[b] = True
+        if 0 < v < C:
+            ctx.open[b] = False
 
 
 def _stream_refuse(layer, cfg):
@@ -187,7 +283,7 @@ class ConformerEncoderLayer(nn.Module):
         self.norm2 = _LayerNorm(d_model)
         self.drop = nn.Dropout(dropout)
 
-    def make_run(self, B, T, m8, src_mask, chunk, compute_dtype=None, next_layer=None, conv_state=None):
+    def make_run(self, B, T, m8, src_mask, chunk, compute_dtype=None, next_layer=None, conv_state=None, conv_slots=None):
         """compute_dtype: dtype of the GEMM operands when the incoming stream x3 is the float32 residual stream of a bf16
         model (functional.RESIDUAL_F32); None = everything in x3.dtype.
         next_layer: the layer that consumes this one's output inside an encoder stack.  Its first LayerNorm (ffn_module1's) then
@@ -195,7 +291,8 @@ class ConformerEncoderLayer(nn.Module):
         for both); run(..., with_post=True) then returns a third value, (LN(y), stats) | None, which the stack hands to the next
         layer's run as `pre_ln`.
         Streaming inference (forward_streaming): src_mask is a functional.DynChunkStream and conv_state the layer's (B, (k-1)/2, 2d)
-        convolution state; T is then the frames of one chunk."""
+        convolution state; T is then the frames of one chunk.  Slot streaming (forward_slots): src_mask is a functional.DynChunkSlots
+        and conv_slots its (valid, counters); B is the slot count and T the chunk size."""
         d_act = self.act
         P1, P2 = _ffn_params(self.ffn_module1), _ffn_params(self.ffn_module2)
         Pc = self.convolution_module.params()
@@ -217,7 +314,8 @@ class ConformerEncoderLayer(nn.Module):
             y2_3, bcell, post2 = cell(h.view(B, T, -1), need, res=y1, ln_next=(Pc["ln1_w"], Pc["ln1_b"], 1e-5))   # :512-530
             y2 = ops.rows2d(y2_3)
             y3, bconv, post3 = F.conv_module_fwd(y2, Pc, d_act, m8, B, T, need, dtype, chunk, p=pd, pre_ln=post2,
-                                                 ln_next=(P2["ln_w"], P2["ln_b"], 1e-5), conv_state=conv_state)   # :532-534
+                                                 ln_next=(P2["ln_w"], P2["ln_b"], 1e-5), conv_state=conv_state,
+                                                 conv_slots=conv_slots)                                           # :532-534
             # (norm2's output is the layer output = the next layer's residual stream: stream dtype, 4th element of ln_next)
             # (inside a stack: where norm2 rides in the second FFN's down-projection, the NEXT layer's first LayerNorm can ride with it)
             y4, bf2, post4, post_next = F.ffn_module_fwd(y3, P2, d_act, need, dtype, p=pd, pre_ln=post3, ln_next=(n2.weight, n2.bias, n2.eps, True),
@@ -299,6 +397,20 @@ class ConformerEncoderLayer(nn.Module):
     def _stream_run(self, ctx, B, C_cur, compute_dtype=None, next_layer=None):
         return self.make_run(B, C_cur, None, ctx.summary, 0, compute_dtype=compute_dtype, next_layer=next_layer,
                              conv_state=ctx.dcconv_state)
+
+    def _slot_alloc(self, lc, enc_ctx, B, compute, device):
+        d = self.norm1.norm.weight.shape[0]
+        sdim = self.mha_layer.local_proj_out_dim if self.mode == "SummaryMixing-fast" else self.mha_layer.summary_out_dim
+        left = lc.dynchunktrain_config.left_context_size
+        ring = (torch.empty((B, sdim), dtype=torch.float32, device=device) if left is None else
+                torch.empty((B, left, sdim), dtype=torch.float32, device=device) if left > 0 else None)
+        lc.summary = F.DynChunkSlots(ring, enc_ctx.counters, enc_ctx.valid, lc.dynchunktrain_config.chunk_size, left)
+        H = (self.convolution_module.kernel_size - 1) // 2
+        lc.dcconv_state = torch.empty((B, H, 2 * d), dtype=compute, device=device)   # (never read before a slot writes it)
+
+    def _slot_run(self, lc, enc_ctx, B, C, compute_dtype=None, next_layer=None):
+        return self.make_run(B, C, None, lc.summary, 0, compute_dtype=compute_dtype, next_layer=next_layer,
+                             conv_state=lc.dcconv_state, conv_slots=(enc_ctx.valid, enc_ctx.counters))
 
     def forward_streaming(self, x, context: ConformerEncoderLayerStreamingContext, pos_embs: torch.Tensor = None):
         """One chunk (B, C_cur, d) of a stream through this layer (reference :539-616).  Returns (output, None); the context
@@ -382,4 +494,59 @@ class ConformerEncoder(nn.Module):
         with torch.no_grad():
             out = self._stream_chunk(src, context, src.dtype)
         _stream_commit(context, C_cur)
+        return out, [None] * len(self.layers)
+
+    def make_slot_context(self, dynchunktrain_config: DynChunkTrainConfig, slots: int):
+        """A blank slot-streaming context for `slots` independent streams; state is allocated on the first step.  Refuses what
+        make_streaming_context refuses."""
+        for layer in self.layers:
+            _stream_refuse(layer, dynchunktrain_config)
+        if not 1 <= int(slots) <= 65535:
+            raise ValueError(f"slot streaming: 1 <= slots <= 65535, got {slots}")
+        return ConformerEncoderSlotContext(dynchunktrain_config=dynchunktrain_config, slots=int(slots),
+                                           layers=[ConformerEncoderLayerSlotContext(dynchunktrain_config) for _ in self.layers])
+
+    def _slot_begin(self, context, src_shape, compute, device, valid, start):
+        """Validate the step (host only) and allocate the state on the first one; -> (valid, start, base) for _slot_commit."""
+        args = _slot_args(context, self.training, src_shape, compute, device, valid, start)
+        if context.counters is None:
+            B = context.slots
+            context.counters = torch.zeros(B, dtype=torch.int64, device=device)
+            context.io = torch.zeros(5 * B, dtype=torch.uint8, device=device)
+            context.valid, context.start = context.io[:4 * B].view(torch.int32), context.io[4 * B:]
+            context.dtype, context.device = compute, torch.device(device)
+            context.frames, context.open = [0] * B, [False] * B
+            context.staging = _SlotStaging(B)
+            for layer, lc in zip(self.layers, context.layers):
+                layer._slot_alloc(lc, context, B, compute, device)
+        return args
+
+    def _slot_stage(self, context, valid, start):
+        """Copy the step's valid / start into the context's device buffers (in stream order, before the step's launches)."""
+        context.staging.copy(context.io, valid, start)
+
+    def _slot_layers(self, src, context, compute):
+        """The layers, the final LayerNorm and the counter advance of one slot step (what a captured step records after
+        smx_slot_begin)."""
+        B, C, _ = src.shape
+        ctx_of = {id(layer): lc for layer, lc in zip(self.layers, context.layers)}
+        out = F.encoder_stack(src, list(self.layers),
+                              lambda layer, comp, nxt=None: layer._slot_run(ctx_of[id(layer)], context, B, C, comp, nxt),
+                              self.norm.norm, list(self.parameters()), compute, pair_next=True)
+        ops.slot_advance(context.counters, context.valid, B, C)
+        return out
+
+    def forward_slots(self, src, valid, start, context: ConformerEncoderSlotContext):
+        """One step (B, C, d) of B independent streams, one per slot.  valid[b] (host ints, 0 .. C): slot b's frames in this step -
+        C a full chunk, 1 .. C-1 its stream's last chunk, 0 the slot sits out (its state is untouched).  start[b] (host bools): slot b
+        begins a new stream here.  Rows [:valid[b]] of slot b's outputs, over the steps of one stream, concatenate to that stream
+        alone through forward_streaming; rows at and beyond valid[b] are unspecified (input rows there are never read).
+        Returns (output, [None] * layers)."""
+        args = self._slot_begin(context, tuple(src.shape), src.dtype, src.device, valid, start)
+        self._slot_stage(context, args[0], args[1])
+        with torch.no_grad():
+            ops.slot_begin(context.counters, context.start, None, None, context.slots, context.dynchunktrain_config.chunk_size,
+                           src.shape[2])
+            out = self._slot_layers(src, context, src.dtype)
+        _slot_commit(context, *args)
         return out, [None] * len(self.layers)

@@ -9,6 +9,11 @@ Streaming (:562-685,731-741): make_streaming_context / encode_streaming run a Dy
 time, from the encoder input on (the front-end is not streamed).  Chunk c gets rows [c C, c C + C_cur) of the positional table, as
 the full forward does; a fixed (C, d) buffer holds them and is advanced on device after each chunk, so a chunk step has one shape
 and no host-side state, and can be captured in a hipGraph (summarymixing_amd.streaming.CapturedStreamStep).
+
+Slot streaming: make_slot_context / encode_slots run B independent streams, one per batch slot, in one step of B x C frames; each
+slot starts, pauses and ends its stream on its own (valid / start per step).  Slot b's positional rows come from its own chunk
+counter: smx_slot_begin writes them into a fixed (B*C, d) buffer at the start of the step, so the step can be captured as well
+(summarymixing_amd.streaming.CapturedSlotStep).
 """
 import math
 from dataclasses import dataclass
@@ -18,12 +23,13 @@ import torch
 from torch import nn
 
 from .... import functional as F
+from .... import ops
 from .... import sequence_parallel as SP
 from ....nnet.activations import Swish
 from ....utils.dynamic_chunk_training import DynChunkTrainConfig  # noqa: F401
 from ...models.VanillaNN import Linear
 from .Branchformer import BranchformerEncoder
-from .Conformer import ConformerEncoder
+from .Conformer import ConformerEncoder, _slot_commit
 
 
 @dataclass
@@ -231,6 +237,60 @@ class TransformerASR(nn.Module):
         return self.encoder._stream_chunk(x, ec, src.dtype)
 
 
+    def make_slot_context(self, dynchunktrain_config: DynChunkTrainConfig, slots: int):
+        """A blank slot-streaming context for `slots` independent streams (encode_slots).  Refuses what make_streaming_context
+        refuses."""
+        if not isinstance(self.encoder, ConformerEncoder):
+            raise NotImplementedError("streaming inference runs the Conformer encoder only (the Branchformer refuses Dynamic "
+                                      "Chunk Training)")
+        enc = self.encoder.make_slot_context(dynchunktrain_config, slots)
+        return TransformerASRStreamingContext(dynchunktrain_config=dynchunktrain_config, encoder_context=enc)
+
+    def encode_slots(self, src, valid, start, context: TransformerASRStreamingContext):
+        """Encode one step (B, C, F) (or (B, C, ch1, ch2)) of B independent streams, one per slot of the context.  valid (B host
+        ints, 0 .. C): slot b's frames in this step - C a full chunk, 1 .. C-1 its stream's last chunk, 0 the slot sits out and its
+        state stays as it was.  start (B host bools): slot b begins a new stream at this step.  For every stream, the rows
+        [:valid[b]] of its steps concatenate to encode_streaming of that stream alone; rows at and beyond valid[b] are unspecified,
+        and the input rows there are never read (they may hold anything).  ValueError, before any launch: feeding a slot with no
+        open stream without start, valid outside 0 .. C, a stream running past max_length, another B, dtype or device."""
+        if src.dim() == 4:
+            bz, t, ch1, ch2 = src.shape
+            src = src.reshape(bz, t, ch1 * ch2)
+        ec, args = self._slot_begin(src, valid, start, context)
+        self.encoder._slot_stage(ec, args[0], args[1])
+        with torch.no_grad():
+            out = self._slot_chunk(src, ec)
+        _slot_commit(ec, *args)
+        return out
+
+    def _slot_begin(self, src, valid, start, context):
+        """Validate the step (host only) and allocate the state on the first one; -> (encoder context, args for _slot_commit)."""
+        ec = context.encoder_context
+        args = self.encoder._slot_begin(ec, tuple(src.shape), src.dtype, src.device, valid, start)
+        if self.positional_encoding_type == "fixed_abs_sine":
+            for b, (v, f) in enumerate(zip(args[0], args[2])):
+                if f + v > self.positional_encoding.max_len:
+                    raise ValueError(f"slot streaming: slot {b} reaches frame {f + v}, beyond max_length "
+                                     f"{self.positional_encoding.max_len}")
+        if ec.pe is None:
+            B, C, d = ec.slots, ec.dynchunktrain_config.chunk_size, self.custom_src_module.layers[0].w.weight.shape[0]
+            if self.positional_encoding_type == "fixed_abs_sine":
+                ec.pe_table = self.positional_encoding.pe[0]
+                ec.pe = torch.zeros((B * C, d), dtype=ec.pe_table.dtype, device=src.device)
+            else:
+                ec.pe = torch.zeros((B * C, d), device=src.device)
+        return ec, args
+
+    def _slot_chunk(self, src, ec):
+        """The launches of one slot step: counters reset / positional rows (smx_slot_begin), input projection + those rows (the
+        (B*C, d) block indexed row by row), the encoder, the counter advance."""
+        B, C, _ = src.shape
+        lin = self.custom_src_module.layers[0].w
+        ops.slot_begin(ec.counters, ec.start, ec.pe_table, ec.pe if ec.pe_table is not None else None, B, C, ec.pe.shape[1])
+        x = F.input_proj_pe(src.reshape(1, B * C, -1), lin.weight, lin.bias, ec.pe, B * C, 0.0)
+        return self.encoder._slot_layers(x.view(B, C, -1), ec, src.dtype)
+
+
 class EncoderWrapper(nn.Module):
     """forward() = transformer.encode() (TransformerASR.py:715-729)."""
 
@@ -249,3 +309,11 @@ class EncoderWrapper(nn.Module):
     def make_streaming_context(self, *args, **kwargs):
         """transformer.make_streaming_context (reference :738-741)."""
         return self.transformer.make_streaming_context(*args, **kwargs)
+
+    def forward_slots(self, x, valid, start, context):
+        """transformer.encode_slots."""
+        return self.transformer.encode_slots(x, valid, start, context)
+
+    def make_slot_context(self, *args, **kwargs):
+        """transformer.make_slot_context."""
+        return self.transformer.make_slot_context(*args, **kwargs)

@@ -673,6 +673,48 @@ def stream_advance(counter, table, pe, C):
             "smx_stream_advance")
 
 
+def slot_summary(s, out, B, C, left, ring, counters, valid):
+    """Per-slot streaming DynChunk summary (smx_slot_summary): s / out (B*C, D), slot b's rows b*C .. b*C + valid[b] - 1 = the window
+    mean of its chunk counters[b]; `valid` (B,) int32 and `counters` (B,) int64 on the device.  Slots with valid 0 are untouched."""
+    D = s.shape[1]
+    ps, lds = _mat(s)
+    po, ldo = _mat(out)
+    tok = _pb(f"slot_summary ({B},{C},{D})", 2 * B * C * D * _es(s))
+    L.check(L.lib().smx_slot_summary(dt(s), ps, lds, po, ldo, _p(ring), _p(counters), _p(valid), B, C, D, -1 if left is None else left,
+                                     _stream()), "smx_slot_summary")
+    _pe(tok)
+    return out
+
+
+def dwconv_slots(p, w, bias, state, valid, counters, B, C, D, k):
+    """GLU + depthwise conv of one slot step (smx_dwconv1d_glu_slots): dwconv_stream per slot with C_cur = valid[b]; the state reads
+    as zero where counters[b] == 0 and is left untouched where valid[b] == 0."""
+    assert state.dtype == p.dtype and state.is_contiguous() and state.shape == (B, (k - 1) // 2, 2 * D)
+    y = torch.empty((B * C, D), dtype=p.dtype, device=p.device)
+    pp, ldp = _mat(p)
+    tok = _pb(f"dwconv_slots ({B},{C},{D}) k={k}", 3 * B * C * D * _es(p))
+    L.check(L.lib().smx_dwconv1d_glu_slots(dt(p), pp, ldp, _p(w), _p(bias), _p(state), _p(y), D, _p(valid), _p(counters), B, C, D, k,
+                                           _stream()), "smx_dwconv1d_glu_slots")
+    _pe(tok)
+    return y
+
+
+def slot_begin(counters, start, table, pe, B, C, D):
+    """First launch of a slot step (smx_slot_begin): counters[b] = 0 where start[b], then pe (B*C, D) = each slot's rows of the
+    positional table (table / pe None: counters only)."""
+    if pe is None:
+        pt, ldt, rows, pp, ldpe, code = None, D, 0, None, D, L.F32
+    else:
+        assert table.dtype == pe.dtype
+        (pt, ldt), (pp, ldpe), rows, code = _mat(table), _mat(pe), table.shape[0], dt(pe)
+    L.check(L.lib().smx_slot_begin(code, _p(counters), _p(start), pt, ldt, rows, pp, ldpe, B, C, D, _stream()), "smx_slot_begin")
+
+
+def slot_advance(counters, valid, B, C):
+    """Last launch of a slot step (smx_slot_advance): counters[b] += (valid[b] == C)."""
+    L.check(L.lib().smx_slot_advance(_p(counters), _p(valid), B, C, _stream()), "smx_slot_advance")
+
+
 def dwconv_bwd(dy, p, w, bias, dw, dbias, B, T, D, k, glu, pad_mode=L.PAD_ZERO, chunk=0, gate=None, dgate_out=None, ws=None):
     """ws (caller-owned, smx_dwconv1d_glu_bwd_workspace bytes): the tap / bias partial rows stay in it for a deferred
     reduce_jobs and dw / dbias are not touched; then returns (dp, dgate, deferred) - deferred False means the shape is outside
