@@ -2,6 +2,7 @@
 """bench.py — encoder frames/s of the LibriSpeech Conformer-SummaryMixing training step on MI355X.
 
     python bench.py --gpus 1 --steps 10 --warmup 3                      # default: config C2b, bf16 training step
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full               # + roofline, CPU baseline, extra points
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" = one pass of the hot path over one synthetic padded utterance batch per GPU: encoder forward
@@ -17,7 +18,9 @@ backward passes accumulate, the reference's fit_batch) or fused (trainer.fuse_mi
 --dump-outputs DIR: after the timed steps, what the last one computed (encoder output; training: also the updated weights and
 the gradients) as DIR/<name>.npy - the inputs are seeded, so two builds of the project compare output for output.
 
-Prints ONE JSON line (rank 0) with the driver contract fields plus
+Prints ONE JSON line (rank 0) with the driver contract fields.  A plain run does only what they need: set up, warm up, time the
+steps, --dump-outputs, print.  --full adds the measurements that take runs of their own (each can be left out again with
+--no-roofline / --no-cpu-baseline / --no-extra-points):
   "roofline":     roofline of the DOMINANT KERNEL of the step: the kernel symbol (template instantiation, as rocprofv3 --stats
                   names it; GEMMs: asked of the library, smx_gemm_plan_query) with the largest share of the in-step kernel time,
                   averaged over all its launches inside one instrumented step: algorithmic bytes / HIP-event time on the stream
@@ -31,7 +34,9 @@ Prints ONE JSON line (rank 0) with the driver contract fields plus
   "roofline_isolated": the FFN up-projection GEMM and the dominant wgrad shape timed back to back in isolation,
   "roofline_pool": HBM roofline of the masked-mean pool kernel at the long-utterance point (config 5),
   "cpu_baseline": the oracle (PyTorch-CPU restatement of the reference graph) timed on this node's host cores
-                  on a bounded sample of the same workload.
+                  on a bounded sample of the same workload,
+  "extra_points": (the default line only) the other batches SURVEY 8(d) defines and the bf16 residual stream, each a short
+                  child run of this script.
 """
 import argparse
 import json
@@ -478,14 +483,17 @@ def main():
     ap.add_argument("--accum", default="sequential", choices=["sequential", "fused"],
                     help="sequential: G forward+backward passes accumulate, one update (the reference's fit_batch); fused: the G "
                          "micro-batches run as ONE batch (trainer.fuse_microbatches: same gradients, sized for 288 GB)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the result line's own fields, also measure the roofline objects, the CPU baseline and (default line) "
+                         "the extra_points; a plain run only sets up, warms up, times the steps and writes --dump-outputs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip cpu_baseline")
     ap.add_argument("--no-extra-points", action="store_true",
-                    help="skip the extra_points of the default line (SURVEY 8d batches: C2b B=64 x 500, C2a B=10 x 375, and the bf16 "
-                         "residual stream), each a short child run of this script")
-    ap.add_argument("--no-roofline", action="store_true")
+                    help="(--full) skip the extra_points of the default line (SURVEY 8d batches: C2b B=64 x 500, C2a B=10 x 375, and "
+                         "the bf16 residual stream), each a short child run of this script")
+    ap.add_argument("--no-roofline", action="store_true", help="(--full) skip the roofline objects")
     ap.add_argument("--roofline-step-only", action="store_true",
-                    help="(the extra_points child runs) only roofline_step - the step's algorithmic bytes / flops over the timed step - "
-                         "instead of the per-kernel roofline objects")
+                    help="(--full; the extra_points child runs) only roofline_step - the step's algorithmic bytes / flops over the timed "
+                         "step - instead of the per-kernel roofline objects")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32; rank 0): the encoder "
                          "output and, when training, the updated weights and the gradients - at most 60 MiB in all, larger arrays as a "
@@ -765,22 +773,23 @@ def main():
             out["comm"]["rccl_version"] = ".".join(str(v) for v in torch.cuda.nccl.version()) if hasattr(torch.cuda, "nccl") else None
             out["comm"]["topology"] = gpu_topology()
     if rank == 0:
-        if args.roofline_step_only and train and world == 1 and not force_dist:
-            out["roofline_step"] = roofline_step_kernels(step, dtype, dt / args.steps * 1e3)[4]
-        elif not args.no_roofline:
-            if train and world == 1 and not force_dist:
-                (out["roofline"], out["roofline_kernels"], out["roofline_symbols"], out["roofline_family"],
-                 out["roofline_step"]) = roofline_step_kernels(step, dtype, dt / args.steps * 1e3)
-                out["roofline_isolated"] = [roofline_wgrad(cfg, dtype), roofline_gemm(cfg, dtype)]
-            else:
-                out["roofline"] = roofline_gemm(cfg, dtype)
-            out["roofline_pool"] = roofline_pool(dtype)
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline(cfg, train)
-        default_line = (args.config == "c2b" and train and world == 1 and not force_dist and args.batch is None
-                        and args.frames is None and args.dtype == "bf16" and not args.dynchunk)
-        if default_line and not args.no_extra_points:
-            out["extra_points"] = extra_points()
+        if args.full:     # measurements of their own, after --dump-outputs (the instrumented steps move the weights on)
+            if args.roofline_step_only and train and world == 1 and not force_dist:
+                out["roofline_step"] = roofline_step_kernels(step, dtype, dt / args.steps * 1e3)[4]
+            elif not args.no_roofline:
+                if train and world == 1 and not force_dist:
+                    (out["roofline"], out["roofline_kernels"], out["roofline_symbols"], out["roofline_family"],
+                     out["roofline_step"]) = roofline_step_kernels(step, dtype, dt / args.steps * 1e3)
+                    out["roofline_isolated"] = [roofline_wgrad(cfg, dtype), roofline_gemm(cfg, dtype)]
+                else:
+                    out["roofline"] = roofline_gemm(cfg, dtype)
+                out["roofline_pool"] = roofline_pool(dtype)
+            if not args.no_cpu_baseline and world == 1:
+                out["cpu_baseline"] = cpu_baseline(cfg, train)
+            default_line = (args.config == "c2b" and train and world == 1 and not force_dist and args.batch is None
+                            and args.frames is None and args.dtype == "bf16" and not args.dynchunk)
+            if default_line and not args.no_extra_points:
+                out["extra_points"] = extra_points()
         print(json.dumps(out), flush=True)
     if world > 1 or force_dist:
         torch.distributed.barrier()
@@ -823,8 +832,8 @@ def extra_points():
             ("C2b ONE utterance B=1 x T=500 (hipGraph replay of the whole step)", ["--config", "c2b", "--batch", "1", "--steps", "30"], {}),
             ("C2b B=128 x T=500 on the bf16 residual stream (SMX_RESIDUAL=bf16, rounds 1-2)", ["--config", "c2b"], {"SMX_RESIDUAL": "bf16"}))
     for label, extra, env in runs:
-        cmd = [sys.executable, os.path.abspath(__file__), "--steps", "10", "--warmup", "4", "--no-cpu-baseline", "--roofline-step-only",
-               "--no-extra-points"] + extra
+        cmd = [sys.executable, os.path.abspath(__file__), "--steps", "10", "--warmup", "4", "--full", "--no-cpu-baseline",
+               "--roofline-step-only", "--no-extra-points"] + extra
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=dict(os.environ, **env))
             d = json.loads(r.stdout.strip().splitlines()[-1])
@@ -894,9 +903,9 @@ def main_stack(args, cfg, dtype, dev, rank, world):
                                           ("bf16" if dtype == torch.bfloat16 else "float32 model"))},
            "model_tflops": value * FLOPS_PER_FRAME_FWD["c5"] / 1e12}
     if rank == 0:
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             out["roofline"] = roofline_pool(dtype)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(cfg, False)
         print(json.dumps(out), flush=True)
     if world > 1:

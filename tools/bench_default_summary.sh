@@ -1,8 +1,8 @@
 #!/usr/bin/env bash
-# The driver's default bench line + a short summary (value, roofline of the dominant kernel, the extra points with their roofline_step).
+# `bench.py --full` on the default config + a short summary (value, roofline of the dominant kernel, the extra points with their roofline_step).
 cd "$(dirname "$0")/.." || exit 1
 O=gpurun_out/r06; mkdir -p $O
-SECONDS=0; python bench.py > $O/bench_default.json 2> $O/bench_default.err
+SECONDS=0; python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 echo "wall ${SECONDS} s"
 python - <<'PY'
 import json

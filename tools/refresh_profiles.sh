@@ -6,14 +6,14 @@ R="${1:-r06}"; TAG="${2:-vX}"
 ROOT="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 OUT="$ROOT/gpurun_out/refresh"; mkdir -p "$OUT"
 cd "$ROOT"
-python bench.py 2>/dev/null | tail -1 > "$OUT/${R}_bench_default.json"
-python bench.py --batch 64 --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT/${R}_bench_b64.json"
+python bench.py --full 2>/dev/null | tail -1 > "$OUT/${R}_bench_default.json"
+python bench.py --batch 64 --full --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT/${R}_bench_b64.json"
 python bench.py --batch 32 --no-cpu-baseline --no-roofline 2>/dev/null | tail -1 > "$OUT/${R}_bench_b32.json"
-python bench.py --config c2a --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT/${R}_bench_c2a.json"
-python bench.py --config c2a --batch 10 --frames 375 --steps 20 --warmup 5 2>/dev/null | tail -1 > "$OUT/${R}_bench_c2a_recipe_batch.json"
-python bench.py --mode forward --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT/${R}_bench_fwd.json"
-python bench.py --config c4 --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT/${R}_bench_c4.json"
-python bench.py --config c5 --steps 5 --warmup 2 2>/dev/null | tail -1 > "$OUT/${R}_bench_c5.json"
+python bench.py --config c2a --full --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT/${R}_bench_c2a.json"
+python bench.py --config c2a --batch 10 --frames 375 --steps 20 --warmup 5 --full 2>/dev/null | tail -1 > "$OUT/${R}_bench_c2a_recipe_batch.json"
+python bench.py --mode forward --full --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT/${R}_bench_fwd.json"
+python bench.py --config c4 --full --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT/${R}_bench_c4.json"
+python bench.py --config c5 --steps 5 --warmup 2 --full 2>/dev/null | tail -1 > "$OUT/${R}_bench_c5.json"
 python bench.py --dynchunk 8,2 --no-cpu-baseline --no-roofline 2>/dev/null | tail -1 > "$OUT/${R}_bench_dynchunk_8_2.json"
 python bench.py --dynchunk 16 --no-cpu-baseline --no-roofline 2>/dev/null | tail -1 > "$OUT/${R}_bench_dynchunk_16.json"
 SMX_RESIDUAL=bf16 python bench.py --no-cpu-baseline --no-roofline --no-extra-points 2>/dev/null | tail -1 > "$OUT/${R}_bench_bf16_stream.json"

@@ -7,7 +7,7 @@ for spec in "NT 2048 512 plain" "NT 512 2048" "NT 512 1024" "NT 512 512 plain" "
   set -- $spec
   N=3750 SMX_LIB=summarymixing_amd/libsmx_diag.so python tools/gemm_stamps.py "$@" >> $O/stamps_3750.txt 2>&1
 done
-python bench.py --config c2a --batch 10 --frames 375 --steps 30 --warmup 5 --no-cpu-baseline --no-extra-points > $O/bench_recipe.json 2>$O/bench_recipe.err
-python bench.py --config c2b --batch 64 --frames 500 --steps 20 --warmup 5 --no-cpu-baseline --no-extra-points > $O/bench_b64.json 2>$O/bench_b64.err
-python bench.py --config c2b --batch 1 --frames 500 --steps 30 --warmup 5 --no-cpu-baseline --no-extra-points > $O/bench_b1.json 2>$O/bench_b1.err
+python bench.py --config c2a --batch 10 --frames 375 --steps 30 --warmup 5 --full --no-cpu-baseline --no-extra-points > $O/bench_recipe.json 2>$O/bench_recipe.err
+python bench.py --config c2b --batch 64 --frames 500 --steps 20 --warmup 5 --full --no-cpu-baseline --no-extra-points > $O/bench_b64.json 2>$O/bench_b64.err
+python bench.py --config c2b --batch 1 --frames 500 --steps 30 --warmup 5 --full --no-cpu-baseline --no-extra-points > $O/bench_b1.json 2>$O/bench_b1.err
 tail -n 3 $O/*.json
