@@ -538,6 +538,40 @@ int smx_ctc_loss_bwd(int dtype, const void* log_probs, int64_t ldlp, const int32
                      const int32_t* tgt_len, int B, int T, int V, int Smax, int blank, const float* nll, const float* gscale,
                      void* grad, int64_t ldg, void* workspace, void* stream);
 
+/* ---- Transducer head (recipe keys `Tjoint`, `transducer_lin`, `transducer_cost`: Transducer_joint(joint="sum"), a Linear to the
+ * vocabulary and speechbrain.nnet.losses.transducer_loss).  Lattice rows are (b, t, u), u fastest: row = (b T + t) U1 + u, U1 = U + 1;
+ * targets int32 (B, U) padded; in_len / tgt_len int32 (B) absolute lengths, clamped to [1, T] / [0, U].  No host synchronisation. ----
+ * joint:      H[b,t,u,:] = act(enc[b,t,:] + dec[b,u,:]); enc (B, T, J), dec (B, U1, J), H (B, T, U1, J), contiguous, J %% 4 == 0.
+ *             bwd: d_enc = sum_u dH act'(.), d_dec = sum_t dH act'(.) (fixed order: t-block partials in `workspace`).
+ * row_stats:  per row of the logits (B T U1 rows of V): lse, lpb = z[blank] - lse, lpy = z[y] - lse (y = targets[b,u], 0 for u = U).
+ * loss_fwd:   nll[b] = -log P(y_b | x_b) (fp32); the recursion runs in fp64: alpha = B T U1 + B doubles (the forward variables,
+ *             then -log P in fp64), kept for the backward.  U1 <= 2048.
+ * loss_bwd:   gb / gy (B T U1 floats) = gscale[b] * d nll / d lpb, d nll / d lpy; exactly 0 outside t < Tb, u <= Ub.
+ * logit_grad: dz[n,v] = [v = blank] gb + [v = y] gy - softmax(z)[v] (gb + gy).
+ * fused GEMM (smx_transducer_fused_ok: J %% 64 == 0, V %% 4 == 0): z = H W^T + bias (W (V, J) in H's dtype, bias fp32 or null) is
+ *   never stored.  gemm_stats: lse / lpb / lpy from per-(row, 128-column tile) partials (smx_transducer_stats_workspace bytes);
+ *   gemm_grad: dz (nrows, V; leading dimension lddz %% 4 == 0) of lattice rows [row0, row0 + nrows), recomputed tile by tile,
+ *   stored once in H's dtype (columns >= V untouched). */
+int smx_transducer_joint_fwd(int dtype, const void* enc, const void* dec, void* H, int B, int T, int U1, int J, int act, void* stream);
+size_t smx_transducer_joint_bwd_workspace(int B, int T, int U1, int J);
+int smx_transducer_joint_bwd(int dtype, const void* dH, const void* enc, const void* dec, void* d_enc, void* d_dec, int B, int T, int U1,
+                             int J, int act, void* workspace, void* stream);
+int smx_transducer_row_stats(int dtype, const void* logits, int64_t ld, const int32_t* targets, int B, int T, int U1, int V, int blank,
+                             float* lse, float* lpb, float* lpy, void* stream);
+int smx_transducer_loss_fwd(const float* lpb, const float* lpy, const int32_t* in_len, const int32_t* tgt_len, int B, int T, int U1,
+                            double* alpha, float* nll, void* stream);
+int smx_transducer_loss_bwd(const float* lpb, const float* lpy, const double* alpha, const float* gscale,
+                            const int32_t* in_len, const int32_t* tgt_len, int B, int T, int U1, float* gb, float* gy, void* stream);
+int smx_transducer_logit_grad(int dtype, const void* logits, int64_t ld, const int32_t* targets, const float* lse, const float* gb,
+                              const float* gy, int B, int T, int U1, int V, int blank, void* dz, int64_t lddz, void* stream);
+int smx_transducer_fused_ok(int dtype, int J, int V);
+size_t smx_transducer_stats_workspace(int rows, int V);
+int smx_transducer_gemm_stats(int dtype, const void* H, const void* W, const float* bias, const int32_t* targets, int B, int T, int U1,
+                              int J, int V, int blank, float* lse, float* lpb, float* lpy, void* workspace, void* stream);
+int smx_transducer_gemm_grad(int dtype, const void* H, const void* W, const float* bias, const int32_t* targets, const float* lse,
+                             const float* gb, const float* gy, int B, int T, int U1, int J, int V, int blank, int row0, int nrows,
+                             void* dz, int64_t lddz, void* stream);
+
 /* ---- Split-K over WORKGROUPS for the long reductions of a small batch (round 6; the recipe's 10 x 375 frames) -------------------
  * smx_gemm_panel_slabs: slab[s] (N x M, float32) = A[:, s K : (s + 1) K] . W_s^T for s < nslice on the panel-resident kernel
  *   (A (N, nslice K) bf16; Wpacked = nslice consecutive smx_weight_pack images, image s = the weight's K-slice s, packed WITHOUT a bias;

@@ -181,6 +181,18 @@ SIGNATURES = {
     "smx_ctc_loss_fwd": (c_i, [c_i, c_vp, c_i64, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_vp, c_vp, c_vp]),
     "smx_ctc_loss_bwd": (c_i, [c_i, c_vp, c_i64, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_vp, c_vp, c_vp, c_i64, c_vp,
                                c_vp]),
+    "smx_transducer_joint_fwd": (c_i, [c_i, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_vp]),
+    "smx_transducer_joint_bwd_workspace": (c_sz, [c_i, c_i, c_i, c_i]),
+    "smx_transducer_joint_bwd": (c_i, [c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_vp, c_vp]),
+    "smx_transducer_row_stats": (c_i, [c_i, c_vp, c_i64, c_vp, c_i, c_i, c_i, c_i, c_i, c_vp, c_vp, c_vp, c_vp]),
+    "smx_transducer_loss_fwd": (c_i, [c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_vp, c_vp, c_vp]),
+    "smx_transducer_loss_bwd": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_vp, c_vp, c_vp]),
+    "smx_transducer_logit_grad": (c_i, [c_i, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_vp, c_i64, c_vp]),
+    "smx_transducer_fused_ok": (c_i, [c_i, c_i, c_i]),
+    "smx_transducer_stats_workspace": (c_sz, [c_i, c_i]),
+    "smx_transducer_gemm_stats": (c_i, [c_i, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "smx_transducer_gemm_grad": (c_i, [c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_vp,
+                                       c_i64, c_vp]),
     "smx_get_config": (c_i, [c_vp]),
     "smx_gemm_ln_tile_rows": (c_i, []),
     "smx_gemm_ln_tile_rows_for": (c_i, [c_i, c_i]),

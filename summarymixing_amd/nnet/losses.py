@@ -1,7 +1,8 @@
-"""CTC loss of the recipes' multitask head (recipe key ``ctc_cost``: speechbrain.nnet.losses.ctc_loss, which wraps
+"""Losses of the recipes' heads: the CTC loss of the multitask head (recipe key ``ctc_cost``: speechbrain.nnet.losses.ctc_loss, which wraps
 ``torch.nn.functional.ctc_loss(..., zero_infinity=True)``; SpeechBrain is not vendored in the reference tree, the call
-site is …/LibriSpeech/ASR/transducer/hparams/conformer_summarymixing_transducer.yaml:297-298).  The forward/backward
-variables and the gradient run in the HIP kernels of csrc/ctc.hip; no CPU fallback."""
+site is …/LibriSpeech/ASR/transducer/hparams/conformer_summarymixing_transducer.yaml:297-298) and the transducer (RNN-T)
+loss the recipe trains on (recipe key ``transducer_cost``: speechbrain.nnet.losses.transducer_loss).  The forward/backward
+variables and the gradients run in the HIP kernels of csrc/ctc.hip and csrc/transducer.hip; no CPU fallback."""
 import torch
 
 from .. import ops
@@ -46,3 +47,65 @@ def ctc_loss(log_probs, targets, input_lens, target_lens, blank_index, reduction
     if reduction == "none":
         return nll
     raise ValueError(f"unknown reduction {reduction!r}")
+
+
+class _RNNT(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, targets, in_len, tgt_len, blank):
+        B, T, U1, V = logits.shape
+        z2 = logits.reshape(-1, V)
+        if not z2.is_contiguous():
+            z2 = z2.contiguous()
+        lse, lpb, lpy = ops.transducer_row_stats(z2, targets, B, T, U1, blank)
+        nll, alpha = ops.transducer_loss_fwd(lpb, lpy, in_len, tgt_len, B, T, U1)
+        ctx.save_for_backward(z2, targets, in_len, tgt_len, lse, lpb, lpy, alpha)
+        ctx.meta = (B, T, U1, V, blank)
+        return nll
+
+    @staticmethod
+    def backward(ctx, gnll):
+        z2, targets, in_len, tgt_len, lse, lpb, lpy, alpha = ctx.saved_tensors
+        B, T, U1, V, blank = ctx.meta
+        gb, gy = ops.transducer_loss_bwd(lpb, lpy, alpha, gnll.float().contiguous(), in_len, tgt_len, B, T, U1)
+        dz = ops.transducer_logit_grad(z2, targets, lse, gb, gy, B, T, U1, blank)
+        return dz.view(B, T, U1, V), None, None, None, None
+
+
+TRANSDUCER_REDUCTIONS = ("mean", "sum", "none")
+
+
+def transducer_lengths(T, targets, input_lens, target_lens, device):
+    """SpeechBrain's relative lengths -> absolute int32 lengths on the device (round(rel * T), round(rel * U)); padded int32 targets."""
+    in_len = (input_lens.to(device) * T).round().to(torch.int32)
+    tgt_len = (target_lens.to(device) * targets.shape[1]).round().to(torch.int32)
+    return targets.to(device=device, dtype=torch.int32).contiguous(), in_len, tgt_len
+
+
+def reduce_transducer(nll, reduction):
+    if reduction == "mean":                          # torchaudio's rnnt_loss and SpeechBrain's own implementation: the batch mean
+        return nll.mean()
+    if reduction == "sum":
+        return nll.sum()
+    return nll
+
+
+def transducer_loss(logits, targets, input_lens, target_lens, blank_index, reduction="mean", use_torchaudio=True):
+    """speechbrain.nnet.losses.transducer_loss.  logits (B, T, U+1, V) raw joint-network scores (CUDA, fp32 or bf16; the
+    log-softmax over V happens inside, in fp32); targets (B, U) padded tokens; input_lens / target_lens RELATIVE lengths.
+    Per utterance -log P(y | x) on the RNN-T lattice, reduced by `reduction` ('mean' | 'sum' | 'none').  use_torchaudio is
+    accepted and ignored (both SpeechBrain back-ends compute the same function)."""
+    if reduction not in TRANSDUCER_REDUCTIONS:
+        raise ValueError(f"unknown reduction {reduction!r} (transducer_loss: 'mean', 'sum' or 'none')")
+    if not logits.is_cuda:
+        raise RuntimeError("summarymixing_amd.nnet.losses.transducer_loss runs on the GPU only (no CPU fallback)")
+    if logits.dim() != 4:
+        raise ValueError(f"transducer_loss: logits (B, T, U+1, V) expected, got {tuple(logits.shape)}")
+    B, T, U1, V = logits.shape
+    if targets.dim() != 2 or targets.shape[0] != B or targets.shape[1] != U1 - 1:
+        raise ValueError(f"transducer_loss: targets (B, U) = ({B}, {U1 - 1}) expected, got {tuple(targets.shape)}")
+    if not 0 <= int(blank_index) < V:
+        raise ValueError(f"transducer_loss: blank_index {blank_index} outside the vocabulary of {V}")
+    ops.dt(logits)
+    tg, in_len, tgt_len = transducer_lengths(T, targets, input_lens, target_lens, logits.device)
+    nll = _RNNT.apply(logits, tg, in_len, tgt_len, int(blank_index))
+    return reduce_transducer(nll, reduction)

@@ -874,6 +874,101 @@ def ctc_bwd(lp2, targets, in_len, tgt_len, B, T, blank, nll, gscale, ws):
     return g
 
 
+# ---- transducer head (csrc/transducer.hip).  Lattice rows (b, t, u), u fastest; every size below comes from tensor shapes and the
+# lengths stay on the device: no call here synchronises with the host.
+def transducer_joint_fwd(enc, dec, act):
+    """enc (B, T, J), dec (B, U1, J) contiguous, same dtype -> H (B, T, U1, J)."""
+    B, T, J = enc.shape
+    U1 = dec.shape[1]
+    H = torch.empty((B, T, U1, J), dtype=enc.dtype, device=enc.device)
+    L.check(L.lib().smx_transducer_joint_fwd(dt(enc), _p(enc), _p(dec), _p(H), B, T, U1, J, act, _stream()), "smx_transducer_joint_fwd")
+    return H
+
+
+def transducer_joint_bwd(dH, enc, dec, act, d_enc=None, d_dec=None):
+    """dH (B, T, U1, J) -> (d_enc (B, T, J), d_dec (B, U1, J)), written into d_enc / d_dec when given (contiguous views)."""
+    B, T, J = enc.shape
+    U1 = dec.shape[1]
+    d_enc = torch.empty_like(enc) if d_enc is None else d_enc
+    d_dec = torch.empty_like(dec) if d_dec is None else d_dec
+    ws = _workspace(L.lib().smx_transducer_joint_bwd_workspace(B, T, U1, J), enc.device, "transducer_joint")
+    L.check(L.lib().smx_transducer_joint_bwd(dt(enc), _p(dH), _p(enc), _p(dec), _p(d_enc), _p(d_dec), B, T, U1, J, act, _p(ws),
+                                             _stream()), "smx_transducer_joint_bwd")
+    return d_enc, d_dec
+
+
+def _row_f32(rows, device, n):
+    return [torch.empty((rows,), dtype=torch.float32, device=device) for _ in range(n)]
+
+
+def transducer_row_stats(z2, targets, B, T, U1, blank):
+    """z2 (B T U1, V) logits -> (lse, lp_blank, lp_y), fp32 per lattice row."""
+    V = z2.shape[1]
+    lse, lpb, lpy = _row_f32(z2.shape[0], z2.device, 3)
+    pz, ldz = _mat(z2)
+    L.check(L.lib().smx_transducer_row_stats(dt(z2), pz, ldz, _p(targets), B, T, U1, V, blank, _p(lse), _p(lpb), _p(lpy), _stream()),
+            "smx_transducer_row_stats")
+    return lse, lpb, lpy
+
+
+def transducer_loss_fwd(lpb, lpy, in_len, tgt_len, B, T, U1):
+    """-> (nll (B) fp32, alpha (B T U1 + B) fp64 kept for the backward: the forward variables, then -log P)."""
+    alpha = torch.empty((lpb.numel() + B,), dtype=torch.float64, device=lpb.device)
+    nll = torch.empty((B,), dtype=torch.float32, device=lpb.device)
+    L.check(L.lib().smx_transducer_loss_fwd(_p(lpb), _p(lpy), _p(in_len), _p(tgt_len), B, T, U1, _p(alpha), _p(nll), _stream()),
+            "smx_transducer_loss_fwd")
+    return nll, alpha
+
+
+def transducer_loss_bwd(lpb, lpy, alpha, gscale, in_len, tgt_len, B, T, U1):
+    """-> (g_blank, g_y) per lattice row, fp32, already scaled by gscale[b]."""
+    gb, gy = torch.empty_like(lpb), torch.empty_like(lpb)
+    L.check(L.lib().smx_transducer_loss_bwd(_p(lpb), _p(lpy), _p(alpha), _p(gscale), _p(in_len), _p(tgt_len), B, T, U1,
+                                            _p(gb), _p(gy), _stream()), "smx_transducer_loss_bwd")
+    return gb, gy
+
+
+def transducer_logit_grad(z2, targets, lse, gb, gy, B, T, U1, blank):
+    V = z2.shape[1]
+    dz = torch.empty((z2.shape[0], V), dtype=z2.dtype, device=z2.device)
+    pz, ldz = _mat(z2)
+    L.check(L.lib().smx_transducer_logit_grad(dt(z2), pz, ldz, _p(targets), _p(lse), _p(gb), _p(gy), B, T, U1, V, blank, _p(dz), V,
+                                              _stream()), "smx_transducer_logit_grad")
+    return dz
+
+
+def transducer_fused_ok(dtype, J, V):
+    return bool(L.lib().smx_transducer_fused_ok(_DT[dtype], J, V))
+
+
+def transducer_gemm_stats(H2, W, bias, targets, B, T, U1, blank):
+    """H2 (B T U1, J), W (V, J) same dtype, bias fp32 (V) or None -> (lse, lp_blank, lp_y); the logits are never stored."""
+    rows, J = H2.shape
+    V = W.shape[0]
+    lse, lpb, lpy = _row_f32(rows, H2.device, 3)
+    ws = torch.empty(L.lib().smx_transducer_stats_workspace(rows, V), dtype=torch.uint8, device=H2.device)
+    tok = _pb(f"transducer_gemm_stats {'bf16' if H2.dtype == torch.bfloat16 else 'f32'} ({rows}x{J})x({J}x{V})",
+              (rows * J + V * J) * _es(H2) + rows * 12, 2.0 * rows * J * V)
+    L.check(L.lib().smx_transducer_gemm_stats(dt(H2), _p(H2), _p(W), _p(bias), _p(targets), B, T, U1, J, V, blank, _p(lse), _p(lpb),
+                                              _p(lpy), _p(ws), _stream()), "smx_transducer_gemm_stats")
+    _pe(tok)
+    return lse, lpb, lpy
+
+
+def transducer_gemm_grad(H2, W, bias, targets, lse, gb, gy, B, T, U1, blank, row0, nrows, dz):
+    """dz (nrows, V) view (unit column stride, any 16-byte multiple leading dimension) = the logit gradient of lattice rows
+    [row0, row0 + nrows), the logits recomputed tile by tile."""
+    J = H2.shape[1]
+    V = W.shape[0]
+    pdz, lddz = _mat(dz)
+    tok = _pb(f"transducer_gemm_grad {'bf16' if H2.dtype == torch.bfloat16 else 'f32'} ({nrows}x{J})x({J}x{V})",
+              (nrows * J + V * J + nrows * V) * _es(H2) + nrows * 12, 2.0 * nrows * J * V)
+    L.check(L.lib().smx_transducer_gemm_grad(dt(H2), _p(H2), _p(W), _p(bias), _p(targets), _p(lse), _p(gb), _p(gy), B, T, U1, J, V,
+                                             blank, row0, nrows, pdz, lddz, _stream()), "smx_transducer_gemm_grad")
+    _pe(tok)
+    return dz
+
+
 _CSGU_DROP_FUSE = True   # (round 4: A/B knob SMX_CSGU_DROP_FUSE removed)     # (read once, like the library's own knobs)
 _STEP_COUNTER = None          # the training loop's device step counter (held HERE, in the Python host; libsmx has no such state)
 
