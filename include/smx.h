@@ -594,7 +594,11 @@ int smx_slab_epilogue(int dtype, const float* slabs, int nslab, int64_t slab_str
  *   shards exchange.  phase 2: window combine + carry[b][c - carry_c0] for carry_c0 <= c < carry_c0 + carry_n (carry_n == 0: one
  *   (B, D) row for every chunk), forward divided by the GLOBAL window length.
  * smx_expdecay_mean_sharded: frames [t_off, t_off + T) of T_glob.  phase 1: ends (2, B, D) <- the states leaving the shard; phase 2:
- *   ends = the states ENTERING it (folded by the caller from the gathered ones), out = the operator with global denominators. */
+ *   ends = the states ENTERING it (folded by the caller from the gathered ones), out = the operator with global denominators.
+ *   The `ends` contract, both phases: states at TRUE frames - ends[0] is f at the shard's last frame (phase 1) / at the frame before
+ *   its first (phase 2), ends[1] is g at the shard's first frame (phase 1) / at the frame after its last (phase 2).  The scan's zero
+ *   padding of the shard's last 16-row chunk is never visible to the caller: the library compensates it in both directions
+ *   (decay^-pad, pad < 16: finite in float32 for decay >= ~0.01), so the caller's fold is decay^T per shard for any T. */
 int smx_chunk_mean_sharded(int dtype, const void* X, int64_t ldx, void* out, int64_t ldo, int B, int T, int D, int chunk, int left,
                            int reverse, int c_off, int phase, const float* carry, int carry_c0, int carry_n, void* workspace, void* stream);
 int smx_expdecay_mean_sharded(int dtype, const void* S, int64_t lds, void* out, int64_t ldo, int B, int T, int D, float decay, int mode,

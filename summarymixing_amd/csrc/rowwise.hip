@@ -371,6 +371,12 @@ __global__ __launch_bounds__(256) void expdecay_carry_kernel(float* __restrict__
   const float gch = expf((float)ED_CH * logf(gamma));    // every chunk is ED_CH rows long (the tail is zero padded)
   // both directions advance in the same loop (two independent chains), 16 chunk values of each fetched ahead
   float cf = f_in ? f_in[idx] : 0.f, cg = g_in ? g_in[idx] : 0.f;
+  // The last chunk is zero padded to ED_CH rows.  g_in is g at the frame after the shard's LAST one, but it seeds the scan at the end of
+  // the padded chunk: the carry step (gch) and the descending scan of expdecay_apply_kernel then decay it through the pad rows as well.
+  // Scale it up by gamma^-pad first (the mirror of `ends` below; pad < 16, finite in float32 for gamma >= ~0.01).  pad == 0 and the
+  // unsharded call (g_in == nullptr) are untouched.
+  const int pad = NC * ED_CH - T_;
+  if (g_in && pad > 0) cg *= expf(-(float)pad * logf(gamma));
   for (int c0 = 0; c0 < NC; c0 += 16) {
     float f[16], g[16];
 #pragma unroll
@@ -391,8 +397,7 @@ __global__ __launch_bounds__(256) void expdecay_carry_kernel(float* __restrict__
     }
   }
   if (ends) {
-    // the last chunk is zero padded to ED_CH rows: its end value is gamma^pad times f at the shard's last frame
-    const int pad = NC * ED_CH - T_;
+    // the padded last chunk's end value is gamma^pad times f at the shard's last frame
     ends[idx] = cf * expf(-(float)pad * logf(gamma));
     ends[(long)B * D + idx] = cg;
   }

@@ -1,7 +1,8 @@
 """Sequence-parallel mode (summarymixing_amd/sequence_parallel.py): the time axis of one batch sharded
-over 2 ranks must reproduce the unsharded encoder - outputs, input gradients and (summed) parameter gradients.
+over 2 (or 3: a middle rank) ranks must reproduce the unsharded encoder - outputs, input gradients and (summed) parameter gradients.
+The arithmetic of the two sharded O(T) summaries alone, at many more geometries: tests/test_seqpar_kernels_gpu.py.
 
-The GPU box has ONE device, so the two ranks share cuda:0 and talk over gloo (host-staged); on a multi-GPU node the same
+The GPU box has ONE device, so the ranks share cuda:0 and talk over gloo (host-staged); on a multi-GPU node the same
 code runs one rank per GPU over RCCL.  Every rank first runs the unsharded encoder itself as the reference."""
 import os
 import subprocess
@@ -25,7 +26,7 @@ rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
 dist.init_process_group("gloo", rank=rank, world_size=world)
 torch.cuda.set_device(0)
 mode, drop_ok = os.environ["SMX_MODE"], True
-d, B, T = 64, 3, 96
+d, B, T = 64, 3, int(os.environ.get("SMX_T", "96"))
 torch.manual_seed(5)
 if os.environ.get("SMX_ENC") == "branchformer":
     from summarymixing_amd.lobes.models.transformer.Branchformer import BranchformerEncoder
@@ -45,7 +46,7 @@ with torch.no_grad():
 enc = enc.cuda()
 x = torch.randn(B, T, d).cuda()
 r = torch.randn(B, T, d).cuda()
-lens = torch.tensor([T, 70, 40])                    # utterance 2 ends inside shard 0: shard 1 holds only its padding
+lens = torch.tensor([T, T * 70 // 96, T * 40 // 96])     # (96: 70, 40) utterance 2 ends inside an earlier shard: the last shard holds only its padding
 pad = (torch.arange(T)[None] < lens[:, None]).cuda()
 if os.environ.get("SMX_NOMASK") == "1":
     pad = None
@@ -95,11 +96,12 @@ def _free_port():
         return s.getsockname()[1]
 
 
-def _run(mode, nomask=False, enc="conformer", dynchunk=""):
+def _run(mode, nomask=False, enc="conformer", dynchunk="", T=96, world=2):
+    """T frames over `world` ranks (all on the one GPU, over gloo); the lengths follow T (worker: lens)."""
     port = _free_port()
     procs = []
-    for rank in range(2):
-        env = dict(os.environ, RANK=str(rank), WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
+    for rank in range(world):
+        env = dict(os.environ, RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), SMX_T=str(T),
                    SMX_ROOT=ROOT, SMX_MODE=mode, SMX_NOMASK="1" if nomask else "0", SMX_ENC=enc, SMX_DYNCHUNK=dynchunk, HSA_ENABLE_IPC_MODE_LEGACY="0")
         procs.append(subprocess.Popen([sys.executable, "-c", WORKER], env=env, stdout=subprocess.PIPE,
                                       stderr=subprocess.STDOUT, text=True))
@@ -165,7 +167,7 @@ rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
 dist.init_process_group("gloo", rank=rank, world_size=world)
 torch.cuda.set_device(0)
 mode = os.environ["SMX_MODE"]
-d, B, T = 64, 3, 96
+d, B, T = 64, 3, int(os.environ.get("SMX_T", "96"))
 torch.manual_seed(5)
 if os.environ.get("SMX_ENC") == "branchformer":
     from summarymixing_amd.lobes.models.transformer.Branchformer import BranchformerEncoder
@@ -183,7 +185,7 @@ enc = enc.cuda().train()
 x = torch.randn(B, T, d).cuda()
 r = torch.randn(B, T, d).cuda()
 v = torch.randn(B, T, d).cuda()
-lens = torch.tensor([T, 70, 40])
+lens = torch.tensor([T, T * 70 // 96, T * 40 // 96])
 pad = (torch.arange(T)[None] < lens[:, None]).cuda()
 kw = {}
 if os.environ.get("SMX_DYNCHUNK"):
@@ -231,11 +233,11 @@ print(f"rank {rank} OK")
 '''
 
 
-def _run_drop(mode, enc="conformer", dynchunk=""):
+def _run_drop(mode, enc="conformer", dynchunk="", T=96, world=2):
     port = _free_port()
     procs = []
-    for rank in range(2):
-        env = dict(os.environ, RANK=str(rank), WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
+    for rank in range(world):
+        env = dict(os.environ, RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), SMX_T=str(T),
                    SMX_ROOT=ROOT, SMX_MODE=mode, SMX_ENC=enc, SMX_DYNCHUNK=dynchunk, HSA_ENABLE_IPC_MODE_LEGACY="0")
         procs.append(subprocess.Popen([sys.executable, "-c", DROP_WORKER], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
     outs = []
@@ -258,3 +260,26 @@ def test_sequence_parallel_trains_with_dropout(mode, enc, dynchunk):
     seed indexed by LOCAL rows; now each rank salts the seeds it draws).  Same seeds -> bit-identical outputs; train != eval; the
     backward reuses the forward's masks (directional derivative of the global loss against <dx, v>); the ranks' seeds differ."""
     _run_drop(mode, enc, dynchunk)
+
+
+# ---- beyond 48 frames x 2 ranks: shards whose length is not a multiple of the expdecay scan's 16-row chunk, and a middle rank ----
+@pytest.mark.parametrize("nomask", [False, True])
+def test_sequence_parallel_expdecay_padded_shard(nomask):
+    """SummaryMixing-expdecay over two shards of 40 frames: the shard's last 16-row scan chunk is zero padded by 8 rows, through
+    which the state entering from the right neighbour must NOT decay (rowwise.hip expdecay_carry_kernel)."""
+    _run("SummaryMixing-expdecay", nomask=nomask, T=80)
+
+
+@pytest.mark.parametrize("mode,enc,dynchunk", [("SummaryMixing-fast", "conformer", ""), ("SummaryMixing-expdecay", "conformer", ""),
+                                               ("SummaryMixing", "branchformer", ""), ("SummaryMixing-fast", "conformer", "8,2"),
+                                               ("SummaryMixing-fast", "conformer", "8,all")])
+def test_sequence_parallel_three_ranks(mode, enc, dynchunk):
+    """120 frames over THREE ranks (40 each): the middle rank's conv modules take two real halos and return two halo gradients (the
+    CSGU reflects at neither end), the expdecay states hop over it (f_in = ends[q] + decay^T f_in, shards padded by 8 rows), the
+    DynChunk summary with unlimited left context sums over several shards (5 chunks per rank; the conv's left halo is 16 frames)."""
+    _run(mode, enc=enc, dynchunk=dynchunk, T=120, world=3)
+
+
+def test_sequence_parallel_trains_with_dropout_three_ranks():
+    """The per-rank seed salt with three distinct ranks (40 frames each, SummaryMixing-expdecay: padded shards, a middle rank)."""
+    _run_drop("SummaryMixing-expdecay", T=120, world=3)
