@@ -367,6 +367,16 @@ __device__ __forceinline__ void tj_mainloop(const T* __restrict__ H, const T* __
     } else {
       const float* Wf = reinterpret_cast<const float*>(Ws);
       const float* Hf = reinterpret_cast<const float*>(Hs);
+      // fp32 operands: each stage is summed on its own and then added to the running sum.  One chain over the whole of J rounds
+      // J / 2 times in a row (x2 MFMAs); at J = 1088 that put lse / lp / dz 4 - 7 x further from fp64 than a blocked fp32 product
+      // (tests/test_transducer_kernels_gpu.py).  Two levels round BK / 2 + J / BK times.
+      f32x16 st[2][2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) st[i][j][e] = 0.f;
 #pragma unroll
       for (int kk = 0; kk < TT::BK / 2; ++kk) {
         float fa[2], fb[2];
@@ -377,8 +387,12 @@ __device__ __forceinline__ void tj_mainloop(const T* __restrict__ H, const T* __
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-          for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i], fb[j], acc[i][j], 0, 0, 0);
+          for (int j = 0; j < 2; ++j) st[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i], fb[j], st[i][j], 0, 0, 0);
       }
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] += st[i][j];
     }
   }
 }

@@ -24,9 +24,10 @@ def _modules(J, V, bias, act=torch.nn.GELU, seed=0):
     return Transducer_joint(joint="sum", nonlinearity=act), lin.cuda()
 
 
-def _lattice(B, T, U, V, seed, ub0=False):
+def _lattice(B, T, U, V, seed, ub0=False, blank=0):
     g = torch.Generator().manual_seed(seed)
-    targets = torch.randint(1, V, (B, U), generator=g)
+    targets = torch.randint(0, V - 1, (B, U), generator=g)
+    targets = targets + (targets >= blank)                # every column but the blank (blank 0: the same draws as randint(1, V))
     in_rel = 0.5 + 0.5 * torch.rand(B, generator=g)
     tg_rel = 0.3 + 0.7 * torch.rand(B, generator=g)
     in_rel[0], tg_rel[0] = 1.0, 1.0
@@ -60,23 +61,22 @@ def test_joint_forward_and_backward_match_fp64(act, dtype, tol):
 _SHAPES = [(3, 50, 9, 32), (4, 120, 40, 1000), (2, 40, 300, 64), (2, 1, 5, 16)]
 
 
-def _loss_case(B, T, U, V, dtype, reduction, seed):
+def _loss_case(B, T, U, V, dtype, reduction, seed, blank=0, w=None):
+    """w: per-utterance weights of a 'none' loss (a non-uniform upstream gradient); None: the plain sum."""
     from summarymixing_amd.nnet.losses import transducer_loss
-    targets, in_rel, tg_rel = _lattice(B, T, U, V, seed, ub0=B > 2)
+    targets, in_rel, tg_rel = _lattice(B, T, U, V, seed, ub0=B > 2, blank=blank)
     logits = (torch.randn(B, T, U + 1, V, generator=torch.Generator().manual_seed(seed + 1)) * 2.0).to(dtype)
     xr = logits.double().requires_grad_(True)
-    ref = rnnt_loss(xr, targets, in_rel, tg_rel, 0, reduction)
-    (ref.sum() if reduction == "none" else ref).backward()
+    ref = rnnt_loss(xr, targets, in_rel, tg_rel, blank, reduction)
+    ((ref if w is None else ref * w.double()).sum() if reduction == "none" else ref).backward()
     x = logits.cuda().requires_grad_(True)
-    loss = transducer_loss(x, targets.cuda(), in_rel.cuda(), tg_rel.cuda(), 0, reduction=reduction, use_torchaudio=False)
-    (loss.sum() if reduction == "none" else loss).backward()
+    loss = transducer_loss(x, targets.cuda(), in_rel.cuda(), tg_rel.cuda(), blank, reduction=reduction, use_torchaudio=False)
+    ((loss if w is None else loss * w.cuda()).sum() if reduction == "none" else loss).backward()
     return loss, ref, x, xr, in_rel, tg_rel
 
 
-@pytest.mark.parametrize("dtype,tl,tg", [(torch.float32, 1e-5, 1e-4), (torch.bfloat16, 2e-2, 3e-2)])
-@pytest.mark.parametrize("B,T,U,V", _SHAPES)
-def test_transducer_loss_matches_fp64(B, T, U, V, dtype, tl, tg):
-    loss, ref, x, xr, in_rel, tg_rel = _loss_case(B, T, U, V, dtype, "mean", 300 + T + U)
+def _loss_matches_fp64(B, T, U, V, dtype, tl, tg, blank):
+    loss, ref, x, xr, in_rel, tg_rel = _loss_case(B, T, U, V, dtype, "mean", 300 + T + U, blank=blank)
     assert loss.dtype == torch.float32 and loss.shape == ()
     assert abs(loss.item() - ref.item()) <= tl * max(1.0, abs(ref.item())), (loss.item(), ref.item())
     assert x.grad.dtype == dtype
@@ -86,11 +86,34 @@ def test_transducer_loss_matches_fp64(B, T, U, V, dtype, tl, tg):
         assert float(x.grad[b, tl_[b]:].abs().sum()) == 0.0 and float(x.grad[b, :, ul_[b] + 1:].abs().sum()) == 0.0
 
 
+@pytest.mark.parametrize("dtype,tl,tg", [(torch.float32, 1e-5, 1e-4), (torch.bfloat16, 2e-2, 3e-2)])
+@pytest.mark.parametrize("B,T,U,V", _SHAPES)
+def test_transducer_loss_matches_fp64(B, T, U, V, dtype, tl, tg):
+    _loss_matches_fp64(B, T, U, V, dtype, tl, tg, 0)
+
+
+@pytest.mark.parametrize("dtype,tl,tg", [(torch.float32, 1e-5, 1e-4), (torch.bfloat16, 2e-2, 3e-2)])
+@pytest.mark.parametrize("B,T,U,V", _SHAPES)
+def test_transducer_loss_matches_fp64_blank_in_the_last_column(B, T, U, V, dtype, tl, tg):
+    _loss_matches_fp64(B, T, U, V, dtype, tl, tg, V - 1)
+
+
 @pytest.mark.parametrize("reduction", ["sum", "none"])
 def test_transducer_loss_reductions(reduction):
     loss, ref, x, xr, _, _ = _loss_case(3, 50, 9, 32, torch.float32, reduction, 11)
     assert loss.shape == ref.shape
     assert rel_err(loss, ref) <= 1e-5 and rel_err(x.grad, xr.grad) <= 1e-4
+
+
+_W = torch.tensor([0.25, -1.5, 3.0])                     # a non-uniform upstream gradient: gscale[b] of the wrong utterance shows
+
+
+@pytest.mark.parametrize("blank", [0, 31])
+def test_transducer_loss_non_uniform_upstream_gradient(blank):
+    loss, ref, x, xr, _, _ = _loss_case(3, 50, 9, 32, torch.float32, "none", 11, blank=blank, w=_W)
+    assert rel_err(loss, ref) <= 1e-5 and rel_err(x.grad, xr.grad) <= 1e-4
+    for b in range(3):                                    # per utterance: the smallest weight is not hidden behind the largest
+        assert rel_err(x.grad[b], xr.grad[b]) <= 1e-4, b
 
 
 def _streams(B, T, U, J, dtype, seed):
@@ -100,28 +123,32 @@ def _streams(B, T, U, J, dtype, seed):
     return enc, dec
 
 
-def _dropin(tj, lin, enc, dec, targets, in_rel, tg_rel, reduction="mean"):
+def _backward(loss, w):
+    (loss if w is None else (loss * w.to(loss.device, loss.dtype)).sum()).backward()
+
+
+def _dropin(tj, lin, enc, dec, targets, in_rel, tg_rel, reduction="mean", blank=0, w=None):
     from summarymixing_amd.nnet.losses import transducer_loss
     e = enc.cuda().requires_grad_(True)
     d = dec.cuda().requires_grad_(True)
     lin.zero_grad(set_to_none=True)
-    loss = transducer_loss(lin(tj(e.unsqueeze(2), d.unsqueeze(1))), targets.cuda(), in_rel.cuda(), tg_rel.cuda(), 0, reduction)
-    loss.backward()
+    loss = transducer_loss(lin(tj(e.unsqueeze(2), d.unsqueeze(1))), targets.cuda(), in_rel.cuda(), tg_rel.cuda(), blank, reduction)
+    _backward(loss, w)
     return loss.detach(), e.grad, d.grad, lin.w.weight.grad.clone(), (lin.w.bias.grad.clone() if lin.w.bias is not None else None)
 
 
-def _fused(tj, lin, enc, dec, targets, in_rel, tg_rel, reduction="mean", four_d=False):
+def _fused(tj, lin, enc, dec, targets, in_rel, tg_rel, reduction="mean", four_d=False, blank=0, w=None):
     from summarymixing_amd.nnet.transducer import transducer_joint_loss
     e = enc.cuda().requires_grad_(True)
     d = dec.cuda().requires_grad_(True)
     lin.zero_grad(set_to_none=True)
     loss = transducer_joint_loss(e.unsqueeze(2) if four_d else e, d.unsqueeze(1) if four_d else d, tj, lin, targets.cuda(),
-                                 in_rel.cuda(), tg_rel.cuda(), 0, reduction)
-    loss.backward()
+                                 in_rel.cuda(), tg_rel.cuda(), blank, reduction)
+    _backward(loss, w)
     return loss.detach(), e.grad, d.grad, lin.w.weight.grad.clone(), (lin.w.bias.grad.clone() if lin.w.bias is not None else None)
 
 
-def _ref_chain(tj, lin, enc, dec, targets, in_rel, tg_rel, reduction="mean"):
+def _ref_chain(tj, lin, enc, dec, targets, in_rel, tg_rel, reduction="mean", blank=0, w=None):
     e = enc.double().requires_grad_(True)
     d = dec.double().requires_grad_(True)
     W = lin.w.weight.detach().to(enc.dtype).double().cpu().requires_grad_(True)
@@ -129,28 +156,81 @@ def _ref_chain(tj, lin, enc, dec, targets, in_rel, tg_rel, reduction="mean"):
     z = joint_ref(e, d, type(tj.nonlinearity)()) @ W.t()
     if b is not None:
         z = z + b
-    loss = rnnt_loss(z, targets, in_rel, tg_rel, 0, reduction)
-    loss.backward()
+    loss = rnnt_loss(z, targets, in_rel, tg_rel, blank, reduction)
+    _backward(loss, w)
     return loss.detach(), e.grad, d.grad, W.grad, (b.grad if b is not None else None)
 
 
-@pytest.mark.parametrize("bias", [False, True])
-@pytest.mark.parametrize("act", ACTS, ids=lambda a: a.__name__)
-def test_fused_path_equals_dropin_chain_fp32(bias, act):
-    B, T, U, J, V = 3, 20, 6, 128, 36                    # 420 rows, V not a multiple of the 128-column tile
+def _fused_equals_dropin_fp32(bias, act, blank, J=128, V=36, reduction="mean", w=None):
+    B, T, U = 3, 20, 6                                   # 420 rows
     tj, lin = _modules(J, V, bias, act)
     enc, dec = _streams(B, T, U, J, torch.float32, 5)
-    targets, in_rel, tg_rel = _lattice(B, T, U, V, 6, ub0=True)
-    a = _dropin(tj, lin, enc, dec, targets, in_rel, tg_rel)
-    f = _fused(tj, lin, enc, dec, targets, in_rel, tg_rel, four_d=True)
-    r = _ref_chain(tj, lin, enc, dec, targets, in_rel, tg_rel)
-    assert abs(f[0].item() - a[0].item()) <= 1e-5 * abs(a[0].item())
+    targets, in_rel, tg_rel = _lattice(B, T, U, V, 6, ub0=True, blank=blank)
+    a = _dropin(tj, lin, enc, dec, targets, in_rel, tg_rel, reduction, blank=blank, w=w)
+    f = _fused(tj, lin, enc, dec, targets, in_rel, tg_rel, reduction, four_d=True, blank=blank, w=w)
+    r = _ref_chain(tj, lin, enc, dec, targets, in_rel, tg_rel, reduction, blank=blank, w=w)
+    if w is None:
+        assert abs(f[0].item() - a[0].item()) <= 1e-5 * abs(a[0].item())
     for i, name in enumerate(("loss", "enc", "dec", "weight", "bias")):
         if a[i] is None:
             assert f[i] is None and not bias
             continue
         assert rel_err(f[i], a[i]) <= 1e-5, name
         assert rel_err(f[i], r[i]) <= 1e-4, name
+    return f, r
+
+
+@pytest.mark.parametrize("bias", [False, True])
+@pytest.mark.parametrize("act", ACTS, ids=lambda a: a.__name__)
+def test_fused_path_equals_dropin_chain_fp32(bias, act):
+    _fused_equals_dropin_fp32(bias, act, 0)              # V = 36: not a multiple of the 128-column tile
+
+
+@pytest.mark.parametrize("bias", [False, True])
+@pytest.mark.parametrize("act", ACTS, ids=lambda a: a.__name__)
+def test_fused_path_equals_dropin_chain_fp32_blank_in_the_last_column(bias, act):
+    _fused_equals_dropin_fp32(bias, act, 35)
+
+
+@pytest.mark.parametrize("blank", [0, 999])
+def test_fused_path_equals_dropin_chain_fp32_at_the_recipe_width(blank):
+    """V = 1000, J = 640 in fp32: eight column tiles, the last ragged (the only fp32 run of the cross-tile combine end to end)."""
+    _fused_equals_dropin_fp32(True, torch.nn.GELU, blank, J=640, V=1000)
+
+
+@pytest.mark.parametrize("blank", [0, 35])
+def test_fused_path_non_uniform_upstream_gradient(blank):
+    f, r = _fused_equals_dropin_fp32(True, torch.nn.GELU, blank, reduction="none", w=_W)
+    for b in range(3):                                    # the stream gradients per utterance
+        assert rel_err(f[1][b], r[1][b]) <= 1e-4 and rel_err(f[2][b], r[2][b]) <= 1e-4, b
+
+
+@pytest.mark.parametrize("dtype,tol", [(torch.float32, 1e-4), (torch.bfloat16, 2e-2)], ids=["f32", "bf16"])
+def test_fused_backward_utterance_groups(monkeypatch, dtype, tol):
+    """B = 5 with one utterance per backward group, two per group (the last group short) and all in one: groups are whole
+    utterances and every reduction has a fixed order, so the stream gradients are bit-identical; the weight and bias gradients add
+    the groups in another order (fp32: within 1e-5 of each other); everything within the path's bar of fp64."""
+    import summarymixing_amd.nnet.transducer as TR
+    B, T, U, J, V = 5, 20, 6, 128, 132
+    per = T * (U + 1)
+    tj, lin = _modules(J, V, True, seed=5)
+    enc, dec = _streams(B, T, U, J, dtype, 31)
+    targets, in_rel, tg_rel = _lattice(B, T, U, V, 32, ub0=True, blank=V - 1)
+    w = torch.tensor([0.25, -1.5, 3.0, 1.0, 0.5])
+    r = _ref_chain(tj, lin, enc, dec, targets, in_rel, tg_rel, "none", blank=V - 1, w=w)
+    runs = []
+    for group_rows in (per, 2 * per + 1, 1 << 30):       # 1 + 1 + 1 + 1 + 1, 2 + 2 + 1, 5
+        monkeypatch.setattr(TR, "_BWD_GROUP_ROWS", group_rows)
+        runs.append(_fused(tj, lin, enc, dec, targets, in_rel, tg_rel, "none", blank=V - 1, w=w))
+    for f in runs:
+        for i in range(5):
+            assert rel_err(f[i], r[i]) <= tol, i
+    for f in runs[:2]:
+        assert torch.equal(f[0], runs[2][0])
+        assert torch.equal(f[1], runs[2][1]), "d_enc differs between group sizes"
+        assert torch.equal(f[2], runs[2][2]), "d_dec differs between group sizes"
+        if dtype == torch.float32:
+            assert rel_err(f[3], runs[2][3]) <= 1e-5 and rel_err(f[4], runs[2][4]) <= 1e-5
 
 
 def test_fused_path_and_dropin_chain_bf16_against_fp64():
