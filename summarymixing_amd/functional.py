@@ -711,11 +711,57 @@ def mlp_bwd(dy, layers, act, saved, dtype, need_dx=True, res_grad=None, dx_out=N
 
 
 # ----------------------------------------------------------------------------------------------------
-# summary pooling variants: masked mean (per utterance), DynChunk window mean, dense (T,T) weights
+# summary operators: one object per way of pooling the summary s over time (summary_op picks the one of a cell run), each with its
+# sequence-parallel form where it has one (`seqpar`).  MeanSummary is per utterance: fwd(s, mask, B, T) -> sbar (B, sdim) float32 and
+# inv (B,) = 1 / valid frames, and a gradient path of its own.  The others are frame-wise, (N, sdim) in the compute dtype:
+# pool(x, out, B, T, reverse=False) is out = M x, reverse=True the transposed operator M^T x of the backward.
 # ----------------------------------------------------------------------------------------------------
+class MeanSummary:
+    """The masked mean over each utterance (summary_mixing.py:216-222); sequence-parallel: partial sums, one all-reduce."""
+    per_utterance, seqpar = True, True
+
+    def fwd(self, s, mask, B, T):
+        if not SP.enabled():
+            return ops.masked_mean(s, mask, B, T, scale=True, want_inv=True)       # (B, sdim) fp32
+        # time axis sharded over the group: local partial sums + valid-frame counts, ONE all-reduce, then the mean
+        sdim = s.shape[1]
+        ssum, _ = ops.masked_mean(s, mask, B, T, scale=False)
+        cnt = (mask.view(B, T).sum(1, dtype=torch.float32) if mask is not None
+               else torch.full((B,), float(T), dtype=torch.float32, device=s.device))
+        buf = torch.cat([ssum, cnt[:, None]], 1)
+        SP.all_reduce_sum(buf)
+        inv = (1.0 / buf[:, sdim]).contiguous()
+        return (buf[:, :sdim] * inv[:, None]).contiguous(), inv
+
+    def pool_fusable(self, B, T, sdim):
+        """Small batches (round 6): the mean over time and its broadcast run as ONE launch (smx_pool_bcast), in both directions."""
+        return _POOL_FUSE and not SP.enabled() and ops.pool_bcast_ok(B, T, sdim)
+
+    def bcast_grad(self, dsbar, inv, ds_out, B, T, side):
+        """ds_out = the broadcast over t of dsbar * inv.  side = (z, mask, act) | None: the act / mask backward of the projection that
+        produced s rides along (smx_masked_mean_bwd_act).  Returns whether it did: ds_out then is that projection's dZ."""
+        SP.all_reduce_sum(dsbar)                       # sequence-parallel: the mean's gradient sums over every shard
+        if side is None:
+            ops.bcast_rows(dsbar, inv, ds_out, B, T)
+            return False
+        ops.bcast_rows_act_bwd(dsbar, inv, ds_out, B, T, side[0], side[1], side[2])
+        return True
+
+    def sum_bcast_grad(self, dsd, inv, ds_out, B, T, side):
+        """bcast_grad of sum_t dsd: one launch for small batches (smx_pool_bcast)."""
+        if self.pool_fusable(B, T, dsd.shape[1]):
+            z_, mk_, a_ = side if side is not None else (None, None, L.ACT_NONE)
+            ops.pool_bcast(dsd, None, B, T, ds=ds_out, scale=False, want_mean=False, inv_in=inv, z=z_, mask_out=mk_,
+                           act=a_ if z_ is not None else L.ACT_NONE)
+            return side is not None
+        dsbar, _ = ops.masked_mean(dsd, None, B, T, scale=False)                   # sum over time
+        return self.bcast_grad(dsbar, inv, ds_out, B, T, side)
+
+
 class DynChunkMask:
     """The (T,T) DynChunk summary mask in closed form (TransformerASR.py:85-110, masked_false_or_true=False):
     frame t of chunk c sees chunks [c-left, c].  `dense()` materialises the reference's boolean matrix."""
+    per_utterance, seqpar = False, True
 
     def __init__(self, T, chunk_size, left_context=None):
         self.T, self.chunk_size, self.left_context = T, chunk_size, left_context
@@ -730,24 +776,93 @@ class DynChunkMask:
             m = m & (t[None, :] >= lo[:, None])
         return m
 
+    def pool(self, x, out, B, T, reverse=False):
+        return (_chunk_mean_seqpar if SP.enabled() else ops.chunk_mean)(x, out, B, T, self.chunk_size, self.left_context,
+                                                                         reverse=reverse)
+
 
 class DynChunkStream:
     """One layer's summary state for streaming inference (the DynChunkMask of a chunk-by-chunk run): `ring` holds the float32 sums
     of the last `left_context` chunks ((B, left, D); (B, D) running sums when left_context is None), `counter` is the context's
     device chunk counter (int64 (1,), shared by all layers).  Passed as cell_run's sum_mask: the summary becomes smx_stream_summary."""
+    per_utterance, seqpar, what = False, False, "streaming summary"
 
     def __init__(self, ring, counter, chunk_size, left_context=None):
         self.ring, self.counter, self.chunk_size, self.left_context = ring, counter, chunk_size, left_context
+
+    def pool(self, x, out, B, T):
+        return ops.stream_summary(x, out, B, T, self.chunk_size, self.left_context, self.ring, self.counter)
 
 
 class DynChunkSlots:
     """One layer's summary state for slot streaming (B independent streams, one per batch slot): `ring` as in DynChunkStream,
     `counters` the context's per-slot device chunk counters (int64 (B,), shared by all layers), `valid` the device int32 (B,)
     frames of each slot in this step.  Passed as cell_run's sum_mask: the summary becomes smx_slot_summary."""
+    per_utterance, seqpar, what = False, False, "slot streaming summary"
 
     def __init__(self, ring, counters, valid, chunk_size, left_context=None):
         self.ring, self.counters, self.valid = ring, counters, valid
         self.chunk_size, self.left_context = chunk_size, left_context
+
+    def pool(self, x, out, B, T):
+        return ops.slot_summary(x, out, B, T, self.left_context, self.ring, self.counters, self.valid)
+
+
+class ExpDecaySummary:
+    """SummaryMixing-expdecay without a sum_mask: (M s) / rowsum(M) with M_ij = decay^|i-j| is a two-sided exponential filter, run by
+    the O(T) kernels (smx_expdecay_mean_*); M is symmetric, so the transposed operator is M (x / rowsum(M))."""
+    per_utterance, seqpar = False, True
+
+    def __init__(self, decay):
+        self.decay = decay
+
+    def pool(self, x, out, B, T, reverse=False):
+        return (_expdecay_seqpar if SP.enabled() else ops.expdecay_mean)(x, out, B, T, self.decay, reverse=reverse)
+
+
+class DenseSummary:
+    """A dense (T,T) weight matrix (a boolean sum_mask, the Laplace weights of expdecay under a mask): sbar[b] = Wn s[b] with the
+    rows of Wn normalised to sum 1 - one batched GEMM each way."""
+    per_utterance, seqpar = False, False
+
+    def __init__(self, weights, dtype, device):
+        w = weights.to(device=device, dtype=torch.float32)
+        self.Wn = ops.cast((w / w.sum(dim=1, keepdim=True)).contiguous(), dtype)   # mask prep (T,T): plumbing
+
+    def pool(self, x, out, B, T, reverse=False):
+        return _dense_pool_bwd(x, B, T, self.Wn, out) if reverse else _dense_pool_fwd(x, B, T, self.Wn, out)
+
+
+def _sdim(P):
+    ly = P["summary_proj"][-1]
+    return ly["W"].shape[0] if ly["kind"] == "linear" else ly["W"].shape[0] * ly["W"].shape[2]
+
+
+def summary_op(mode, cfg, P, sum_mask, T, dtype, device, need_bwd):
+    """The summary operator of one run of the cell, or the refusal of a combination no kernel serves."""
+    sm = None if mode == "SummaryMixing-lite" else sum_mask                        # the lite branch ignores sum_mask (:286-310)
+    if isinstance(sm, (DynChunkStream, DynChunkSlots)) and (need_bwd or mode not in ("SummaryMixing", "SummaryMixing-fast")):
+        raise NotImplementedError(f"{sm.what}: inference of the SummaryMixing / SummaryMixing-fast modes only")
+    if mode == "SummaryMixing-expdecay" and sm is None and _sdim(P) % 8 == 0:
+        # the frozen decay constant (summary_mixing.py:154-157) is read once
+        op = ExpDecaySummary(cfg["decay"]() if "decay" in cfg else float(P["decay_constant"].detach().float().cpu()))
+    elif mode == "SummaryMixing-expdecay":
+        # Laplace weights (summary_mixing.py:316-365): M_ij = decay^|i-j| * binary_mask
+        idx = torch.arange(T, device=device)
+        lap = torch.exp((idx[None, :] - idx[:, None]).abs().float() * torch.log(P["decay_constant"].detach().float()))
+        if isinstance(sm, DynChunkMask):
+            sm = sm.dense(device)
+        if sm is not None:
+            lap = lap * sm.to(device=device, dtype=torch.float32)
+        op = DenseSummary(lap, dtype, device)
+    elif sm is None:
+        op = MeanSummary()
+    else:
+        op = DenseSummary(sm, dtype, device) if isinstance(sm, torch.Tensor) else sm
+    if SP.enabled() and not op.seqpar:
+        raise NotImplementedError("sequence-parallel mode supports the per-utterance mean, the Dynamic Chunk Training mask and "
+                                  "the mask-free expdecay summary (no dense sum_mask)")
+    return op
 
 
 def _chunk_mean_seqpar(x, out, B, T, chunk, left, reverse=False):
@@ -809,10 +924,9 @@ def _expdecay_seqpar(x, out, B, T, decay, reverse=False):
     return out
 
 
-def _dense_pool_fwd(s, B, T, Wn):
+def _dense_pool_fwd(s, B, T, Wn, out):
     """sbar[b] = Wn (T,T) @ s[b]  (Wn already row-normalised, compute dtype)."""
     D = s.shape[1]
-    out = torch.empty((B * T, D), dtype=s.dtype, device=s.device)
     ops.gemm(L.GEMM_NN, Wn, s, out, T, D, T, None, batch=B, sa=0, sb=T * s.stride(0), sc=T * D)
     return out
 
@@ -826,13 +940,138 @@ def _dense_pool_bwd(dsbar, B, T, Wn, ds_out):
 
 
 # ----------------------------------------------------------------------------------------------------
-# the SummaryMixing cell
+# the SummaryMixing cell: projections -> summary -> merge, and the backward of the three
 # ----------------------------------------------------------------------------------------------------
+def _cell_project(P, mode, act, l, x, mask, need_bwd, p_drop):
+    """The projections of x -> (local, s, cat, s1, sv_lp, sv_s): sv_lp the saved state of the projection that produced `local`
+    (fast mode: global_proj, which produced s as well; sv_s is then None), sv_s that of summary_proj.
+    cat, s1: in training, where the last layer of that projection is a Linear, it writes D(local) (dropout seed s1) straight into the
+    merge input cat = [D(local) | D(repeat(sbar))] (summary_mixing.py:237-239,282-284): the dropout rides in its epilogue.  Else None."""
+    dtype, N = x.dtype, x.shape[0]
+    cat = s1 = None
+    if mode == "SummaryMixing-fast":
+        gp = P["global_proj"]
+        if p_drop > 0.0 and len(gp) == 1 and gp[0]["kind"] == "linear" and l % 8 == 0:
+            # columns < l only, mask indexed (n, l); the summary half is pooled from cat and then overwritten by the dropped
+            # broadcast of its mean
+            s1 = ops.new_dropout_seed()
+            cat = torch.empty((N, 2 * l), dtype=dtype, device=x.device)
+            g, sv_g = mlp_fwd(x, gp, act, mask, need_bwd, dtype, last_drop=(p_drop, s1), last_out=cat, last_drop_cols=l)
+        else:
+            g, sv_g = mlp_fwd(x, gp, act, mask, need_bwd, dtype)                   # (N, 2l)
+        return g[:, :l], g[:, l:], cat, s1, sv_g, None
+    lp = P["local_proj"]
+    lw, sdim = (lp[-1]["W"].shape[0] if lp[-1]["kind"] == "linear" else 0), _sdim(P)
+    if p_drop > 0.0 and lw and lw % 8 == 0 and sdim % 8 == 0:
+        s1 = ops.new_dropout_seed()
+        cat = torch.empty((N, lw + sdim), dtype=dtype, device=x.device)
+        local, sv_l = mlp_fwd(x, lp, act, mask, need_bwd, dtype, last_drop=(p_drop, s1), last_out=cat[:, :lw])
+    else:
+        local, sv_l = mlp_fwd(x, lp, act, mask, need_bwd, dtype)
+    s, sv_s = mlp_fwd(x, P["summary_proj"], act, mask, need_bwd, dtype)
+    return local, s, cat, s1, sv_l, sv_s
+
+
+def _cell_summary(op, s, mask, B, T, p_drop, cat):
+    """s -> (sbar, inv, s2).  Small batches in training, when the projections left a `cat`: mean over time + repeat + the merge
+    input's dropout (seed s2) in ONE launch, straight into the summary half of cat (fast mode: in place - a workgroup reads all T rows
+    of its columns before it writes any); sbar is then None.  Else s2 is None and the merge draws it."""
+    sdim = s.shape[1]
+    if op.per_utterance and p_drop > 0.0 and cat is not None and op.pool_fusable(B, T, sdim):
+        s2 = ops.new_dropout_seed()
+        _, inv = ops.pool_bcast(s, mask, B, T, ds=cat[:, cat.shape[1] - sdim:], scale=True, want_mean=False, want_inv=True,
+                                drop=(p_drop, s2))
+        return None, inv, s2
+    if op.per_utterance:
+        return op.fwd(s, mask, B, T) + (None,)
+    return op.pool(s, torch.empty((B * T, sdim), dtype=s.dtype, device=s.device), B, T), None, None
+
+
+def _cell_merge(mg, Wm, act, op, local, sbar, cat, s1, s2, p_drop, B, T, need_bwd, res, ln_next, out, out_drop):
+    """y = res + act(local W_l^T + sbar W_s^T + b) -> (y, zm, post, sbar_t, cat, s1, s2).  post: (LN(y), stats) where the LayerNorm
+    ln_next rode in the epilogue, else None.  sbar_t: the summary as the merge read it (for its wgrad), None in training."""
+    dtype, lw = local.dtype, local.shape[1]
+    Wl, Ws = Wm[:, :lw], Wm[:, lw:]
+    post = []
+    lnn = None if ln_next is None else LnNext(ln_next[0], ln_next[1], ln_next[2], need_bwd)
+    if p_drop > 0.0:
+        # training: dropout acts on cat[local, repeat(sbar)] per FRAME (summary_mixing.py:237-239,282-284), which
+        # breaks the per-utterance factorisation -> materialise the dropped concatenation once and run K = l + s
+        if s2 is None:                                     # (else cat is complete: smx_pool_bcast wrote the dropped broadcast)
+            if cat is not None:
+                s2 = ops.new_dropout_seed()
+            else:
+                s1, s2 = ops.new_dropout_seed(), ops.new_dropout_seed()
+                cat = torch.empty((local.shape[0], lw + sbar.shape[1]), dtype=dtype, device=local.device)
+                ops.dropout(local, p_drop, s1, out=cat[:, :lw])
+            if op.per_utterance:
+                ops.bcast_rows(sbar, None, cat[:, lw:], B, T, drop=(p_drop, s2))   # repeat + dropout in one pass
+            else:
+                ops.dropout(sbar, p_drop, s2, out=cat[:, lw:])
+        sbar_t = None
+        y, zm = linear_fwd(cat, Wm, mg["b"], act, None, res=res, save_z=need_bwd, ln_next=lnn, ln_post=post, out=out,
+                           drop=out_drop, wparam=mg["W"])
+    elif op.per_utterance:
+        sbar_t = ops.cast(sbar, dtype)                                         # (B, sdim) in compute dtype
+        c0, _ = linear_fwd(sbar_t, Ws, None, out_f32=True)                     # (B, s_out) fp32
+        y, zm = linear_fwd(local, Wl, mg["b"], act, None, res=res, c0=c0, c0_mode=L.C0_GROUP, c0_div=T,
+                           save_z=need_bwd, ln_next=lnn, ln_post=post, out=out, drop=out_drop)
+    else:
+        sbar_t = sbar
+        c0, _ = linear_fwd(sbar, Ws, None, out_f32=True)                       # (N, s_out) fp32
+        y, zm = linear_fwd(local, Wl, mg["b"], act, None, res=res, c0=c0, c0_mode=L.C0_ROW, save_z=need_bwd, out=out,
+                           drop=out_drop)
+    return y, zm, (post[0] if post else None), sbar_t, cat, s1, s2
+
+
+def _cell_lite(P, act, op, x, mask, B, T, need_bwd, res):
+    """SummaryMixing-lite (summary_mixing.py:286-310): the per-utterance summary alone, repeated over time -> (y3, bwd | None)."""
+    dtype, N, dev = x.dtype, x.shape[0], x.device
+    s, sv_s = mlp_fwd(x, P["summary_proj"], act, mask, need_bwd, dtype)
+    sdim = s.shape[1]
+    sbar, inv = op.fwd(s, mask, B, T)
+    if res is None:
+        y3 = ops.cast(sbar, dtype).unsqueeze(1).expand(B, T, sdim)                 # stride-0 view like :308
+    else:                                                                          # inside an encoder layer: res + summary
+        yb = torch.empty((N, sdim), dtype=res.dtype, device=dev)                   # (res.dtype: the stream may be float32)
+        ops.bcast_rows(sbar, None, yb, B, T)
+        y3 = ops.axpby(1.0, res, 1.0, yb).view(B, T, sdim)
+
+    def bwd_lite(dy3, dz_in=None):
+        assert dz_in is None
+        dy = ops.rows2d(dy3.contiguous())
+        dsbar, _ = ops.masked_mean(dy, None, B, T, scale=False)                    # sum over time
+        ds = torch.empty((N, sdim), dtype=dtype, device=dev)
+        op.bcast_grad(dsbar, inv, ds, B, T, None)
+        dx = mlp_bwd(ds, P["summary_proj"], act, sv_s, dtype)
+        return dx.view(B, T, -1)
+    return y3, (bwd_lite if need_bwd else None)
+
+
+def _fused_sides(P, fast, act, lproj, sv_lp, sv_s, lw):
+    """What the cell's backward fuses of the act / mask backward of the projections' last layers -> (up_local, side), each None when
+    that layer is not a Linear or has neither activation nor mask.
+    up_local: linear_bwd's `up` for the LOCAL columns of lproj: the merge dgrad's epilogue (SMX_EPI_ACT_GRAD) emits their dZ (the
+    bias gradient comes out of the projection's own wgrad).
+    side = (z, mask, act) for the SUMMARY columns - of global_proj (fast mode, when the local ones are fused too), else of summary_proj,
+    whose mlp_bwd then starts from dZ: it rides in the broadcast of the mean's gradient (MeanSummary.bcast_grad)."""
+    z, mk = sv_lp[-1][1], sv_lp[-1][2]
+    up_local = side = None
+    if lproj[-1]["kind"] == "linear" and (z is not None or mk is not None):
+        up_local = (z[:, :lw] if z is not None else None, act if z is not None else L.ACT_NONE, mk, 1.0, None, None)
+        if fast:
+            side = (z[:, lw:] if z is not None else None, mk, act)
+    if not fast and P["summary_proj"][-1]["kind"] == "linear":
+        z, mk = sv_s[-1][1], sv_s[-1][2]
+        if z is not None or mk is not None:
+            side = (z, mk, act if z is not None else L.ACT_NONE)
+    return up_local, side
+
+
 def cell_run(P, cfg, B, T, mask, sum_mask, p_drop=0.0):
-    """Build run(x, need_bwd) for the cell.  P: parameter dict, cfg: mode/act/l.
-    Returns a closure operating on (B,T,d) tensors.  `skip_is_input_res`: optional (N,s) residual added to the
-    output (Conformer `x + skip`, Conformer.py:530) -- its gradient is returned by bwd as a second value."""
+    """Build run(x, need_bwd) for the cell.  P: parameter dict, cfg: mode/act/l.  Returns a closure operating on (B,T,d) tensors."""
     mode, act, l = cfg["mode"], cfg["act"], cfg["local_proj_out_dim"]
+    fast = mode == "SummaryMixing-fast"
 
     def run(x3, need_bwd, res=None, ln_next=None, out=None, out_drop=None):
         """ln_next = (gamma, beta, eps) of the LayerNorm that follows the cell output: run in the merge GEMM's epilogue where
@@ -840,192 +1079,23 @@ def cell_run(P, cfg, B, T, mask, sum_mask, p_drop=0.0):
         out / out_drop = (p, seed): the caller applies dropout to the cell output and wants it in a (N, s_out) view of its own
         buffer (the Branchformer's merge input): both ride in the merge GEMM's epilogue, and the backward takes the dropout
         backward into its first pass (not for the lite mode)."""
-        dtype = x3.dtype
-        x = ops.rows2d(x3)
-        N = x.shape[0]
-        dev = x.device
-        pool_kind = "mean"
-        Wn = None
-        sm = sum_mask
-        decay = None
-        def _sdim():
-            ly = P["summary_proj"][-1]
-            return ly["W"].shape[0] if ly["kind"] == "linear" else ly["W"].shape[0] * ly["W"].shape[2]
-        if mode == "SummaryMixing-expdecay" and sm is None and _sdim() % 8 == 0:
-            # no sum_mask: (M s)/rowsum(M) with M_ij = decay^|i-j| is a two-sided exponential filter -> O(T) kernels
-            # (smx_expdecay_mean_*); the frozen decay constant (summary_mixing.py:154-157) is read once
-            decay = cfg["decay"]() if "decay" in cfg else float(P["decay_constant"].detach().float().cpu())
-            pool_kind = "expdecay"
-        elif mode == "SummaryMixing-expdecay":
-            # Laplace weights (summary_mixing.py:316-365): M_ij = decay^|i-j| * binary_mask
-            idx = torch.arange(T, device=dev)
-            lap = torch.exp((idx[None, :] - idx[:, None]).abs().float() * torch.log(P["decay_constant"].detach().float()))
-            if isinstance(sm, DynChunkMask):
-                sm = sm.dense(dev)
-            if sm is not None:
-                lap = lap * sm.to(device=dev, dtype=torch.float32)
-            sm = lap
+        dtype, x = x3.dtype, ops.rows2d(x3)
+        N, dev = x.shape[0], x.device
+        op = summary_op(mode, cfg, P, sum_mask, T, dtype, dev, need_bwd)
         if mode == "SummaryMixing-lite":
-            sm = None                                   # the lite branch ignores sum_mask (:286-310)
-        if isinstance(sm, DynChunkMask):
-            pool_kind = "chunk"
-        elif isinstance(sm, DynChunkStream):
-            if need_bwd or mode not in ("SummaryMixing", "SummaryMixing-fast"):
-                raise NotImplementedError("streaming summary: inference of the SummaryMixing / SummaryMixing-fast modes only")
-            pool_kind = "stream"
-        elif isinstance(sm, DynChunkSlots):
-            if need_bwd or mode not in ("SummaryMixing", "SummaryMixing-fast"):
-                raise NotImplementedError("slot streaming summary: inference of the SummaryMixing / SummaryMixing-fast modes only")
-            pool_kind = "slots"
-        elif sm is not None:
-            pool_kind = "dense"
-            w = sm.to(device=dev, dtype=torch.float32)
-            Wn = ops.cast((w / w.sum(dim=1, keepdim=True)).contiguous(), dtype)   # mask prep (T,T): plumbing
-
-        # ---- projections -------------------------------------------------------------------------
-        cat = s1 = s2 = None
-        cat_has_local = False
-        if mode == "SummaryMixing-fast":
-            gp = P["global_proj"]
-            if p_drop > 0.0 and len(gp) == 1 and gp[0]["kind"] == "linear" and l % 8 == 0:
-                # training: the projection writes straight into the merge input cat = [D(local) | s]: the dropout of the
-                # local half (summary_mixing.py:282-284) rides in its epilogue (columns < l only, mask indexed (n, l)); the
-                # summary half is pooled from there and then overwritten by the dropped broadcast of its mean
-                s1 = ops.new_dropout_seed()
-                cat = torch.empty((N, 2 * l), dtype=dtype, device=dev)
-                g, sv_g = mlp_fwd(x, gp, act, mask, need_bwd, dtype, last_drop=(p_drop, s1), last_out=cat, last_drop_cols=l)
-                cat_has_local = True
-            else:
-                g, sv_g = mlp_fwd(x, gp, act, mask, need_bwd, dtype)               # (N, 2l)
-            local, s = g[:, :l], g[:, l:]
-            sv_l = sv_s = None
-        elif mode == "SummaryMixing-lite":
-            s, sv_s = mlp_fwd(x, P["summary_proj"], act, mask, need_bwd, dtype)
-            local = None
-            sv_l = sv_g = None
-        else:
-            lp = P["local_proj"]
-            lw_ = lp[-1]["W"].shape[0] if lp[-1]["kind"] == "linear" else 0
-            if p_drop > 0.0 and lw_ and lw_ % 8 == 0 and _sdim() % 8 == 0:
-                # training: the local projection's last Linear writes D(local) straight into the merge input
-                # cat = [D(local) | D(repeat(sbar))] (summary_mixing.py:237-239): its dropout rides in the GEMM epilogue
-                s1 = ops.new_dropout_seed()
-                cat = torch.empty((N, lw_ + _sdim()), dtype=dtype, device=dev)
-                local, sv_l = mlp_fwd(x, lp, act, mask, need_bwd, dtype, last_drop=(p_drop, s1), last_out=cat[:, :lw_])
-                cat_has_local = True
-            else:
-                local, sv_l = mlp_fwd(x, lp, act, mask, need_bwd, dtype)
-            s, sv_s = mlp_fwd(x, P["summary_proj"], act, mask, need_bwd, dtype)
-            sv_g = None
-        sdim = s.shape[1]
-
-        # ---- summary ------------------------------------------------------------------------------
-        inv = None
-        pool_fused = False
-        sp = SP.enabled()
-        if sp and pool_kind not in ("mean", "expdecay", "chunk"):
-            raise NotImplementedError("sequence-parallel mode supports the per-utterance mean, the Dynamic Chunk Training mask and "
-                                      "the mask-free expdecay summary (no dense sum_mask)")
-        if sp and pool_kind == "expdecay":
-            sbar = torch.empty((N, sdim), dtype=dtype, device=dev)
-            _expdecay_seqpar(s, sbar, B, T, decay)
-        elif sp and pool_kind == "chunk":
-            sbar = torch.empty((N, sdim), dtype=dtype, device=dev)
-            _chunk_mean_seqpar(s, sbar, B, T, sm.chunk_size, sm.left_context)
-        elif sp:
-            # time axis sharded over the group: local partial sums + valid-frame counts, ONE all-reduce, then the mean
-            ssum, _ = ops.masked_mean(s, mask, B, T, scale=False)
-            cnt = (mask.view(B, T).sum(1, dtype=torch.float32) if mask is not None
-                   else torch.full((B,), float(T), dtype=torch.float32, device=dev))
-            buf = torch.cat([ssum, cnt[:, None]], 1)
-            SP.all_reduce_sum(buf)
-            inv = (1.0 / buf[:, sdim]).contiguous()
-            sbar = (buf[:, :sdim] * inv[:, None]).contiguous()
-        elif pool_kind == "mean" and p_drop > 0.0 and cat_has_local and _POOL_FUSE and ops.pool_bcast_ok(B, T, sdim):
-            # small batches (round 6): mean over time + repeat + the merge input's dropout in ONE launch, straight into the summary
-            # half of cat (fast mode: in place - a workgroup reads all T rows of its columns before it writes any)
-            s2 = ops.new_dropout_seed()
-            sbar = None
-            _, inv = ops.pool_bcast(s, mask, B, T, ds=cat[:, cat.shape[1] - sdim:], scale=True, want_mean=False, want_inv=True,
-                                    drop=(p_drop, s2))
-            pool_fused = True
-        elif pool_kind == "mean":
-            sbar, inv = ops.masked_mean(s, mask, B, T, scale=True, want_inv=True)   # (B, sdim) fp32
-        elif pool_kind == "chunk":
-            sbar = torch.empty((N, sdim), dtype=dtype, device=dev)
-            ops.chunk_mean(s, sbar, B, T, sm.chunk_size, sm.left_context)
-        elif pool_kind == "stream":
-            sbar = torch.empty((N, sdim), dtype=dtype, device=dev)
-            ops.stream_summary(s, sbar, B, T, sm.chunk_size, sm.left_context, sm.ring, sm.counter)
-        elif pool_kind == "slots":
-            sbar = torch.empty((N, sdim), dtype=dtype, device=dev)
-            ops.slot_summary(s, sbar, B, T, sm.left_context, sm.ring, sm.counters, sm.valid)
-        elif pool_kind == "expdecay":
-            sbar = torch.empty((N, sdim), dtype=dtype, device=dev)
-            ops.expdecay_mean(s, sbar, B, T, decay)
-        else:
-            sbar = _dense_pool_fwd(s, B, T, Wn)
-
-        if mode == "SummaryMixing-lite":
-            if res is None:
-                y3 = ops.cast(sbar, dtype).unsqueeze(1).expand(B, T, sdim)        # stride-0 view like :308
-            else:                                                                 # inside an encoder layer: res + summary
-                yb = torch.empty((N, sdim), dtype=res.dtype, device=dev)           # (res.dtype: the stream may be float32)
-                ops.bcast_rows(sbar, None, yb, B, T)
-                y3 = ops.axpby(1.0, res, 1.0, yb).view(B, T, sdim)
-
-            def bwd_lite(dy3, dz_in=None):
-                assert dz_in is None
-                dy = ops.rows2d(dy3.contiguous())
-                dsbar, _ = ops.masked_mean(dy, None, B, T, scale=False)            # sum over time
-                SP.all_reduce_sum(dsbar)                                           # (sequence-parallel: over all shards)
-                ds = torch.empty((N, sdim), dtype=dtype, device=dev)
-                ops.bcast_rows(dsbar, inv, ds, B, T)
-                dx = mlp_bwd(ds, P["summary_proj"], act, sv_s, dtype)
-                return dx.view(B, T, -1)
-            return (y3, (bwd_lite if need_bwd else None), None) if ln_next is not None else (y3, (bwd_lite if need_bwd else None))
-
-        # ---- merge: y = res + act(local W_l^T + sbar W_s^T + b) -------------------------------------
+            y3, bwd = _cell_lite(P, act, op, x, mask, B, T, need_bwd, res)
+            return (y3, bwd, None) if ln_next is not None else (y3, bwd)
+        local, s, cat, s1, sv_lp, sv_s = _cell_project(P, mode, act, l, x, mask, need_bwd, p_drop)
+        lw, sdim = local.shape[1], s.shape[1]
+        sbar, inv, s2 = _cell_summary(op, s, mask, B, T, p_drop, cat)
         mg = P["summary_local_merging"][0]
         Wm = wcast(mg["W"], dtype)                                              # (s_out, l + sdim)
-        lw = local.shape[1]
-        Wl, Ws = Wm[:, :lw], Wm[:, lw:]
-        post = []
-        lnn = None if ln_next is None else LnNext(ln_next[0], ln_next[1], ln_next[2], need_bwd)
-        if p_drop > 0.0:
-            # training: dropout acts on cat[local, repeat(sbar)] per FRAME (summary_mixing.py:237-239,282-284), which
-            # breaks the per-utterance factorisation -> materialise the dropped concatenation once and run K = l + s
-            if pool_fused:
-                pass                                       # (cat is complete: smx_pool_bcast wrote the dropped broadcast)
-            elif cat_has_local:
-                s2 = ops.new_dropout_seed()
-            else:
-                s1, s2 = ops.new_dropout_seed(), ops.new_dropout_seed()
-                cat = torch.empty((N, lw + sdim), dtype=dtype, device=dev)
-                ops.dropout(local, p_drop, s1, out=cat[:, :lw])
-            if pool_fused:
-                pass
-            elif pool_kind == "mean":
-                ops.bcast_rows(sbar, None, cat[:, lw:], B, T, drop=(p_drop, s2))   # repeat + dropout in one pass
-            else:
-                ops.dropout(sbar, p_drop, s2, out=cat[:, lw:])
-            sbar_t = None
-            y, zm = linear_fwd(cat, Wm, mg["b"], act, None, res=res, save_z=need_bwd, ln_next=lnn, ln_post=post, out=out,
-                               drop=out_drop, wparam=mg["W"])
-        elif pool_kind == "mean":
-            sbar_t = ops.cast(sbar, dtype)                                         # (B, sdim) in compute dtype
-            c0, _ = linear_fwd(sbar_t, Ws, None, out_f32=True)                     # (B, s_out) fp32
-            y, zm = linear_fwd(local, Wl, mg["b"], act, None, res=res, c0=c0, c0_mode=L.C0_GROUP, c0_div=T,
-                               save_z=need_bwd, ln_next=lnn, ln_post=post, out=out, drop=out_drop)
-        else:
-            sbar_t = sbar
-            c0, _ = linear_fwd(sbar, Ws, None, out_f32=True)                       # (N, s_out) fp32
-            y, zm = linear_fwd(local, Wl, mg["b"], act, None, res=res, c0=c0, c0_mode=L.C0_ROW, save_z=need_bwd, out=out,
-                               drop=out_drop)
+        y, zm, post, sbar_t, cat, s1, s2 = _cell_merge(mg, Wm, act, op, local, sbar, cat, s1, s2, p_drop, B, T, need_bwd, res, ln_next,
+                                                       out, out_drop)
         y3 = y.view(B, T, -1)
-        post = post[0] if post else None
         if not need_bwd:
             return (y3, None, post) if ln_next is not None else (y3, None)
+        lproj = P["global_proj"] if fast else P["local_proj"]
 
         def bwd(dy3, ln=None, ln_res=None, ln_second=None, dz_in=None):
             """ln / ln_res / ln_second (only when bwd.can_fuse_ln): the LayerNorm whose output is this cell's input runs its
@@ -1035,68 +1105,15 @@ def cell_run(P, cfg, B, T, mask, sum_mask, p_drop=0.0):
             dy = ops.rows2d(dy3) if out_drop is not None else ops.rows2d(dy3 if dy3.is_contiguous() else dy3.contiguous())
             s_out = dy.shape[1]
             gWm, gbm = gacc(mg["W"]), gacc(mg["b"])
-            # buffer that receives [dlocal | ds] for the fast mode (one dg for the fused projection)
-            if mode == "SummaryMixing-fast":
+            if fast:             # one buffer receives [dlocal | ds]: the dZ of the fused projection
                 dg = torch.empty((N, 2 * l), dtype=dtype, device=dev)
                 dlocal_out, ds_out = dg[:, :l], dg[:, l:]
             else:
                 dlocal_out = torch.empty((N, lw), dtype=dtype, device=dev)
                 ds_out = torch.empty((N, sdim), dtype=dtype, device=dev)
-            # the projections whose outputs are `local` (and, fused, `s`): their act/mask backward for the LOCAL columns is
-            # fused into the merge dgrad's epilogue (SMX_EPI_ACT_GRAD), which then emits dZ and the bias gradient
-            if mode == "SummaryMixing-fast":
-                lproj, sv_lp = P["global_proj"], sv_g
-            else:
-                lproj, sv_lp = P["local_proj"], sv_l
-            fuse_local = lproj[-1]["kind"] == "linear"
-            up_local = None
-            if fuse_local:
-                z_lp, mk_lp = sv_lp[-1][1], sv_lp[-1][2]
-                up_local = (z_lp[:, :lw] if z_lp is not None else None, act if z_lp is not None else L.ACT_NONE, mk_lp, 1.0,
-                            None, None)                   # (the bias gradient comes out of the projection's own wgrad)
-                if z_lp is None and mk_lp is None:
-                    up_local = None
-                    fuse_local = False
-            # fast mode + per-utterance mean: the broadcast of the summary gradient applies the act/mask backward of the
-            # summary columns of global_proj itself (smx_masked_mean_bwd_act) - no separate act_mask_bwd pass over ds
-            sum_done = False
-
-            def bcast_side():
-                """(z, mask, act) of the projection that produced the summary columns when its act / mask backward can ride in the
-                broadcast of the summary gradient, else None."""
-                if mode == "SummaryMixing-fast" and fuse_local:
-                    z_g, mk_g = sv_g[-1][1], sv_g[-1][2]
-                    if z_g is not None or mk_g is not None:
-                        return (z_g[:, l:] if z_g is not None else None, mk_g, act)
-                elif mode != "SummaryMixing-fast" and P["summary_proj"][-1]["kind"] == "linear":
-                    # full / expdecay modes: the same for the last layer of summary_proj (its mlp_bwd then starts from dZ)
-                    z_s, mk_s = sv_s[-1][1], sv_s[-1][2]
-                    if z_s is not None or mk_s is not None:
-                        return (z_s, mk_s, act if z_s is not None else L.ACT_NONE)
-                return None
-
-            def bcast_ds(dsbar_):
-                nonlocal sum_done
-                SP.all_reduce_sum(dsbar_)                  # sequence-parallel: the mean's gradient sums over every shard
-                side = bcast_side()
-                if side is not None:
-                    ops.bcast_rows_act_bwd(dsbar_, inv, ds_out, B, T, side[0], side[1], side[2])
-                    sum_done = True
-                    return
-                ops.bcast_rows(dsbar_, inv, ds_out, B, T)
-
-            def sum_bcast_ds(dsd_):
-                """ds_out = broadcast over t of (sum_t dsd_) * inv [* act'(z) * mask]: one launch for small batches (smx_pool_bcast)."""
-                nonlocal sum_done
-                if _POOL_FUSE and not SP.enabled() and ops.pool_bcast_ok(B, T, dsd_.shape[1]):
-                    side = bcast_side()
-                    z_, mk_, a_ = side if side is not None else (None, None, L.ACT_NONE)
-                    ops.pool_bcast(dsd_, None, B, T, ds=ds_out, scale=False, want_mean=False, inv_in=inv, z=z_, mask_out=mk_,
-                                   act=a_ if z_ is not None else L.ACT_NONE)
-                    sum_done = side is not None
-                    return
-                dsbar_, _ = ops.masked_mean(dsd_, None, B, T, scale=False)               # sum over time
-                bcast_ds(dsbar_)
+            up_local, side = _fused_sides(P, fast, act, lproj, sv_lp, sv_s, lw)
+            fuse_local = up_local is not None
+            sum_done = False     # ds_out already is the dZ of the projection behind s (`side` rode in the mean's broadcast)
             if p_drop > 0.0:
                 # dgrad of the K = l + s merge as two GEMMs over the column halves of W: the dropout backward of each half
                 # (and the local half's act/mask backward) rides in the epilogue instead of separate passes
@@ -1110,68 +1127,48 @@ def cell_run(P, cfg, B, T, mask, sum_mask, p_drop=0.0):
                     ops.act_mask_bwd(dy, zm, None, act, 1.0, dzm, None if wb else gbm, drop=out_drop)
                 if gWm is not None:
                     _wgrad(dzm, cat, gWm, N, s_out, lw + sdim, gbm if wb else None)
-                if fuse_local:
-                    e = ops.epilogue(act=up_local[1], act_grad_z=up_local[0], row_mask=up_local[2], drop=(p_drop, s1),
-                                     colsum=up_local[5]) if up_local[0] is not None else \
-                        ops.epilogue(row_mask=up_local[2], drop=(p_drop, s1), colsum=up_local[5])
-                else:
-                    e = ops.epilogue(drop=(p_drop, s1))
-                ops.gemm(L.GEMM_NN, dzm, Wm[:, :lw], dlocal_out, N, lw, s_out, e)
+                z_up, a_up, mk_up = up_local[:3] if fuse_local else (None, L.ACT_NONE, None)
+                ops.gemm(L.GEMM_NN, dzm, Wm[:, :lw], dlocal_out, N, lw, s_out,
+                         ops.epilogue(act=a_up, act_grad_z=z_up, row_mask=mk_up, drop=(p_drop, s1)))
                 dsd = torch.empty((N, sdim), dtype=dtype, device=dev)
                 ops.gemm(L.GEMM_NN, dzm, Wm[:, lw:], dsd, N, sdim, s_out, ops.epilogue(drop=(p_drop, s2)))
-                if pool_kind == "mean":
-                    sum_bcast_ds(dsd)
-                elif pool_kind == "chunk":
-                    (_chunk_mean_seqpar if SP.enabled() else ops.chunk_mean)(dsd, ds_out, B, T, sm.chunk_size, sm.left_context, reverse=True)
-                elif pool_kind == "expdecay":
-                    (_expdecay_seqpar if SP.enabled() else ops.expdecay_mean)(dsd, ds_out, B, T, decay, reverse=True)
+                if op.per_utterance:
+                    sum_done = op.sum_bcast_grad(dsd, inv, ds_out, B, T, side)
                 else:
-                    _dense_pool_bwd(dsd, B, T, Wn, ds_out)
-            elif pool_kind == "mean":
-                _, dzm = linear_bwd(dy if dz_in is None else dz_in, local, Wl, zm, act, None, 1.0,
+                    op.pool(dsd, ds_out, B, T, reverse=True)
+            else:
+                _, dzm = linear_bwd(dy if dz_in is None else dz_in, local, Wm[:, :lw], zm, act, None, 1.0,
                                     gWm[:, :lw] if gWm is not None else None, gbm, True, None, dx_out=dlocal_out, up=up_local,
                                     dz_ready=dz_in is not None, drop=out_drop)
-                # per-utterance sums of dZ (the gradient of the C0 side input) through the fixed-order pool kernel: the
-                # fused variant (smx_act_mask_bwd dgroup) adds with fp32 atomics, i.e. not bit-reproducibly
-                dc0, _ = ops.masked_mean(dzm, None, B, T, scale=False)
-                dc0_t = ops.cast(dc0, dtype)
-                if gWm is not None:      # dW_s += dc0^T sbar
-                    ops.wgrad(dc0_t, sbar_t, gWm[:, lw:], B, s_out, sdim)
-                dsbar = torch.empty((B, sdim), dtype=torch.float32, device=dev)
-                ops.gemm(L.GEMM_NN, dc0_t, Ws, dsbar, B, sdim, s_out, ops.epilogue(out_mode=L.OUT_F32))
-                bcast_ds(dsbar)
-            else:
-                _, dzm = linear_bwd(dy if dz_in is None else dz_in, local, Wl, zm, act, None, 1.0,
-                                    gWm[:, :lw] if gWm is not None else None, gbm, True, None, dx_out=dlocal_out, up=up_local,
-                                    dz_ready=dz_in is not None, drop=out_drop)
-                if gWm is not None:      # dW_s += dzm^T sbar
-                    ops.wgrad(dzm, sbar_t, gWm[:, lw:], N, s_out, sdim)
-                dsb = torch.empty((N, sdim), dtype=dtype, device=dev)
-                ops.gemm(L.GEMM_NN, dzm, Ws, dsb, N, sdim, s_out, None)
-                if pool_kind == "chunk":
-                    (_chunk_mean_seqpar if SP.enabled() else ops.chunk_mean)(dsb, ds_out, B, T, sm.chunk_size, sm.left_context, reverse=True)
-                elif pool_kind == "expdecay":
-                    (_expdecay_seqpar if SP.enabled() else ops.expdecay_mean)(dsb, ds_out, B, T, decay, reverse=True)
+                if op.per_utterance:
+                    # per-utterance sums of dZ (the gradient of the C0 side input) through the fixed-order pool kernel: the
+                    # fused variant (smx_act_mask_bwd dgroup) adds with fp32 atomics, i.e. not bit-reproducibly
+                    dc0, _ = ops.masked_mean(dzm, None, B, T, scale=False)
+                    dc0_t = ops.cast(dc0, dtype)
+                    if gWm is not None:      # dW_s += dc0^T sbar
+                        ops.wgrad(dc0_t, sbar_t, gWm[:, lw:], B, s_out, sdim)
+                    dsbar = torch.empty((B, sdim), dtype=torch.float32, device=dev)
+                    ops.gemm(L.GEMM_NN, dc0_t, Wm[:, lw:], dsbar, B, sdim, s_out, ops.epilogue(out_mode=L.OUT_F32))
+                    sum_done = op.bcast_grad(dsbar, inv, ds_out, B, T, side)
                 else:
-                    _dense_pool_bwd(dsb, B, T, Wn, ds_out)
-            if mode == "SummaryMixing-fast":
-                if fuse_local:
-                    # dg[:, :l] already holds dZ (and db[:l] is done): finish the summary columns in place
-                    z_g, mk_g = sv_g[-1][1], sv_g[-1][2]
-                    if (z_g is not None or mk_g is not None) and not sum_done:
-                        ops.act_mask_bwd(ds_out, z_g[:, l:] if z_g is not None else None, mk_g,
-                                         act if z_g is not None else L.ACT_NONE, 1.0, ds_out, None)
-                if ln is not None:
-                    return mlp_bwd(dg, P["global_proj"], act, sv_g, dtype, dz_ready=fuse_local, res_grad=ln_res, ln=ln,
-                                   ln_second=ln_second)
-                dx = mlp_bwd(dg, P["global_proj"], act, sv_g, dtype, dz_ready=fuse_local)
-            else:
-                dx = mlp_bwd(dlocal_out, P["local_proj"], act, sv_l, dtype, dz_ready=fuse_local)
+                    if gWm is not None:      # dW_s += dzm^T sbar
+                        ops.wgrad(dzm, sbar_t, gWm[:, lw:], N, s_out, sdim)
+                    dsb = torch.empty((N, sdim), dtype=dtype, device=dev)
+                    ops.gemm(L.GEMM_NN, dzm, Wm[:, lw:], dsb, N, sdim, s_out, None)
+                    op.pool(dsb, ds_out, B, T, reverse=True)
+            if not fast:
+                dx = mlp_bwd(dlocal_out, lproj, act, sv_lp, dtype, dz_ready=fuse_local)
                 dx = mlp_bwd(ds_out, P["summary_proj"], act, sv_s, dtype, res_grad=dx, dz_ready=sum_done)
-            return dx.view(B, T, -1)
-        bwd.can_fuse_ln = (mode == "SummaryMixing-fast" and len(P["global_proj"]) == 1 and P["global_proj"][0]["kind"] == "linear")
+                return dx.view(B, T, -1)
+            if side is not None and not sum_done:
+                # dg[:, :l] already holds dZ (and db[:l] is done): finish the summary columns in place
+                ops.act_mask_bwd(ds_out, side[0], side[1], act if side[0] is not None else L.ACT_NONE, 1.0, ds_out, None)
+            if ln is not None:
+                return mlp_bwd(dg, lproj, act, sv_lp, dtype, dz_ready=fuse_local, res_grad=ln_res, ln=ln, ln_second=ln_second)
+            return mlp_bwd(dg, lproj, act, sv_lp, dtype, dz_ready=fuse_local).view(B, T, -1)
+        bwd.can_fuse_ln = fast and len(lproj) == 1 and lproj[0]["kind"] == "linear"
         if bwd.can_fuse_ln:      # the dgrad that would carry the LayerNorm backward: dX = dG (N x 2l) W_g - what ln_fusable must check
-            bwd.ln_reduce, bwd.ln_W = P["global_proj"][0]["W"].shape[0], wcast(P["global_proj"][0]["W"], dtype)
+            bwd.ln_reduce, bwd.ln_W = lproj[0]["W"].shape[0], wcast(lproj[0]["W"], dtype)
         # what the cell does first to its incoming gradient: dy * act'(zm) (a producer that can, writes it as a second output)
         bwd.pre = (1.0, None, None, zm, act) if (zm is not None and act != L.ACT_NONE) else None
         return (y3, bwd, post) if ln_next is not None else (y3, bwd)
