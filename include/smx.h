@@ -572,6 +572,38 @@ int smx_transducer_gemm_grad(int dtype, const void* H, const void* W, const floa
                              const float* gb, const float* gy, int B, int T, int U1, int J, int V, int blank, int row0, int nrows,
                              void* dz, int64_t lddz, void* stream);
 
+/* ---- Transducer prediction network (recipe keys `emb`, `dec`, recipes/LibriSpeech/ASR/transducer/hparams/
+ * conformer_summarymixing_transducer.yaml:301-310: speechbrain.nnet.embedding.Embedding(consider_as_one_hot) and
+ * speechbrain.nnet.RNN.LSTM, one layer, unidirectional, batch first; neither source is part of the reference tree - the yardstick is
+ * torch.nn.LSTM).  Gate order i, f, g, o (torch's); G = 4 H gate columns.  Supported H: multiples of 32 in [32, 4096]
+ * (smx_lstm_ok; SMX_EUNSUPPORTED otherwise); B is free (rows are padded to the 16-row MFMA tile inside the kernels).
+ * One launch per time step on `stream`, nothing else: a captured call is a plain chain.  No atomics: bit-reproducible.
+ * lstm_fwd:  gates_u = Gx[b,u,:] + h_{u-1} W_hh^T; c_u = f c_{u-1} + i g; h_u = o tanh(c_u).  Gx (B, U, G) fp32 = the input
+ *            contribution with BOTH biases folded in (the dense route: smx_gemm with SMX_OUT_F32; the one-hot route:
+ *            smx_onehot_gates_fwd).  W_hh (G, H), h0 (B, H) or null, Y (B, U, H), hn (B, H): dtype; c0 (B, H) or null, cn (B, H):
+ *            fp32 - the cell state and the gate pre-activations never leave fp32, h is rounded to dtype where it is stored.
+ *            For a backward: Hprev (B, U, H) dtype <- h_{u-1} per step (the operand of the dW_hh product), gates (B, U, G) fp32 <-
+ *            the ACTIVATED gates, C (B, U, H) fp32 <- c_u; all three null for inference.  U = 1 with h0 / c0 is the decoding step.
+ * lstm_bwd:  BPTT from dY (B, U, H) dtype or null, dhn / dcn (B, H) fp32 or null.  W_hh^T (H, G) dtype.  -> dG (B, U, G) dtype (the
+ *            gradient of the gate pre-activations: dW_hh += dG^T Hprev, db += colsum dG, dX = dG W_ih through the ordinary GEMM
+ *            routes), dh0 and dc0 (B, H) fp32.
+ * onehot_rows: Y (rows, V - 1) = the one-hot rows of the int32 tokens with the blank's column removed: column col(k) = k below the
+ *            blank, k - 1 above it; the blank (and any token outside [0, V)) gives a zero row.
+ * onehot_gates_fwd: Gx[r,:] = keep[r] WihT[col(token[r]),:] + bias; WihT (V - 1, G) = W_ih^T in dtype, bias (G) fp32 = b_ih + b_hh,
+ *            keep (rows) fp32 per-token factors (0 or 1/(1-p)) or null.  No one-hot tensor is written.
+ * onehot_gates_wgrad: dW_ih (G, V - 1; fp32, leading dimension lddw) [:, col(token[r])] += keep[r] dG[r,:], the rows of one token
+ *            summed in ascending order by the workgroup of its first row.  G %% 4 == 0. */
+int smx_lstm_ok(int dtype, int H);
+int smx_lstm_fwd(int dtype, const float* Gx, const void* Whh, const void* h0, const float* c0, void* Y, void* Hprev, float* gates,
+                 float* C, void* hn, float* cn, int B, int U, int H, void* stream);
+int smx_lstm_bwd(int dtype, const void* dY, const float* dhn, const float* dcn, const void* WhhT, const float* gates, const float* C,
+                 const float* c0, void* dG, float* dc0, float* dh0, int B, int U, int H, void* stream);
+int smx_onehot_rows(int dtype, const int32_t* tokens, void* Y, int64_t ldy, int rows, int V, int blank, void* stream);
+int smx_onehot_gates_fwd(int dtype, const int32_t* tokens, const float* keep, const void* WihT, int64_t ldw, const float* bias, float* Gx,
+                         int rows, int V, int blank, int G, void* stream);
+int smx_onehot_gates_wgrad(int dtype, const int32_t* tokens, const float* keep, const void* dG, int64_t lddg, float* dWih, int64_t lddw,
+                           int rows, int V, int blank, int G, void* stream);
+
 /* ---- Split-K over WORKGROUPS for the long reductions of a small batch (round 6; the recipe's 10 x 375 frames) -------------------
  * smx_gemm_panel_slabs: slab[s] (N x M, float32) = A[:, s K : (s + 1) K] . W_s^T for s < nslice on the panel-resident kernel
  *   (A (N, nslice K) bf16; Wpacked = nslice consecutive smx_weight_pack images, image s = the weight's K-slice s, packed WITHOUT a bias;

@@ -193,6 +193,12 @@ SIGNATURES = {
     "smx_transducer_gemm_stats": (c_i, [c_i, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "smx_transducer_gemm_grad": (c_i, [c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_vp,
                                        c_i64, c_vp]),
+    "smx_lstm_ok": (c_i, [c_i, c_i]),
+    "smx_lstm_fwd": (c_i, [c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_vp]),
+    "smx_lstm_bwd": (c_i, [c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_vp]),
+    "smx_onehot_rows": (c_i, [c_i, c_vp, c_vp, c_i64, c_i, c_i, c_i, c_vp]),
+    "smx_onehot_gates_fwd": (c_i, [c_i, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i, c_i, c_i, c_i, c_vp]),
+    "smx_onehot_gates_wgrad": (c_i, [c_i, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i, c_i, c_i, c_i, c_vp]),
     "smx_get_config": (c_i, [c_vp]),
     "smx_gemm_ln_tile_rows": (c_i, []),
     "smx_gemm_ln_tile_rows_for": (c_i, [c_i, c_i]),

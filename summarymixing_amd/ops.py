@@ -969,6 +969,94 @@ def transducer_gemm_grad(H2, W, bias, targets, lse, gb, gy, B, T, U1, blank, row
     return dz
 
 
+# ---- prediction network (csrc/lstm.hip): one-hot Embedding rows, the one-hot input route of the LSTM, the recurrence and its BPTT.
+def _tokens_i32(tokens):
+    assert tokens.is_cuda, "summarymixing_amd kernels run on the GPU only (no CPU fallback)"
+    return tokens.reshape(-1).to(torch.int32).contiguous()
+
+
+def lstm_ok(dtype, H):
+    return bool(L.lib().smx_lstm_ok(_DT[dtype], H))
+
+
+def onehot_rows(tokens, V, blank, dtype):
+    """tokens (...) integer -> (..., V - 1) one-hot rows without the blank's column (the blank: a zero row)."""
+    tk = _tokens_i32(tokens)
+    Y = torch.empty((tk.numel(), V - 1), dtype=dtype, device=tk.device)
+    L.check(L.lib().smx_onehot_rows(_DT[dtype], _p(tk), _p(Y), V - 1, tk.numel(), V, blank, _stream()), "smx_onehot_rows")
+    return Y.view(*tokens.shape, V - 1)
+
+
+def token_keep(n, p, seed, device):
+    """The n per-token factors (0 or 1 / (1 - p), fp32) of the prediction network's embedding dropout for `seed`: smx_dropout on a
+    column of ones, so mask index = token index (and the device step counter applies as to every dropout)."""
+    return dropout(torch.ones((n, 1), dtype=torch.float32, device=device), p, seed).view(n)
+
+
+def onehot_gates_fwd(tk32, keep, WihT, bias, V, blank):
+    """tk32 (rows) int32, WihT (V - 1, G) = W_ih^T, bias (G) fp32, keep (rows) fp32 or None -> Gx (rows, G) fp32."""
+    rows, G = tk32.numel(), WihT.shape[1]
+    Gx = torch.empty((rows, G), dtype=torch.float32, device=tk32.device)
+    pw, ldw = _mat(WihT)
+    tok = _pb(f"onehot_gates_fwd ({rows}x{G})", rows * G * (4 + _es(WihT)))
+    L.check(L.lib().smx_onehot_gates_fwd(dt(WihT), _p(tk32), _p(keep), pw, ldw, _p(bias), _p(Gx), rows, V, blank, G, _stream()),
+            "smx_onehot_gates_fwd")
+    _pe(tok)
+    return Gx
+
+
+def onehot_gates_wgrad(tk32, keep, dG, gW, V, blank):
+    """gW (G, V - 1) fp32 [:, col(token[r])] += keep[r] dG[r, :], a fixed order per column (bit-reproducible)."""
+    rows, G = dG.shape
+    pg, ldg = _mat(dG)
+    pw, ldw = _mat(gW)
+    assert gW.dtype == torch.float32 and gW.shape == (G, V - 1)
+    tok = _pb(f"onehot_gates_wgrad ({rows}x{G})", rows * G * (4 + _es(dG)))
+    L.check(L.lib().smx_onehot_gates_wgrad(dt(dG), _p(tk32), _p(keep), pg, ldg, pw, ldw, rows, V, blank, G, _stream()),
+            "smx_onehot_gates_wgrad")
+    _pe(tok)
+
+
+def lstm_fwd(Gx, Whh, h0, c0, B, U, save):
+    """Gx (B U, 4H) fp32, W_hh (4H, H), h0 (B, H) in W_hh's dtype or None, c0 (B, H) fp32 or None -> (Y (B, U, H), hn (B, H), cn (B, H)
+    fp32, saved); saved = (Hprev, gates, C) when `save`, else None."""
+    H = Whh.shape[1]
+    dev, T = Whh.device, Whh.dtype
+    assert Gx.dtype == torch.float32 and Gx.is_contiguous() and Gx.shape == (B * U, 4 * H) and Whh.is_contiguous()
+    assert (h0 is None or (h0.dtype == T and h0.is_contiguous())) and (c0 is None or (c0.dtype == torch.float32 and c0.is_contiguous()))
+    Y = torch.empty((B, U, H), dtype=T, device=dev)
+    hn = torch.empty((B, H), dtype=T, device=dev)
+    cn = torch.empty((B, H), dtype=torch.float32, device=dev)
+    saved = None
+    if save:
+        saved = (torch.empty((B, U, H), dtype=T, device=dev), torch.empty((B, U, 4 * H), dtype=torch.float32, device=dev),
+                 torch.empty((B, U, H), dtype=torch.float32, device=dev))
+    sv = saved or (None, None, None)
+    tok = _pb(f"lstm_fwd {'bf16' if T == torch.bfloat16 else 'f32'} (B {B}, U {U}, H {H})", U * 4 * H * H * _es(Whh) + B * U * H * 36,
+              2.0 * B * U * 4 * H * H)
+    L.check(L.lib().smx_lstm_fwd(_DT[T], _p(Gx), _p(Whh), _p(h0), _p(c0), _p(Y), _p(sv[0]), _p(sv[1]), _p(sv[2]), _p(hn), _p(cn),
+                                 B, U, H, _stream()), "smx_lstm_fwd")
+    _pe(tok)
+    return Y, hn, cn, saved
+
+
+def lstm_bwd(dY, dhn, dcn, WhhT, gates, C, c0, B, U):
+    """dY (B, U, H) in W_hh's dtype or None, dhn / dcn (B, H) fp32 or None, WhhT (H, 4H) -> (dG (B U, 4H), dh0, dc0 (B, H) fp32)."""
+    H = WhhT.shape[0]
+    dev, T = WhhT.device, WhhT.dtype
+    assert WhhT.is_contiguous() and (dY is None or (dY.dtype == T and dY.is_contiguous()))
+    assert all(t is None or (t.dtype == torch.float32 and t.is_contiguous()) for t in (dhn, dcn, c0))
+    dG = torch.empty((B * U, 4 * H), dtype=T, device=dev)
+    dh0 = torch.empty((B, H), dtype=torch.float32, device=dev)
+    dc0 = torch.empty((B, H), dtype=torch.float32, device=dev)
+    tok = _pb(f"lstm_bwd {'bf16' if T == torch.bfloat16 else 'f32'} (B {B}, U {U}, H {H})", U * 4 * H * H * _es(WhhT) + B * U * H * 40,
+              2.0 * B * U * 4 * H * H)
+    L.check(L.lib().smx_lstm_bwd(_DT[T], _p(dY), _p(dhn), _p(dcn), _p(WhhT), _p(gates), _p(C), _p(c0), _p(dG), _p(dc0), _p(dh0),
+                                 B, U, H, _stream()), "smx_lstm_bwd")
+    _pe(tok)
+    return dG, dh0, dc0
+
+
 _CSGU_DROP_FUSE = True   # (round 4: A/B knob SMX_CSGU_DROP_FUSE removed)     # (read once, like the library's own knobs)
 _STEP_COUNTER = None          # the training loop's device step counter (held HERE, in the Python host; libsmx has no such state)
 
