@@ -604,6 +604,38 @@ int smx_onehot_gates_fwd(int dtype, const int32_t* tokens, const float* keep, co
 int smx_onehot_gates_wgrad(int dtype, const int32_t* tokens, const float* keep, const void* dG, int64_t lddg, float* dWih, int64_t lddw,
                            int rows, int V, int blank, int G, void* stream);
 
+/* ---- Greedy transducer decoding (recipe key `Greedysearcher`, recipes/LibriSpeech/ASR/transducer/hparams/
+ * conformer_summarymixing_transducer.yaml:375-381: speechbrain.decoders.transducer.TransducerBeamSearcher with beam_size 1; its source
+ * is not part of the reference tree - the semantics below are SpeechBrain's transducer_greedy_decode written from memory, the
+ * yardstick is a float64 restatement of them).  At most one symbol per frame.  Per row b and frame t:
+ *   a = act(enc[b,t,:] + pdec[b,:]) (fp32, rounded to dtype);  z = a W_lin^T + b_lin (fp32, never stored);  k = argmax z, the lowest
+ *   index on a tie;  k != blank: append k, logp += z[k] - logsumexp(z), one LSTM step on token k (the W_ih^T row gather of
+ *   smx_onehot_gates_fwd; c fp32, h rounded to dtype) and pdec = h W_proj^T;  k == blank: the row's state is untouched.
+ * Supported (smx_greedy_ok; SMX_EUNSUPPORTED otherwise): H as smx_lstm_ok, J a multiple of 64 in [64, 832], V >= 2; B is free.
+ * Three launches per frame on `stream`, the same three whatever the data (logit partials per 128-column tile; select + masked LSTM
+ * step; pdec), plus one that clears the outputs: no host synchronisation, no copy to the host, no atomics - a captured call is a
+ * plain chain, values are bit-reproducible, and a row's values do not depend on B or on the other rows.
+ * State per row: h (B, H) dtype, c (B, H) fp32, pdec (B, J) dtype, frames_seen (B) int32.  Decoding enc[:, :T1] and then
+ * enc[:, T1:] on the same state equals decoding enc in one call, bit for bit.
+ * greedy_start:  the state before the first frame: one LSTM step from h = c = 0 on the blank (the embedding's zero row: the gates
+ *            are `bias` alone), pdec = h W_proj^T, frames_seen = 0.
+ * greedy_decode: enc[b,t,:] at enc + b ld_b + t ld_t elements (both strides multiples of 16 bytes); in_len (B) int32: the frames
+ *            of THIS call's enc that count per row (frames at or beyond it emit nothing and leave the row's state alone), or null:
+ *            all T.  WihT (V - 1, 4H; leading dimension ldw) and bias (4H) fp32 = b_ih + b_hh exactly as smx_onehot_gates_fwd takes
+ *            them; Whh (4H, H), Wproj (J, H), Wlin (V, J): dtype; blin (V) fp32 or null.  h_alt (B, H) dtype: the other half of h's
+ *            double buffer (workgroups read h while others write the frame's new h), caller-owned, contents undefined on return;
+ *            the final state is always in h.  Outputs: tokens (B, T) int32 padded with -1, frames (B, T) int32 (the row's frame
+ *            count at each emission, counted from greedy_start across calls; padded with -1), n_tok (B) int32, logp (B) fp32 - ADDED
+ *            into, so a stream keeps its running score.  workspace: smx_greedy_workspace(B, V) bytes, 16-byte aligned. */
+int smx_greedy_ok(int dtype, int H, int J, int V);
+size_t smx_greedy_workspace(int B, int V);
+int smx_greedy_start(int dtype, const float* bias, const void* Wproj, void* h, float* c, void* pdec, int32_t* frames_seen, int B, int H,
+                     int J, void* stream);
+int smx_greedy_decode(int dtype, const void* enc, int64_t ld_b, int64_t ld_t, const int32_t* in_len, const void* WihT, int64_t ldw,
+                      const float* bias, const void* Whh, const void* Wproj, const void* Wlin, const float* blin, void* h, void* h_alt,
+                      float* c, void* pdec, int32_t* frames_seen, int32_t* tokens, int32_t* frames, int32_t* n_tok, float* logp, int B,
+                      int T, int H, int J, int V, int act, int blank, void* workspace, void* stream);
+
 /* ---- Split-K over WORKGROUPS for the long reductions of a small batch (round 6; the recipe's 10 x 375 frames) -------------------
  * smx_gemm_panel_slabs: slab[s] (N x M, float32) = A[:, s K : (s + 1) K] . W_s^T for s < nslice on the panel-resident kernel
  *   (A (N, nslice K) bf16; Wpacked = nslice consecutive smx_weight_pack images, image s = the weight's K-slice s, packed WITHOUT a bias;

@@ -199,6 +199,11 @@ SIGNATURES = {
     "smx_onehot_rows": (c_i, [c_i, c_vp, c_vp, c_i64, c_i, c_i, c_i, c_vp]),
     "smx_onehot_gates_fwd": (c_i, [c_i, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i, c_i, c_i, c_i, c_vp]),
     "smx_onehot_gates_wgrad": (c_i, [c_i, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i, c_i, c_i, c_i, c_vp]),
+    "smx_greedy_ok": (c_i, [c_i, c_i, c_i, c_i]),
+    "smx_greedy_workspace": (c_sz, [c_i, c_i]),
+    "smx_greedy_start": (c_i, [c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_vp]),
+    "smx_greedy_decode": (c_i, [c_i, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_vp, c_vp]),
     "smx_get_config": (c_i, [c_vp]),
     "smx_gemm_ln_tile_rows": (c_i, []),
     "smx_gemm_ln_tile_rows_for": (c_i, [c_i, c_i]),

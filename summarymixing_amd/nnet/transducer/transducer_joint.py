@@ -28,7 +28,7 @@ def joint_inputs(tjoint, input_TN, input_PN):
     """Validate the recipe's 4-D training form and return the contiguous (B, T, J) / (B, U1, J) views (raises before any launch)."""
     if input_TN.dim() != 4 or input_PN.dim() != 4:
         raise NotImplementedError("Transducer_joint: only the 4-D training form (B, T, 1, J) + (B, 1, U+1, J) is implemented "
-                                  "(the 1-D decoding form belongs to greedy / beam search, which is out of scope)")
+                                  "(the 1-D decoding form is not called: greedy decoding runs in nnet.transducer.greedy_decode, beam search is not built)")
     B, T, one_t, J = input_TN.shape
     if one_t != 1 or input_PN.shape[1] != 1 or input_PN.shape[0] != B or input_PN.shape[3] != J:
         raise ValueError(f"Transducer_joint: expected (B, T, 1, J) and (B, 1, U+1, J), got {tuple(input_TN.shape)} and "

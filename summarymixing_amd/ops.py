@@ -1057,6 +1057,51 @@ def lstm_bwd(dY, dhn, dcn, WhhT, gates, C, c0, B, U):
     return dG, dh0, dc0
 
 
+# ---- greedy transducer decoding (csrc/greedy.hip).  Everything stays on the device: no call here synchronises with the host.
+def greedy_ok(dtype, H, J, V):
+    return dtype in _DT and bool(L.lib().smx_greedy_ok(_DT[dtype], H, J, V))
+
+
+def greedy_start(bias, Wproj, B):
+    """bias (4H) fp32 = b_ih + b_hh, W_proj (J, H) -> the state before the first frame: (h (B, H), c (B, H) fp32, pdec (B, J),
+    frames_seen (B) int32 zeros)."""
+    J, H = Wproj.shape
+    dev, T = Wproj.device, Wproj.dtype
+    assert bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == 4 * H and Wproj.is_contiguous()
+    h = torch.empty((B, H), dtype=T, device=dev)
+    c = torch.empty((B, H), dtype=torch.float32, device=dev)
+    pdec = torch.empty((B, J), dtype=T, device=dev)
+    seen = torch.empty((B,), dtype=torch.int32, device=dev)
+    L.check(L.lib().smx_greedy_start(_DT[T], _p(bias), _p(Wproj), _p(h), _p(c), _p(pdec), _p(seen), B, H, J, _stream()), "smx_greedy_start")
+    return h, c, pdec, seen
+
+
+def greedy_decode(enc, in_len, WihT, bias, Whh, Wproj, Wlin, blin, state, logp, act, blank):
+    """enc (B, T, J) with unit stride along J; in_len (B) int32 or None; state = (h, c, pdec, frames_seen), updated IN PLACE; logp (B)
+    fp32, added into -> (tokens (B, T) int32 padded with -1, frames (B, T) int32, n_tok (B) int32)."""
+    B, T, J = enc.shape
+    h, c, pdec, seen = state
+    H, V = Whh.shape[1], Wlin.shape[0]
+    dev, DT = enc.device, enc.dtype
+    assert enc.is_cuda, "summarymixing_amd kernels run on the GPU only (no CPU fallback)"
+    assert all(w.dtype == DT and w.is_contiguous() for w in (Whh, Wproj, Wlin, h, pdec)) and WihT.dtype == DT and WihT.stride(1) == 1
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in (bias, c, logp) + ((blin,) if blin is not None else ()))
+    assert seen.dtype == torch.int32 and (in_len is None or (in_len.dtype == torch.int32 and in_len.is_contiguous()))
+    assert h.shape == (B, H) and c.shape == (B, H) and pdec.shape == (B, J) and WihT.shape == (V - 1, 4 * H) and Wlin.shape[1] == J
+    tokens = torch.empty((B, T), dtype=torch.int32, device=dev)
+    frames = torch.empty((B, T), dtype=torch.int32, device=dev)
+    n_tok = torch.empty((B,), dtype=torch.int32, device=dev)
+    h_alt = torch.empty_like(h)
+    ws = _workspace(L.lib().smx_greedy_workspace(B, V), dev, "greedy")
+    tok = _pb(f"greedy_decode {'bf16' if DT == torch.bfloat16 else 'f32'} (B {B}, T {T}, V {V}, H {H}, J {J})",
+              T * (V * J + 4 * H * H + J * H) * _es(enc), 2.0 * B * T * (V * J + 4 * H * H + J * H))
+    L.check(L.lib().smx_greedy_decode(_DT[DT], _p(enc), enc.stride(0), enc.stride(1), _p(in_len), _p(WihT), WihT.stride(0), _p(bias),
+                                      _p(Whh), _p(Wproj), _p(Wlin), _p(blin), _p(h), _p(h_alt), _p(c), _p(pdec), _p(seen), _p(tokens),
+                                      _p(frames), _p(n_tok), _p(logp), B, T, H, J, V, act, blank, _p(ws), _stream()), "smx_greedy_decode")
+    _pe(tok)
+    return tokens, frames, n_tok
+
+
 _CSGU_DROP_FUSE = True   # (round 4: A/B knob SMX_CSGU_DROP_FUSE removed)     # (read once, like the library's own knobs)
 _STEP_COUNTER = None          # the training loop's device step counter (held HERE, in the Python host; libsmx has no such state)
 

@@ -1,0 +1,256 @@
+"""Greedy transducer decoding on the GPU (csrc/greedy.hip behind nnet.transducer.greedy_decode, CapturedGreedy and
+decoders.transducer.TransducerBeamSearcher) against the float64 restatement tests/_greedy_ref.py on the same, dtype-rounded
+parameters and inputs.
+
+float32 decodes the reference's exact sequence on cases the CPU suite proves admissible (test_greedy_cpu.py: the reference's smallest
+gap >= 8 x the fp32 emulation's largest logit deviation).  A free-running bf16 decode cannot be asked that (its deviations exceed
+the gaps), so both dtypes are also judged on a FORCED trajectory: the reference replays the GPU's own sequence and every choice the
+GPU made must be within `bar` of the reference's best logit at that frame, bar = max(TOL, 4 x floor), the floor being the emulation's
+deviation on that same trajectory - measured on the CPU, never from the code under test.  Everything else is bit equality."""
+import pytest
+import torch
+
+from tests import _greedy_ref as R
+from tests._util import TOL, report
+
+pytestmark = pytest.mark.gpu
+
+F32, BF16 = torch.float32, torch.bfloat16
+ALL = ("small", "blank7", "two_tiles", "one_frame", "long", "recipe", "v300", "t8", "tie")
+
+
+def _mods(p, blank):
+    from summarymixing_amd.nnet.embedding import Embedding
+    from summarymixing_amd.nnet.linear import Linear
+    from summarymixing_amd.nnet.RNN import LSTM
+    from summarymixing_amd.nnet.transducer import Transducer_joint
+    V, J = p["w_lin"].shape
+    H = p["w_hh"].shape[1]
+    emb, dec, proj = Embedding(V, consider_as_one_hot=True, blank_id=blank), LSTM(H, input_size=V - 1), Linear(J, input_size=H, bias=False)
+    tj, lin = Transducer_joint(joint="sum", nonlinearity=torch.nn.GELU), Linear(V, input_size=J)
+    with torch.no_grad():
+        dec.rnn.weight_ih_l0.copy_(p["w_ih"]); dec.rnn.weight_hh_l0.copy_(p["w_hh"])
+        dec.rnn.bias_ih_l0.copy_(p["b_ih"]); dec.rnn.bias_hh_l0.copy_(p["b_hh"])
+        proj.w.weight.copy_(p["w_proj"]); lin.w.weight.copy_(p["w_lin"]); lin.w.bias.copy_(p["b_lin"])
+    return tuple(m.cuda() for m in (emb, dec, proj, tj, lin))
+
+
+_cache = {}
+
+
+def _setup(name, dtype=F32):
+    """(modules on the GPU, enc on the GPU in dtype, params, enc on the CPU, blank) of a named case, built once."""
+    if (name, dtype) not in _cache:
+        p, enc, blank = R.case(name, dtype)
+        _cache[(name, dtype)] = (_mods(p, blank), enc.cuda().to(dtype), p, enc, blank)
+    return _cache[(name, dtype)]
+
+
+def _decode(name, dtype=F32, **kw):
+    from summarymixing_amd.nnet.transducer import greedy_decode
+    mods, enc, p, enc_cpu, blank = _setup(name, dtype)
+    return greedy_decode(enc, *mods, **kw)
+
+
+def _lists(r):
+    """(hyps, frames) as lists of lists, one host copy each."""
+    tk, fr, n = r.tokens.cpu(), r.frames.cpu(), r.counts.cpu()
+    assert bool(((tk >= 0) == (torch.arange(tk.shape[1]).view(1, -1) < n.view(-1, 1))).all()), "tokens are not padded with -1 after counts"
+    return [tk[b, :n[b]].tolist() for b in range(len(n))], [fr[b, :n[b]].tolist() for b in range(len(n))]
+
+
+def _same_state(a, b):
+    return all(torch.equal(x, y) for x, y in zip(a, b))
+
+
+def _same(a, b):
+    return (torch.equal(a.tokens, b.tokens) and torch.equal(a.frames, b.frames) and torch.equal(a.counts, b.counts)
+            and torch.equal(a.scores, b.scores) and _same_state(a.state, b.state))
+
+
+# ---- 1. float32, free-running: the reference's exact sequence
+@pytest.mark.parametrize("name", R.EXACT + ("tie",))
+def test_fp32_decodes_the_reference_sequence(name):
+    mods, enc, p, enc_cpu, blank = _setup(name)
+    ref = R.decode(p, enc_cpu, blank)
+    r = _decode(name)
+    hyps, frames = _lists(r)
+    assert hyps == ref["hyps"] and frames == ref["frames"] and r.counts.cpu().tolist() == ref["n"].tolist()
+    err = float((r.scores.cpu().double() - ref["scores"]).abs().max() / ref["scores"].abs().max().clamp(min=1e-30))
+    report(f"greedy_fp32_free[{name}]", {"score_rel_err": err, "bar": TOL[F32][0], "tokens": int(ref["n"].sum())})
+    assert err <= TOL[F32][0], err
+    assert torch.equal(r.state.frames_seen.cpu(), torch.full_like(r.state.frames_seen.cpu(), enc.shape[1]))
+    if name == "tie":
+        assert sum(h.count(R.TIE[7]) for h in hyps) >= 2 and sum(h.count(R.TIE[8]) for h in hyps) == 0
+
+
+# ---- 2. both dtypes, forced trajectory
+@pytest.mark.parametrize("dtype", [F32, BF16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("name", ALL)
+def test_every_choice_is_within_the_bar_of_the_reference_best(name, dtype):
+    mods, enc, p, enc_cpu, blank = _setup(name, dtype)
+    r = _decode(name, dtype)
+    hyps, frames = _lists(r)
+    B, T = enc.shape[:2]
+    choice = R.choice_from(hyps, frames, [len(h) for h in hyps], [0] * B, T, blank)
+    ref, emu = R.ref_and_emu(p, enc_cpu, blank, dtype, forced=choice)
+    assert ref["hyps"] == hyps and ref["frames"] == frames                    # (the replay took the GPU's trajectory)
+    floor = max(R.deviation(ref, emu))
+    bar = max(TOL[dtype][0], 4 * floor)
+    z = ref["z"]
+    zmax = float(z.abs().max())
+    short = (z.max(-1).values - z.gather(2, choice.unsqueeze(-1)).squeeze(-1)) / zmax       # (B, T), >= 0; every frame, nothing left out
+    serr = float((r.scores.cpu().double() - ref["scores"]).abs().max() / ref["scores"].abs().max().clamp(min=1e-30))
+    report(f"greedy_forced[{name}-{'bf16' if dtype == BF16 else 'f32'}]",
+           {"choice_shortfall": float(short.max()), "score_rel_err": serr, "floor": floor, "bar": bar})
+    assert float(short.max()) <= bar, (float(short.max()), bar)
+    assert serr <= bar, (serr, bar)
+
+
+# ---- 3. chunked == whole, bit for bit
+@pytest.mark.parametrize("dtype", [F32, BF16], ids=["f32", "bf16"])
+@pytest.mark.parametrize("name,splits", [("small", (1, 7, 16)), ("t8", (1,) * 8)])
+def test_chunked_equals_whole(name, splits, dtype):
+    from summarymixing_amd.nnet.transducer import greedy_decode
+    mods, enc, p, enc_cpu, blank = _setup(name, dtype)
+    whole = greedy_decode(enc, *mods)
+    hw, fw = _lists(whole)
+    B = enc.shape[0]
+    hyps, frames, state, t0 = [[] for _ in range(B)], [[] for _ in range(B)], None, 0
+    for n in splits:
+        r = greedy_decode(enc[:, t0:t0 + n], *mods, state=state)
+        h, f = _lists(r)
+        for b in range(B):
+            hyps[b] += h[b]; frames[b] += f[b]
+        state, t0 = r.state, t0 + n
+    assert t0 == enc.shape[1] and hyps == hw and frames == fw
+    assert torch.equal(r.scores, whole.scores) and _same_state(state, whole.state)
+
+
+# ---- 4. lengths
+@pytest.mark.parametrize("dtype", [F32, BF16], ids=["f32", "bf16"])
+def test_lengths_stop_a_row_where_its_frames_end(dtype):
+    from summarymixing_amd.nnet.transducer import greedy_decode
+    mods, enc, p, enc_cpu, blank = _setup("small", dtype)
+    T = enc.shape[1]
+    r = greedy_decode(enc, *mods, lengths=torch.tensor([1.0, 7 / T, 0.0]))
+    whole = greedy_decode(enc, *mods)
+    alone = greedy_decode(enc[1:2, :7], *mods)
+    h, f = _lists(r)
+    hw, fw = _lists(whole)
+    ha, fa = _lists(alone)
+    assert h[0] == hw[0] and f[0] == fw[0] and h[1] == ha[0] and f[1] == fa[0] and h[2] == [] and len(ha[0]) > 0
+    assert torch.equal(r.scores[1:2], alone.scores) and all(torch.equal(x[1:2], y) for x, y in zip(r.state, alone.state))
+    assert r.state.frames_seen.cpu().tolist() == [T, 7, 0] and float(r.scores[2]) == 0.0
+    start = greedy_decode(enc[2:3], *mods, lengths=torch.tensor([0.0])).state
+    zero = torch.zeros_like(start.h)
+    assert all(torch.equal(x[2:3], y) for x, y in zip(r.state, start)) and not torch.equal(start.h, zero)
+    ref_h = R.start_state(p, 1, torch.float64)[0]
+    assert float((start.h.cpu().double() - ref_h).abs().max()) <= TOL[dtype][0] * float(ref_h.abs().max())
+
+
+# ---- 5. row independence
+@pytest.mark.parametrize("dtype", [F32, BF16], ids=["f32", "bf16"])
+def test_a_row_decodes_the_same_alone(dtype):
+    from summarymixing_amd.nnet.transducer import greedy_decode
+    mods, enc, p, enc_cpu, blank = _setup("two_tiles", dtype)
+    whole = greedy_decode(enc, *mods)
+    for b in range(enc.shape[0]):
+        one = greedy_decode(enc[b:b + 1], *mods)
+        assert (torch.equal(one.tokens, whole.tokens[b:b + 1]) and torch.equal(one.frames, whole.frames[b:b + 1])
+                and torch.equal(one.scores, whole.scores[b:b + 1]) and all(torch.equal(x, y[b:b + 1]) for x, y in zip(one.state, whole.state))), b
+
+
+# ---- 6. extremes
+def test_blank_bias_extremes():
+    from summarymixing_amd.nnet.transducer import greedy_decode
+    mods, enc, p, enc_cpu, blank = _setup("blank7")
+    B, T = enc.shape[:2]
+    start = greedy_decode(enc, *mods, lengths=torch.zeros(B)).state
+    for shift, want in ((1e4, 0), (-1e4, T)):
+        q = dict(p, b_lin=p["b_lin"].clone())
+        q["b_lin"][blank] = shift
+        r = greedy_decode(enc, *_mods(q, blank))
+        assert r.counts.cpu().tolist() == [want] * B
+        if want == 0:
+            assert all(torch.equal(x, y) for x, y in zip(r.state[:3], start[:3])) and float(r.scores.abs().max()) == 0.0
+            assert bool((r.tokens == -1).all()) and bool((r.frames == -1).all())
+        else:
+            assert bool((r.tokens != blank).all()) and bool((r.tokens >= 0).all())
+            assert torch.equal(r.frames.cpu(), torch.arange(T, dtype=torch.int32).expand(B, T))
+
+
+# ---- 7. reproducibility and capture
+@pytest.mark.parametrize("dtype", [F32, BF16], ids=["f32", "bf16"])
+def test_two_calls_and_a_captured_replay_give_the_same_bits(dtype):
+    from summarymixing_amd.nnet.transducer import CapturedGreedy, greedy_decode
+    mods, enc, p, enc_cpu, blank = _setup("small", dtype)
+    a, b = greedy_decode(enc, *mods), greedy_decode(enc, *mods)
+    assert _same(a, b) and int(a.counts.sum()) > 0
+    B, T = enc.shape[:2]
+    cap = CapturedGreedy(*mods, B=B, T=T, dtype=dtype)
+    assert _same(cap.decode(enc), a)
+    enc2 = enc.flip(1).contiguous()
+    want = greedy_decode(enc2, *mods)
+    assert _same(cap.decode(enc2), want) and not torch.equal(want.tokens, a.tokens)
+    assert _same(cap.decode(enc), a)
+
+
+# ---- 8. surface
+@pytest.mark.parametrize("dtype", [F32, BF16], ids=["f32", "bf16"])
+def test_searcher_returns_the_decoded_lists_and_the_documented_score(dtype):
+    from summarymixing_amd.decoders.transducer import TransducerBeamSearcher
+    mods, enc, p, enc_cpu, blank = _setup("blank7", dtype)
+    emb, dec, proj, tj, lin = mods
+    s = TransducerBeamSearcher(decode_network_lst=[emb, dec, proj], tjoint=tj, classifier_network=[lin], blank_id=blank, beam_size=1,
+                               nbest=1, lm_module=None, lm_weight=0.0, state_beam=2.3, expand_beam=2.3)
+    hyps, score, a3, a4 = s(enc)
+    r = _decode("blank7", dtype)
+    assert hyps == _lists(r)[0] and all(isinstance(k, int) for h in hyps for k in h) and a3 is None and a4 is None
+    assert abs(score - float(r.scores.exp().mean())) <= 1e-6 * abs(score) + 1e-30
+    with pytest.raises(RuntimeError, match="GPU only"):
+        s(enc.cpu())
+
+
+def test_unsupported_shapes_raise_before_any_launch():
+    from summarymixing_amd.nnet.transducer import greedy_decode
+    p, enc = R.make_case(1, 2, 12, 32, 96, 0, 0)
+    with pytest.raises(NotImplementedError):
+        greedy_decode(enc.cuda(), *_mods(p, 0))
+
+
+# ---- 9. against the merged training chain
+def test_the_training_lattice_walks_the_same_path():
+    """[blank] + hyp through prediction_network, Transducer_joint and transducer_lin gives the (B, T, U+1, V) lattice of the training
+    chain; walking it greedily on the host must take the decoder's path wherever the lattice's own smallest gap on the path is
+    >= 8 x its deviation from the fp64 reference - with an admissible case that is every frame, and the test asserts it is."""
+    from summarymixing_amd.nnet.transducer import prediction_network
+    name = "small"
+    mods, enc, p, enc_cpu, blank = _setup(name)
+    emb, dec, proj, tj, lin = mods
+    r = _decode(name)
+    hyps, frames = _lists(r)
+    ref = R.decode(p, enc_cpu, blank)
+    B, T = enc.shape[:2]
+    U = max(len(h) for h in hyps)
+    tb = torch.full((B, U + 1), blank, dtype=torch.long)
+    for b in range(B):
+        tb[b, 1:1 + len(hyps[b])] = torch.tensor(hyps[b], dtype=torch.long)
+    with torch.no_grad():
+        pn = prediction_network(tb.cuda(), emb, dec, proj)
+        lat = lin(tj(enc.unsqueeze(2), pn.unsqueeze(1))).cpu().double()          # (B, T, U+1, V)
+    checked = 0
+    for b in range(B):
+        u, walked = 0, []
+        for t in range(T):
+            z = lat[b, t, u]
+            top = torch.topk(z, 2).values
+            dev = float((z - ref["z"][b, t]).abs().max())
+            assert float(top[0] - top[1]) >= 8 * dev, (b, t, float(top[0] - top[1]), dev)
+            checked += 1
+            k = int(z.argmax())
+            if k != blank:
+                walked.append(k)
+                u += 1
+        assert walked == hyps[b], b
+    assert checked == B * T
