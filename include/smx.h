@@ -636,6 +636,31 @@ int smx_greedy_decode(int dtype, const void* enc, int64_t ld_b, int64_t ld_t, co
                       float* c, void* pdec, int32_t* frames_seen, int32_t* tokens, int32_t* frames, int32_t* n_tok, float* logp, int B,
                       int T, int H, int J, int V, int act, int blank, void* workspace, void* stream);
 
+/* ---- RNN language model (recipe key `lm_model`, recipes/LibriSpeech/ASR/transducer/hparams/
+ * conformer_summarymixing_transducer.yaml:340-349: speechbrain.lobes.models.RNNLM.RNNLM - a trainable Embedding table, a two-layer
+ * speechbrain.nnet.RNN.LSTM of 2048 units, one DNN block and an output Linear; none of these sources is part of the reference tree -
+ * the yardstick is torch.nn.Embedding / torch.nn.LSTM).  The decode step (U = 1, a few dozen rows, the state fed back) streams every
+ * LSTM weight once, so it is ONE launch per layer whose grid runs over hidden units only:
+ * lstm_step: gates[b,:] = bias + x_b W_ih^T + h[b,:] W_hh^T (fp32 sums, gate order i, f, g, o); c'[b] = f c[b] + i g; h'[b] = o tanh(c').
+ *            W_ih (4H, I) and W_hh (4H, H) in dtype exactly as torch.nn.LSTM stores them (no transposed image), bias (4H) fp32 =
+ *            b_ih + b_hh.  tok == null: x_b = row b of the dense X (B, I; leading dimension ldx, dtype).  tok (B) int32: X is a
+ *            (V, I; ldx) table in dtype and x_b = X[tok[b], :] AS STORED (a padding row is not special); a token outside [0, V) reads
+ *            as a zero row (smx_onehot_rows' convention).  h (B, H) dtype and c (B, H) fp32: the incoming state, each null = zeros;
+ *            h' (B, H) dtype and c' (B, H) fp32 are DISTINCT buffers (other workgroups read h, c and X while h', c' are written):
+ *            SMX_EINVAL if they overlap the inputs.  Supported (smx_lstm_step_ok; SMX_EUNSUPPORTED otherwise): H as smx_lstm_ok, I a
+ *            multiple of 32 in [32, 4096], ldx a multiple of 8, 16-byte aligned X / W_ih / W_hh / h; B is free: the 16-row batch
+ *            tiles are looped inside the workgroup that holds a 32-row weight tile (8 units x 4 gates), so no weight element is
+ *            fetched by two workgroups whatever B is, and H = 2048 launches 256 workgroups.  One launch on `stream`, nothing else (a
+ *            captured step is a plain chain); no atomics, every sum in a fixed order: bit-reproducible, and a row's values do not
+ *            depend on B or on the other rows.
+ * gather_rows: Y[r,:] = table[tok[r],:] in dtype (rows x D; table (V, D); leading dimensions ldt, ldy), zeros for a token outside
+ *            [0, V).  D, ldt and ldy multiples of 8 elements, 16-byte aligned bases. */
+int smx_lstm_step_ok(int dtype, int I, int H);
+int smx_lstm_step(int dtype, const void* X, int64_t ldx, const int32_t* tok, int V, const void* Wih, const void* Whh, const float* bias,
+                  const void* h, const float* c, void* h_out, float* c_out, int B, int I, int H, void* stream);
+int smx_gather_rows(int dtype, const int32_t* tok, const void* table, int64_t ldt, void* Y, int64_t ldy, int rows, int V, int D,
+                    void* stream);
+
 /* ---- Split-K over WORKGROUPS for the long reductions of a small batch (round 6; the recipe's 10 x 375 frames) -------------------
  * smx_gemm_panel_slabs: slab[s] (N x M, float32) = A[:, s K : (s + 1) K] . W_s^T for s < nslice on the panel-resident kernel
  *   (A (N, nslice K) bf16; Wpacked = nslice consecutive smx_weight_pack images, image s = the weight's K-slice s, packed WITHOUT a bias;

@@ -199,6 +199,9 @@ SIGNATURES = {
     "smx_onehot_rows": (c_i, [c_i, c_vp, c_vp, c_i64, c_i, c_i, c_i, c_vp]),
     "smx_onehot_gates_fwd": (c_i, [c_i, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i, c_i, c_i, c_i, c_vp]),
     "smx_onehot_gates_wgrad": (c_i, [c_i, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i, c_i, c_i, c_i, c_vp]),
+    "smx_lstm_step_ok": (c_i, [c_i, c_i, c_i]),
+    "smx_lstm_step": (c_i, [c_i, c_vp, c_i64, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_vp]),
+    "smx_gather_rows": (c_i, [c_i, c_vp, c_vp, c_i64, c_vp, c_i64, c_i, c_i, c_i, c_vp]),
     "smx_greedy_ok": (c_i, [c_i, c_i, c_i, c_i]),
     "smx_greedy_workspace": (c_sz, [c_i, c_i]),
     "smx_greedy_start": (c_i, [c_i, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_vp]),

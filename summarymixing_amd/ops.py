@@ -1057,6 +1057,49 @@ def lstm_bwd(dY, dhn, dcn, WhhT, gates, C, c0, B, U):
     return dG, dh0, dc0
 
 
+# ---- the RNN language model's decode step and table gather (csrc/lstm_step.hip)
+def lstm_step_ok(dtype, I, H):
+    return dtype in _DT and bool(L.lib().smx_lstm_step_ok(_DT[dtype], I, H))
+
+
+def lstm_step(x, Wih, Whh, bias, h, c, h_out=None, c_out=None, tokens=None):
+    """One LSTM-cell step in one launch (smx_lstm_step).  tokens None: x (B, I) dense rows (unit stride along I); tokens (B) int32: x is
+    the (V, I) table and row b of the input is x[tokens[b]] as stored (outside the table: zeros).  W_ih (4H, I), W_hh (4H, H) as
+    torch.nn.LSTM stores them, bias (4H) fp32 = b_ih + b_hh, h (B, H) in the weights' dtype or None, c (B, H) fp32 or None.
+    -> (h' (B, H), c' (B, H) fp32), written into h_out / c_out when given: buffers DISTINCT from h, c and x."""
+    H, I = Whh.shape[1], Wih.shape[1]
+    T, dev = Whh.dtype, Whh.device
+    assert Whh.is_cuda, "summarymixing_amd kernels run on the GPU only (no CPU fallback)"
+    assert Wih.dtype == T and x.dtype == T and Wih.is_contiguous() and Whh.is_contiguous() and Wih.shape[0] == 4 * H and x.shape[1] == I
+    assert bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == 4 * H
+    B = x.shape[0] if tokens is None else tokens.numel()
+    assert tokens is None or (tokens.dtype == torch.int32 and tokens.is_contiguous())
+    assert (h is None or (h.dtype == T and h.is_contiguous() and h.shape == (B, H)))
+    assert (c is None or (c.dtype == torch.float32 and c.is_contiguous() and c.shape == (B, H)))
+    if h_out is None:
+        h_out = torch.empty((B, H), dtype=T, device=dev)
+    if c_out is None:
+        c_out = torch.empty((B, H), dtype=torch.float32, device=dev)
+    assert h_out.dtype == T and h_out.is_contiguous() and c_out.dtype == torch.float32 and c_out.is_contiguous()
+    px, ldx = _mat(x)
+    tok = _pb(f"lstm_step {'bf16' if T == torch.bfloat16 else 'f32'} (B {B}, I {I}, H {H})", 4 * H * (I + H) * _es(Whh) + B * (I + 2 * H) * _es(Whh) + 8 * B * H,
+              2.0 * B * 4 * H * (I + H))
+    L.check(L.lib().smx_lstm_step(_DT[T], px, ldx, _p(tokens), x.shape[0] if tokens is not None else 0, _p(Wih), _p(Whh), _p(bias),
+                                  _p(h), _p(c), _p(h_out), _p(c_out), B, I, H, _stream()), "smx_lstm_step")
+    _pe(tok)
+    return h_out, c_out
+
+
+def gather_rows(tokens, table):
+    """tokens (...) integer, table (V, D) -> (..., D) = table[tokens] in the table's dtype (a token outside [0, V): a zero row)."""
+    tk = _tokens_i32(tokens)
+    V, D = table.shape
+    Y = torch.empty((tk.numel(), D), dtype=table.dtype, device=table.device)
+    pt, ldt = _mat(table)
+    L.check(L.lib().smx_gather_rows(dt(table), _p(tk), pt, ldt, _p(Y), D, tk.numel(), V, D, _stream()), "smx_gather_rows")
+    return Y.view(*tokens.shape, D)
+
+
 # ---- greedy transducer decoding (csrc/greedy.hip).  Everything stays on the device: no call here synchronises with the host.
 def greedy_ok(dtype, H, J, V):
     return dtype in _DT and bool(L.lib().smx_greedy_ok(_DT[dtype], H, J, V))
