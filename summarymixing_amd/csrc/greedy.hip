@@ -7,9 +7,10 @@
 //                            training joint stores H), times a 128-column slice of W_lin on the MFMA; per (row, tile) the tile's
 //                            max, its first argmax and sum exp(z - max).  z is never stored.
 //   2. greedy_step_kernel    every workgroup re-reduces the V / 128 partials of its 16 rows (k = argmax, lowest index on a tie; log-prob
-//                            = -log sum exp(z - z[k])), then the LSTM step of lstm.hip masked per row: rows that emit take
-//                            gates = W_ih^T[col(k)] + bias + h W_hh^T and a new (h, c), the others copy h.  h is double-buffered (other
-//                            workgroups read h_prev in the same launch).  The workgroup of hidden tile 0 appends (token, frame,
+//                            = -log sum exp(z - z[k])), then the LSTM step of lstm.hip masked per row, built from the same pieces of
+//                            lstm_tile.h (gate_tiles, onehot_gate_input with keep = 1, lstm_cell): rows that emit take a new (h, c)
+//                            - bit for bit what lstm.hip gives when the hypothesis is fed back through its one-hot route - and
+//                            the others copy h.  h is double-buffered (other workgroups read h_prev in the same launch).  The workgroup of hidden tile 0 appends (token, frame,
 //                            log-prob) and counts the frame.
 //   3. greedy_proj_kernel    pdec = h W_proj^T for all rows (idempotent for the rows that did not emit: no mask).
 // Batch rows beyond B of the last tile re-read row B - 1 and are never stored.  A row's values depend on that row alone: the
@@ -30,6 +31,16 @@ static int greedy_tiles(int V) { return (V + GREEDY_TILE_V - 1) / GREEDY_TILE_V;
 template <typename T> struct GreedyPad;           // a's LDS rows are 16 bytes longer than J elements (the rows start in different banks)
 template <> struct GreedyPad<float> { static constexpr int value = 4; };
 template <> struct GreedyPad<bf16_t> { static constexpr int value = 8; };
+
+// the (value, column) pairs of 16 neighbouring lanes meet: a higher value wins, the lower column on a tie; all 16 end with the winner
+__device__ __forceinline__ void argmax_meet16(float& m, int& k) {
+#pragma unroll
+  for (int off = 8; off > 0; off >>= 1) {
+    const float om = __shfl_xor(m, off, 16);
+    const int ok = __shfl_xor(k, off, 16);
+    if (om > m || (om == m && ok < k)) { m = om; k = ok; }
+  }
+}
 
 struct GreedyLogits {
   const void* enc; long ld_b, ld_t;     // enc[b,t,:] = enc + b ld_b + t ld_t
@@ -74,7 +85,7 @@ __global__ __launch_bounds__(256) void greedy_logits_kernel(GreedyLogits s) {
     for (int i = 0; i < 4; ++i) zt[q * 4 + i][c0 + r] = v < s.V ? acc[i] + bias : -INFINITY;
   }
   __syncthreads();
-  // 16 threads per row, 8 consecutive columns each, then the 16 meet: a higher value wins, the lower column on a tie
+  // 16 threads per row, 8 consecutive columns each, then the 16 meet
   const int bb = threadIdx.x >> 4, jj = threadIdx.x & 15;
   float m = zt[bb][jj * 8];
   int k = jj * 8;
@@ -83,12 +94,7 @@ __global__ __launch_bounds__(256) void greedy_logits_kernel(GreedyLogits s) {
     const float z = zt[bb][jj * 8 + i];
     if (z > m) { m = z; k = jj * 8 + i; }
   }
-#pragma unroll
-  for (int off = 8; off > 0; off >>= 1) {
-    const float om = __shfl_xor(m, off, 16);
-    const int ok = __shfl_xor(k, off, 16);
-    if (om > m || (om == m && ok < k)) { m = om; k = ok; }
-  }
+  argmax_meet16(m, k);
   float sum = 0.f;
 #pragma unroll
   for (int i = 0; i < 8; ++i) sum += __expf(zt[bb][jj * 8 + i] - m);
@@ -122,7 +128,6 @@ __global__ __launch_bounds__(256) void greedy_step_kernel(GreedyStep s) {
   __shared__ int s_k[16], s_emit[16], s_live[16];
   __shared__ float s_lp[16];
   const int H = s.H, j0 = blockIdx.x * 16, b0 = blockIdx.y * 16;
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
   const int bb = threadIdx.x >> 4, jj = threadIdx.x & 15, b = b0 + bb, j = j0 + jj;
   if (s.start) {
     if (jj == 0) { s_k[bb] = s.blank; s_emit[bb] = 1; s_live[bb] = 0; s_lp[bb] = 0.f; }
@@ -135,12 +140,7 @@ __global__ __launch_bounds__(256) void greedy_step_kernel(GreedyStep s) {
       const float om = s.pmax[o + t];
       if (t == jj || om > m) { m = om; k = s.parg[o + t]; }                  // (tiles ascend: a tie keeps the lower column)
     }
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) {
-      const float om = __shfl_xor(m, off, 16);
-      const int ok = __shfl_xor(k, off, 16);
-      if (om > m || (om == m && ok < k)) { m = om; k = ok; }
-    }
+    argmax_meet16(m, k);
     float sum = 0.f;
     for (int t = jj; t < s.NT; t += 16) sum += s.psum[o + t] * __expf(s.pmax[o + t] - m);
 #pragma unroll
@@ -158,33 +158,19 @@ __global__ __launch_bounds__(256) void greedy_step_kernel(GreedyStep s) {
 #pragma unroll
   for (int i = 0; i < 16; ++i) any |= s_emit[i];
   const T* hp = reinterpret_cast<const T*>(s.hp);
-  lstm_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  if (any && hp) {                                                            // (uniform; a frame of blanks reads no W_hh)
-    const T* a_row = hp + (long)min(b0 + r, s.B - 1) * H;
-    const T* b_row = reinterpret_cast<const T*>(s.Whh) + ((long)w * H + j0 + r) * H;
-    acc = tile_dot(a_row, b_row, H, q);
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) red[w][q * 4 + i][r] = acc[i];
-  __syncthreads();
+  gate_tiles(red, any ? hp : nullptr, (long)H, s.Whh, H, s.B, b0, j0);        // (a frame of blanks reads no W_hh)
   if (b >= s.B) return;
   T* hn = reinterpret_cast<T*>(s.hn);
   const int k = s_k[bb];
   if (s_emit[bb]) {
     const int col = onehot_col(k, s.V, s.blank);
-    float g[4];
+    float z[4], g[4], c;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const float wx = col >= 0 ? to_f32(reinterpret_cast<const T*>(s.WihT)[(long)col * s.ldw + i * H + j]) : 0.f;
-      g[i] = fmaf(1.f, wx, s.bias[i * H + j]);                                // (the value smx_onehot_gates_fwd gives)
+      z[i] = red[i][bb][jj] + onehot_gate_input(1.f, wx, s.bias[i * H + j]);
     }
-    const float gi = sigmoidf_(red[0][bb][jj] + g[0]);
-    const float gf = sigmoidf_(red[1][bb][jj] + g[1]);
-    const float gg = tanhf(red[2][bb][jj] + g[2]);
-    const float go = sigmoidf_(red[3][bb][jj] + g[3]);
-    const float cprev = s.start ? 0.f : s.c[(long)b * H + j];
-    const float c = gf * cprev + gi * gg;
-    hn[(long)b * H + j] = from_f32<T>(go * tanhf(c));
+    hn[(long)b * H + j] = from_f32<T>(lstm_cell(z, s.start ? 0.f : s.c[(long)b * H + j], g, c));
     s.c[(long)b * H + j] = c;
   } else {
     hn[(long)b * H + j] = hp[(long)b * H + j];
@@ -271,13 +257,11 @@ extern "C" int smx_greedy_start(int dtype, const float* bias, const void* Wproj,
   s.bias = bias; s.hn = h; s.c = c; s.seen = frames_seen;
   s.B = B; s.H = H; s.V = 2; s.blank = 0; s.start = 1;
   const dim3 grid(H / 16, (B + 15) / 16);
-  if (dtype == SMX_BF16) {
-    hipLaunchKernelGGL(greedy_step_kernel<bf16_t>, grid, dim3(256), 0, STREAM, s);
-    launch_proj<bf16_t>(h, Wproj, pdec, B, H, J, STREAM);
-  } else {
-    hipLaunchKernelGGL(greedy_step_kernel<float>, grid, dim3(256), 0, STREAM, s);
-    launch_proj<float>(h, Wproj, pdec, B, H, J, STREAM);
-  }
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(greedy_step_kernel<T>, grid, dim3(256), 0, STREAM, s);
+    launch_proj<T>(h, Wproj, pdec, B, H, J, STREAM);
+  });
   return check_launch("smx_greedy_start");
 }
 
@@ -304,8 +288,6 @@ extern "C" int smx_greedy_decode(int dtype, const void* enc, int64_t ld_b, int64
   const long n_out = (long)B * T, n_h = (long)B * H;
   const int nblk = (int)std::min<long>(1024, (std::max(n_out, n_h) + 255) / 256 + 1);
   void* h_first = (T & 1) ? h_alt : nullptr;
-  if (dtype == SMX_BF16) hipLaunchKernelGGL(greedy_begin_kernel<bf16_t>, dim3(nblk), dim3(256), 0, STREAM, tokens, frames, n_tok, (const bf16_t*)h, (bf16_t*)h_first, n_out, B, n_h);
-  else hipLaunchKernelGGL(greedy_begin_kernel<float>, dim3(nblk), dim3(256), 0, STREAM, tokens, frames, n_tok, (const float*)h, (float*)h_first, n_out, B, n_h);
   GreedyLogits g;
   g.enc = enc; g.ld_b = ld_b; g.ld_t = ld_t; g.pdec = pdec; g.Wlin = Wlin; g.blin = blin;
   g.pmax = pmax; g.parg = parg; g.psum = psum;
@@ -318,21 +300,19 @@ extern "C" int smx_greedy_decode(int dtype, const void* enc, int64_t ld_b, int64
   s.B = B; s.H = H; s.V = V; s.NT = NT; s.blank = blank; s.start = 0;
   const dim3 lgrid(NT, (B + 15) / 16), sgrid(H / 16, (B + 15) / 16);
   const size_t lds = 16 * (size_t)(J + (dtype == SMX_BF16 ? 8 : 4)) * es;
-  for (int t = 0; t < T; ++t) {
-    // frame t reads the half that frame t - 1 wrote; the parity is chosen so that frame T - 1 writes h
-    const bool from_h = ((T - t) & 1) == 0;
-    g.t = t; s.t = t;
-    s.hp = from_h ? h : h_alt;
-    s.hn = from_h ? h_alt : h;
-    if (dtype == SMX_BF16) {
-      hipLaunchKernelGGL(greedy_logits_kernel<bf16_t>, lgrid, dim3(256), lds, STREAM, g);
-      hipLaunchKernelGGL(greedy_step_kernel<bf16_t>, sgrid, dim3(256), 0, STREAM, s);
-      launch_proj<bf16_t>(s.hn, Wproj, pdec, B, H, J, STREAM);
-    } else {
-      hipLaunchKernelGGL(greedy_logits_kernel<float>, lgrid, dim3(256), lds, STREAM, g);
-      hipLaunchKernelGGL(greedy_step_kernel<float>, sgrid, dim3(256), 0, STREAM, s);
-      launch_proj<float>(s.hn, Wproj, pdec, B, H, J, STREAM);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using E = decltype(tag);                                                   // (T is the frame count here)
+    hipLaunchKernelGGL(greedy_begin_kernel<E>, dim3(nblk), dim3(256), 0, STREAM, tokens, frames, n_tok, (const E*)h, (E*)h_first, n_out, B, n_h);
+    for (int t = 0; t < T; ++t) {
+      // frame t reads the half that frame t - 1 wrote; the parity is chosen so that frame T - 1 writes h
+      const bool from_h = ((T - t) & 1) == 0;
+      g.t = t; s.t = t;
+      s.hp = from_h ? h : h_alt;
+      s.hn = from_h ? h_alt : h;
+      hipLaunchKernelGGL(greedy_logits_kernel<E>, lgrid, dim3(256), lds, STREAM, g);
+      hipLaunchKernelGGL(greedy_step_kernel<E>, sgrid, dim3(256), 0, STREAM, s);
+      launch_proj<E>(s.hn, Wproj, pdec, B, H, J, STREAM);
     }
-  }
+  });
   return check_launch("smx_greedy_decode");
 }

@@ -7,6 +7,8 @@
 // H = 512 and every workgroup reads 1/32 of it), the four tiles meet in LDS and thread (b, j) finishes its cell in fp32.  The
 // backward step has the same shape: wave w reduces over gate w's slice of dgates_{u+1} against W_hh^T.  Batch rows beyond B of
 // the last tile are computed from row B - 1 and never stored.  Every sum has a fixed order and nothing is atomic: values are bit-reproducible.
+// The cell itself (lstm_cell, lstm_cell_bwd), the forward's four gate tiles (gate_tiles) and the one-hot input (onehot_col,
+// onehot_gate_input) live in lstm_tile.h: greedy.hip's masked step and lstm_step.hip's one-launch step compute the same cell from them.
 #include "lstm_tile.h"
 
 namespace smx {
@@ -29,33 +31,20 @@ template <typename T>
 __global__ __launch_bounds__(256) void lstm_step_fwd_kernel(LstmFwdStep s) {
   __shared__ float red[4][16][17];
   const int H = s.H, j0 = blockIdx.x * 16, b0 = blockIdx.y * 16;
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
   const T* hp = reinterpret_cast<const T*>(s.hp);
-  lstm_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  if (hp) {                                                                   // (uniform)
-    const T* a_row = hp + (long)min(b0 + r, s.B - 1) * s.ld_hp;
-    const T* b_row = reinterpret_cast<const T*>(s.Whh) + ((long)w * H + j0 + r) * H;
-    acc = tile_dot(a_row, b_row, H, q);
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) red[w][q * 4 + i][r] = acc[i];
-  __syncthreads();
+  gate_tiles(red, hp, s.ld_hp, s.Whh, H, s.B, b0, j0);
   const int bb = threadIdx.x >> 4, jj = threadIdx.x & 15, b = b0 + bb, j = j0 + jj;
   if (b >= s.B) return;
-  const float* g = s.gx + (long)b * s.ld_gx;
-  const float gi = sigmoidf_(red[0][bb][jj] + g[j]);
-  const float gf = sigmoidf_(red[1][bb][jj] + g[H + j]);
-  const float gg = tanhf(red[2][bb][jj] + g[2 * H + j]);
-  const float go = sigmoidf_(red[3][bb][jj] + g[3 * H + j]);
-  const float cprev = s.cp ? s.cp[(long)b * s.ld_cp + j] : 0.f;
-  const float c = gf * cprev + gi * gg;
-  const T h = from_f32<T>(go * tanhf(c));
+  const float* gx = s.gx + (long)b * s.ld_gx;
+  const float z[4] = {red[0][bb][jj] + gx[j], red[1][bb][jj] + gx[H + j], red[2][bb][jj] + gx[2 * H + j], red[3][bb][jj] + gx[3 * H + j]};
+  float g[4], c;
+  const T h = from_f32<T>(lstm_cell(z, s.cp ? s.cp[(long)b * s.ld_cp + j] : 0.f, g, c));
   reinterpret_cast<T*>(s.y)[(long)b * s.ld_y + j] = h;
   if (s.hprev0) reinterpret_cast<T*>(s.hprev0)[(long)b * s.ld_hn + j] = hp ? hp[(long)b * s.ld_hp + j] : from_f32<T>(0.f);
   if (s.hnext) reinterpret_cast<T*>(s.hnext)[(long)b * s.ld_hn + j] = h;
   if (s.gates) {
     float* ga = s.gates + (long)b * s.ld_g;
-    ga[j] = gi; ga[H + j] = gf; ga[2 * H + j] = gg; ga[3 * H + j] = go;
+    ga[j] = g[0]; ga[H + j] = g[1]; ga[2 * H + j] = g[2]; ga[3 * H + j] = g[3];
   }
   if (s.csave) s.csave[(long)b * s.ld_cs + j] = c;
   s.crun[(long)b * H + j] = c;
@@ -89,8 +78,7 @@ __global__ __launch_bounds__(256) void lstm_step_bwd_kernel(LstmBwdStep s) {
     const T* b_row = reinterpret_cast<const T*>(s.WhhT) + (long)(j0 + r) * 4 * H + (long)w * H;
     acc = tile_dot(a_row, b_row, H, q);
   }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) red[w][q * 4 + i][r] = acc[i];
+  gate_tile_to_lds(red, acc, w, q, r);
   __syncthreads();
   const int bb = threadIdx.x >> 4, jj = threadIdx.x & 15, b = b0 + bb, j = j0 + jj;
   if (b >= s.B) return;
@@ -102,16 +90,13 @@ __global__ __launch_bounds__(256) void lstm_step_bwd_kernel(LstmBwdStep s) {
   if (s.dy) dh += to_f32(reinterpret_cast<const T*>(s.dy)[(long)b * s.ld_dy + j]);
   if (s.dhn) dh += s.dhn[(long)b * H + j];
   const float* ga = s.gates + (long)b * s.ld_g;
-  const float gi = ga[j], gf = ga[H + j], gg = ga[2 * H + j], go = ga[3 * H + j];
-  const float tc = tanhf(s.c[(long)b * s.ld_c + j]);
-  const float cprev = s.cp ? s.cp[(long)b * s.ld_cp + j] : 0.f;
-  const float dcv = (s.dc_in ? s.dc_in[(long)b * H + j] : 0.f) + dh * go * (1.f - tc * tc);
+  const float g[4] = {ga[j], ga[H + j], ga[2 * H + j], ga[3 * H + j]};
+  float dz[4];
+  s.dc[(long)b * H + j] = lstm_cell_bwd(g, s.c[(long)b * s.ld_c + j], s.cp ? s.cp[(long)b * s.ld_cp + j] : 0.f, dh,
+                                        s.dc_in ? s.dc_in[(long)b * H + j] : 0.f, dz);
   T* dg = reinterpret_cast<T*>(s.dg) + (long)b * s.ld_dg;
-  dg[j] = from_f32<T>(dcv * gg * gi * (1.f - gi));
-  dg[H + j] = from_f32<T>(dcv * cprev * gf * (1.f - gf));
-  dg[2 * H + j] = from_f32<T>(dcv * gi * (1.f - gg * gg));
-  dg[3 * H + j] = from_f32<T>(dh * tc * go * (1.f - go));
-  s.dc[(long)b * H + j] = dcv * gf;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) dg[i * H + j] = from_f32<T>(dz[i]);
 }
 
 template <typename T>
@@ -134,9 +119,9 @@ __global__ __launch_bounds__(256) void onehot_gates_fwd_kernel(const int32_t* __
   float w[4] = {0.f, 0.f, 0.f, 0.f};
   if (col >= 0) load4(WT + (long)col * ldw + n, w);
   const float4 bq = *reinterpret_cast<const float4*>(bias + n);
-  // (keep = 1: fl(w + bias), the value the dense route's GEMM gives for a one-hot row - its fp32 sum is w exactly)
   float4 o;
-  o.x = fmaf(k, w[0], bq.x); o.y = fmaf(k, w[1], bq.y); o.z = fmaf(k, w[2], bq.z); o.w = fmaf(k, w[3], bq.w);
+  o.x = onehot_gate_input(k, w[0], bq.x); o.y = onehot_gate_input(k, w[1], bq.y);
+  o.z = onehot_gate_input(k, w[2], bq.z); o.w = onehot_gate_input(k, w[3], bq.w);
   *reinterpret_cast<float4*>(Gx + (long)r * G + n) = o;
 }
 
@@ -207,8 +192,7 @@ extern "C" int smx_lstm_fwd(int dtype, const float* Gx, const void* Whh, const v
     s.crun = cn;
     s.hn = u == U - 1 ? hn : nullptr;
     s.B = B; s.H = H;
-    if (dtype == SMX_BF16) hipLaunchKernelGGL(lstm_step_fwd_kernel<bf16_t>, grid, dim3(256), 0, STREAM, s);
-    else hipLaunchKernelGGL(lstm_step_fwd_kernel<float>, grid, dim3(256), 0, STREAM, s);
+    dispatch_dtype(dtype, [&](auto tag) { hipLaunchKernelGGL(lstm_step_fwd_kernel<decltype(tag)>, grid, dim3(256), 0, STREAM, s); });
   }
   return check_launch("smx_lstm_fwd");
 }
@@ -242,8 +226,7 @@ extern "C" int smx_lstm_bwd(int dtype, const void* dY, const float* dhn, const f
       else { s.cp = C + (long)(u - 1) * H; s.ld_cp = UH; }
       s.dg = (char*)dG + (size_t)u * 4 * H * es; s.ld_dg = 4 * UH;
     }
-    if (dtype == SMX_BF16) hipLaunchKernelGGL(lstm_step_bwd_kernel<bf16_t>, grid, dim3(256), 0, STREAM, s);
-    else hipLaunchKernelGGL(lstm_step_bwd_kernel<float>, grid, dim3(256), 0, STREAM, s);
+    dispatch_dtype(dtype, [&](auto tag) { hipLaunchKernelGGL(lstm_step_bwd_kernel<decltype(tag)>, grid, dim3(256), 0, STREAM, s); });
   }
   return check_launch("smx_lstm_bwd");
 }
@@ -253,8 +236,10 @@ extern "C" int smx_onehot_rows(int dtype, const int32_t* tokens, void* Y, int64_
   SMX_REQUIRE(tokens && Y, "smx_onehot_rows: null pointer");
   SMX_REQUIRE(rows >= 0 && V >= 2 && blank >= 0 && blank < V && ldy >= V - 1, "smx_onehot_rows: bad sizes rows=%d V=%d blank=%d", rows, V, blank);
   if (rows == 0) return SMX_OK;
-  if (dtype == SMX_BF16) hipLaunchKernelGGL(onehot_rows_kernel<bf16_t>, dim3(rows), dim3(256), 0, STREAM, tokens, (bf16_t*)Y, (long)ldy, V, blank);
-  else hipLaunchKernelGGL(onehot_rows_kernel<float>, dim3(rows), dim3(256), 0, STREAM, tokens, (float*)Y, (long)ldy, V, blank);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(onehot_rows_kernel<T>, dim3(rows), dim3(256), 0, STREAM, tokens, (T*)Y, (long)ldy, V, blank);
+  });
   return check_launch("smx_onehot_rows");
 }
 
@@ -273,8 +258,10 @@ extern "C" int smx_onehot_gates_fwd(int dtype, const int32_t* tokens, const floa
   if (!aligned16(WihT) || !aligned16(bias) || !aligned16(Gx)) return fail(SMX_EUNSUPPORTED, "smx_onehot_gates_fwd: operands must be 16-byte aligned");
   if (rows == 0) return SMX_OK;
   const dim3 grid(rows, (G + 1023) / 1024);
-  if (dtype == SMX_BF16) hipLaunchKernelGGL(onehot_gates_fwd_kernel<bf16_t>, grid, dim3(256), 0, STREAM, tokens, keep, (const bf16_t*)WihT, (long)ldw, bias, Gx, V, blank, G);
-  else hipLaunchKernelGGL(onehot_gates_fwd_kernel<float>, grid, dim3(256), 0, STREAM, tokens, keep, (const float*)WihT, (long)ldw, bias, Gx, V, blank, G);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(onehot_gates_fwd_kernel<T>, grid, dim3(256), 0, STREAM, tokens, keep, (const T*)WihT, (long)ldw, bias, Gx, V, blank, G);
+  });
   return check_launch("smx_onehot_gates_fwd");
 }
 
@@ -287,7 +274,9 @@ extern "C" int smx_onehot_gates_wgrad(int dtype, const int32_t* tokens, const fl
   if (!aligned16(dG)) return fail(SMX_EUNSUPPORTED, "smx_onehot_gates_wgrad: dgates must be 16-byte aligned");
   if (rows == 0) return SMX_OK;
   const dim3 grid(rows, (G + 1023) / 1024);
-  if (dtype == SMX_BF16) hipLaunchKernelGGL(onehot_gates_wgrad_kernel<bf16_t>, grid, dim3(256), 0, STREAM, tokens, keep, (const bf16_t*)dG, (long)lddg, dWih, (long)lddw, rows, V, blank, G);
-  else hipLaunchKernelGGL(onehot_gates_wgrad_kernel<float>, grid, dim3(256), 0, STREAM, tokens, keep, (const float*)dG, (long)lddg, dWih, (long)lddw, rows, V, blank, G);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL(onehot_gates_wgrad_kernel<T>, grid, dim3(256), 0, STREAM, tokens, keep, (const T*)dG, (long)lddg, dWih, (long)lddw, rows, V, blank, G);
+  });
   return check_launch("smx_onehot_gates_wgrad");
 }

@@ -12,7 +12,8 @@
 // into registers, one step ahead of the MFMAs (weights are used once per workgroup: LDS staging would be a round trip for
 // nothing); the same 32 bytes of the activation rows (h, x or a gathered table row; L2 hits) pair with them, so the k order inside
 // a step is a permutation the two operands share.  The eight partial tiles of a batch tile meet in LDS, are added in a fixed tree, and
-// thread (row, unit) finishes its cell in fp32.  No atomics, every sum in a fixed order that depends on (I, H) alone: values are
+// thread (row, unit) finishes its cell in fp32 (lstm_tile.h's lstm_cell, the cell of lstm.hip and greedy.hip; the K-split reduction before
+// it is this file's own).  No atomics, every sum in a fixed order that depends on (I, H) alone: values are
 // bit-reproducible and a row's values do not depend on B or on the other rows.  Tile rows beyond B repeat row B - 1 and are never
 // stored.
 #include "lstm_tile.h"
@@ -159,11 +160,10 @@ __global__ __launch_bounds__(64 * STEP_WAVES) void lstm_step_kernel(LstmStepArgs
                             ((red[4][n][bb][cc] + red[5][n][bb][cc]) + (red[6][n][bb][cc] + red[7][n][bb][cc]));
             z[g] = p + s.bias[g * H + j];
           }
-          const float gi = sigmoidf_(z[0]), gf = sigmoidf_(z[1]), gg = tanhf(z[2]), go = sigmoidf_(z[3]);
-          const float cprev = s.c ? s.c[(long)b * H + j] : 0.f;
-          const float c = gf * cprev + gi * gg;
+          float gates[4], c;
+          const float h = lstm_cell(z, s.c ? s.c[(long)b * H + j] : 0.f, gates, c);
           s.c_out[(long)b * H + j] = c;
-          reinterpret_cast<T*>(s.h_out)[(long)b * H + j] = from_f32<T>(go * tanhf(c));
+          reinterpret_cast<T*>(s.h_out)[(long)b * H + j] = from_f32<T>(h);
         }
       }
     }
@@ -230,8 +230,7 @@ extern "C" int smx_lstm_step(int dtype, const void* X, int64_t ldx, const int32_
   LstmStepArgs s;
   s.x = X; s.ldx = (long)ldx; s.tok = tok; s.V = V; s.Wih = Wih; s.Whh = Whh; s.bias = bias; s.h = h; s.c = c;
   s.h_out = h_out; s.c_out = c_out; s.B = B; s.I = I; s.H = H;
-  if (dtype == SMX_BF16) launch_step<bf16_t>(s, STREAM);
-  else launch_step<float>(s, STREAM);
+  dispatch_dtype(dtype, [&](auto tag) { launch_step<decltype(tag)>(s, STREAM); });
   return check_launch("smx_lstm_step");
 }
 

@@ -183,6 +183,13 @@ __device__ __forceinline__ void dispatch_act(int act, F&& f) {
     default: f(ActTag<SMX_ACT_NONE>{}); break;
   }
 }
+// The host-side counterpart for the operand dtype: f(tag) with a value of bf16_t or float, `using T = decltype(tag)` inside f.
+// One body per launch site, compiled for both types (the entry points have refused every other dtype before they get here).
+template <typename F>
+static inline void dispatch_dtype(int dtype, F&& f) {
+  if (dtype == SMX_BF16) f(bf16_t());
+  else f(float());
+}
 
 // counter-based dropout: keep(n, c) is a pure function of (seed, n * D + c), so the backward pass regenerates the
 // forward mask from the seed instead of storing it.  Two rounds of a 32-bit multiply/xorshift mix (lowbias32) on the

@@ -113,6 +113,20 @@ def weights_changed():
     _WEPOCH[0] += 1
 
 
+def derived(held, name, srcs, build):
+    """build(*srcs): an image derived from the tensors `srcs` (W^T, a K-padded W, a bias sum, an fp32 copy of a vector), kept in the
+    dict `held` under `name` and rebuilt when a source changed: its address, dtype or torch version counter, or the weight epoch
+    above for what smx_adamw_step rewrites in place.  Inside a graph capture nothing is reused or kept: the captured step builds its
+    own images, so a replay that follows a captured optimizer update sees the new weights."""
+    if torch.cuda.is_current_stream_capturing():
+        return build(*srcs)
+    stamp = tuple((t.data_ptr(), t.dtype, t._version) for t in srcs) + (_WEPOCH[0],)
+    ent = held.get(name)
+    if ent is None or ent[1] != stamp:
+        ent = held[name] = (srcs, stamp, build(*srcs))      # (srcs held: their storage cannot be recycled under the stamp)
+    return ent[2]
+
+
 # device job tables of the trainer-managed packed images, per device and per signature.  A table whose launch was captured stays
 # alive for the life of the process (the graph holds its raw pointer); the others are dropped when the set of images changes.
 _pack_tables = {}   # (device, signature) -> [device table, blocks, captured?]

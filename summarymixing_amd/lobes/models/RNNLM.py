@@ -20,8 +20,6 @@ the forward and the state-dict names below (``embedding.Embedding.weight``, ``rn
 ``dnn.norm.norm.weight``, ``out.w.weight``) were written from memory of SpeechBrain 1.0 so that the pretrained ``lm.ckpt`` loads with
 ``strict=True`` - see DESIGN.md §I.12.  The names of a second DNN block are not certain, so ``dnn_blocks != 1`` is refused.  The
 arithmetic yardstick is torch.nn (tests/_rnnlm_ref.py)."""
-import math
-
 import torch
 from torch import nn
 
@@ -31,7 +29,6 @@ from ...nnet import RNN as _RNN
 from ...nnet.activations import act_code
 from ...nnet.linear import Linear
 
-_NO_CPU = "summarymixing_amd kernels run on the GPU only (no CPU fallback)"
 _E_MIN, _E_MAX, _E_STEP = 32, 4096, 32      # the input widths csrc/lstm_step.hip supports (smx_lstm_step_ok)
 
 
@@ -43,30 +40,13 @@ class _Table(nn.Module):
         self.Embedding = nn.Embedding(num_embeddings, embedding_dim, padding_idx=0)
 
 
-class _StackParams(nn.Module):
-    """torch.nn.LSTM's parameters of an L-layer unidirectional stack: names, shapes, order and default initialisation."""
-
-    def __init__(self, input_size, hidden_size, num_layers):
-        super().__init__()
-        for k in range(num_layers):
-            I = input_size if k == 0 else hidden_size
-            setattr(self, f"weight_ih_l{k}", nn.Parameter(torch.empty(4 * hidden_size, I)))
-            setattr(self, f"weight_hh_l{k}", nn.Parameter(torch.empty(4 * hidden_size, hidden_size)))
-            setattr(self, f"bias_ih_l{k}", nn.Parameter(torch.empty(4 * hidden_size)))
-            setattr(self, f"bias_hh_l{k}", nn.Parameter(torch.empty(4 * hidden_size)))
-        self._derived = {}                   # images derived from the weights (nnet.RNN._derived); not part of the state_dict
-        s = 1.0 / math.sqrt(hidden_size)
-        for p in self.parameters():
-            nn.init.uniform_(p, -s, s)
-
-
 class _StackedLSTM(nn.Module):
     """Holder of the stack under SpeechBrain's ``.rnn`` (nnet.RNN.LSTM keeps refusing num_layers != 1)."""
 
     def __init__(self, input_size, hidden_size, num_layers, re_init):
         super().__init__()
         self.input_size, self.hidden_size, self.num_layers = input_size, hidden_size, num_layers
-        self.rnn = _StackParams(input_size, hidden_size, num_layers)
+        self.rnn = _RNN._LSTMParams(input_size, hidden_size, num_layers)
         if re_init:
             _RNN.rnn_init(self.rnn)
 
@@ -84,12 +64,6 @@ class _DNNBlock(nn.Module):
         super().__init__()
         self.linear = Linear(neurons, input_size=input_size, bias=True)
         self.norm = _Norm(neurons)
-
-
-def _to(t, dtype):
-    if t.dtype == dtype:
-        return t
-    return ops.cast(t, dtype) if (t.dtype in ops._DT and dtype in ops._DT) else t.to(dtype)
 
 
 class RNNLM(nn.Module):
@@ -117,37 +91,14 @@ class RNNLM(nn.Module):
         self.rnn = _StackedLSTM(E, H, int(rnn_layers), rnn_re_init)
         self.dnn = _DNNBlock(H, int(dnn_neurons))
         self.out = Linear(self.output_neurons, input_size=int(dnn_neurons), bias=True)
-        self._images = {}                    # float32 images of biases and LayerNorm vectors (_image); not part of the state_dict
-
-    # ---- parameter images ---------------------------------------------------------------------------------------------------
-    def _layer(self, k, T):
-        """(W_ih, W_hh in T, bias (4H) fp32 = b_ih + b_hh) of layer k."""
-        p = self.rnn.rnn
-        w_ih, w_hh = getattr(p, f"weight_ih_l{k}"), getattr(p, f"weight_hh_l{k}")
-        b_ih, b_hh = getattr(p, f"bias_ih_l{k}"), getattr(p, f"bias_hh_l{k}")
-        Wih, Whh = F.wcast(w_ih, T).contiguous(), F.wcast(w_hh, T).contiguous()
-        bsum = self._image(f"bsum{k}", (b_ih, b_hh), lambda: ops.axpby(
-            1.0, _to(b_ih.detach(), torch.float32).view(1, -1), 1.0, _to(b_hh.detach(), torch.float32).view(1, -1)).view(-1))
-        return Wih, Whh, bsum
-
-    def _image(self, name, srcs, build):
-        """A float32 image of one or two parameters (a bias sum, a bias or LayerNorm vector), kept and rebuilt under the rules of
-        nnet.RNN._derived: torch's version counters and functional's weight epoch; inside a graph capture nothing is reused or kept."""
-        if torch.cuda.is_current_stream_capturing():
-            return build()
-        stamp = tuple((t.data_ptr(), t.dtype, t._version) for t in srcs) + (F._WEPOCH[0],)
-        ent = self._images.get(name)
-        if ent is None or ent[1] != stamp:
-            ent = (srcs, stamp, build())
-            self._images[name] = ent
-        return ent[2]
+        self._derived = {}                   # float32 images of the head's biases and LayerNorm vectors; not part of the state_dict
 
     def _f32(self, name, param):
-        return self._image(name, (param,), lambda: _to(param.detach(), torch.float32).contiguous())
+        return F.derived(self._derived, name, (param,), lambda p: ops.cast(p.detach(), torch.float32).contiguous())
 
     def _check(self, x):
         if not x.is_cuda:
-            raise RuntimeError(_NO_CPU)
+            raise RuntimeError(ops.NO_CPU)
         if x.dtype.is_floating_point or x.dim() not in (1, 2):
             raise ValueError(f"RNNLM: integer tokens (B, U) or (B,) expected, got {tuple(x.shape)} {x.dtype}")
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
@@ -166,9 +117,9 @@ class RNNLM(nn.Module):
         h, c = hx
         if h is not None and (not h.is_cuda or tuple(h.shape) != (L, B, H)) or c is not None and (not c.is_cuda or tuple(c.shape) != (L, B, H)):
             raise ValueError(f"RNNLM: hx = (h, c), each ({L}, {B}, {H}) on the GPU")
-        h = _to(h.detach(), T).contiguous() if h is not None else None
-        c = _to(c.detach(), torch.float32).contiguous() if c is not None else None
-        return h, c
+        def to(t, dtype):                    # (a state of any float dtype is accepted back: what the cast kernels do not take goes through torch)
+            return t if t is None else (ops.cast(t.detach(), dtype) if t.dtype in ops._DT else t.detach().to(dtype)).contiguous()
+        return to(h, T), to(c, torch.float32)
 
     def _head(self, y2, T):
         d = self.dnn
@@ -197,7 +148,7 @@ class RNNLM(nn.Module):
         tk = ops._tokens_i32(tokens)
         table = self.embedding.Embedding.weight.detach()
         for k in range(L):
-            Wih, Whh, bsum = self._layer(k, T)
+            Wih, Whh, bsum = _RNN.lstm_weights(self.rnn.rnn, k, T)
             hk, ck = (h[k] if h is not None else None), (c[k] if c is not None else None)
             if k == 0:
                 ops.lstm_step(table, Wih, Whh, bsum, hk, ck, hn[0], cn[0], tokens=tk)
@@ -211,25 +162,14 @@ class RNNLM(nn.Module):
         B, U = tokens.shape
         L, H = self.rnn.num_layers, self.rnn.hidden_size
         h, c = self._state(hx, B, T)
-        p = self.rnn.rnn
         x = ops.gather_rows(tokens, self.embedding.Embedding.weight.detach())                  # (B, U, E)
         hn, cn = [], []
-        for k in range(L):
-            Wih, Whh, bsum = self._layer(k, T)
-            I = x.shape[2]
-            x2 = x.reshape(B * U, I)
-            if I % _RNN._K_PAD != 0:                                                         # (as nnet.RNN's dense route)
-                Kp = (I + _RNN._K_PAD - 1) // _RNN._K_PAD * _RNN._K_PAD
-                xp = torch.zeros((B * U, Kp), dtype=T, device=x.device)
-                xp[:, :I].copy_(x2)
-                Wih = _RNN._derived(p, f"Wih_pad{k}", Wih, lambda w: _RNN._pad_k(w, Kp))
-                x2 = xp
-            Gx, _ = F.linear_fwd(x2, Wih, bsum, out_f32=T != torch.float32)
-            x, hk, ck, _ = ops.lstm_fwd(Gx, Whh, h[k] if h is not None else None, c[k] if c is not None else None, B, U, False)
+        for k in range(L):                                                                     # (no graph: _check refused grad mode)
+            x, hk, ck = _RNN.lstm_apply(x, (h[k] if h is not None else None, c[k] if c is not None else None), self.rnn, k=k)
             hn.append(hk)
             cn.append(ck)
         logits = self._head(x.view(B * U, H), T).view(B, U, -1)
-        return logits, (torch.stack(hn, 0), torch.stack(cn, 0))
+        return logits, (torch.cat(hn, 0), torch.cat(cn, 0))
 
     def forward(self, x, hx=None):
         """x: tokens (B, U) -> logits (B, U, V), or (B,) -> (B, V); with return_hidden: (logits, (h_n, c_n))."""

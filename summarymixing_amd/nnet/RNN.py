@@ -17,33 +17,45 @@ H_MIN, H_MAX, H_STEP = 32, 4096, 32         # what csrc/lstm.hip supports (smx_l
 _K_PAD = 64                                 # the dense input is zero-padded to a multiple of the bf16 GEMM's 64-element K stage
 
 
-def _derived(holder, name, src, build):
-    """Images derived from a weight in its compute dtype (W_ih^T, W_hh^T, the K-padded W_ih), kept on the parameter holder and
-    rebuilt when the weight changed: torch's version counter, and functional's weight epoch for the trainer-managed bf16 shadows
-    that smx_adamw_step rewrites in place.  Inside a graph capture nothing is reused or kept: the captured step builds its own
-    images, so a replay that follows a captured optimizer update sees the new weights."""
-    if torch.cuda.is_current_stream_capturing():
-        return build(src)
-    stamp = (src.data_ptr(), src.dtype, src._version, F._WEPOCH[0])
-    ent = holder._derived.get(name)
-    if ent is None or ent[1] != stamp:
-        ent = (src, stamp, build(src))                      # (src held: its storage cannot be recycled under the stamp)
-        holder._derived[name] = ent
-    return ent[2]
+def _transposed(w):
+    return w.t().contiguous()
 
 
-def _pad_k(W, Kp):
-    Wp = torch.zeros((W.shape[0], Kp), dtype=W.dtype, device=W.device)
-    Wp[:, :W.shape[1]].copy_(W)
-    return Wp
+def lstm_weights(params, k, T):
+    """(W_ih in T, W_hh in T contiguous, b_ih + b_hh in fp32) of layer k of an _LSTMParams.  The bias sum and the images of the two
+    weights that the routes below ask for (W_ih^T, W_hh^T, the K-padded W_ih) are kept in params._derived under functional.derived's
+    rules."""
+    b_ih, b_hh = getattr(params, f"bias_ih_l{k}"), getattr(params, f"bias_hh_l{k}")
+    bsum = F.derived(params._derived, f"bsum{k}", (b_ih, b_hh), lambda a, b: ops.axpby(
+        1.0, ops.cast(a.detach(), torch.float32).view(1, -1), 1.0, ops.cast(b.detach(), torch.float32).view(1, -1)).view(-1))
+    return F.wcast(getattr(params, f"weight_ih_l{k}"), T), F.wcast(getattr(params, f"weight_hh_l{k}"), T).contiguous(), bsum
 
 
-def _pad_grad(holder, param, Kp):
+def dense_gates(x2, Wih, bsum, params, k):
+    """Gx (rows, 4H) fp32 = x2 W_ih^T + bsum on the MFMA GEMM -> (Gx, the x2 and the W_ih it ran on: both zero-padded along K to a
+    multiple of _K_PAD when the input width is none, the padded W_ih a kept image)."""
+    rows, I = x2.shape
+    if I % _K_PAD != 0:
+        Kp = (I + _K_PAD - 1) // _K_PAD * _K_PAD
+        xp = torch.zeros((rows, Kp), dtype=x2.dtype, device=x2.device)
+        xp[:, :I].copy_(x2)
+
+        def pad(w):
+            Wp = torch.zeros((w.shape[0], Kp), dtype=w.dtype, device=w.device)
+            Wp[:, :I].copy_(w)
+            return Wp
+        x2, Wih = xp, F.derived(params._derived, f"Wih_pad{k}", (Wih,), pad)
+    elif not x2.is_contiguous():
+        x2 = x2.contiguous()
+    Gx, _ = F.linear_fwd(x2, Wih, bsum, out_f32=x2.dtype != torch.float32)
+    return Gx, x2, Wih
+
+
+def _pad_grad(params, k, param, Kp):
     """Persistent fp32 (4H, Kp) gradient image of the K-padded W_ih (a stable address for the deferred wgrad workspaces)."""
-    g = holder._derived.get("gWp")
+    g = params._derived.get(f"gWp{k}")
     if g is None or g.shape[1] != Kp or g.device != param.device:
-        g = torch.zeros((param.shape[0], Kp), dtype=torch.float32, device=param.device)
-        holder._derived["gWp"] = g
+        g = params._derived[f"gWp{k}"] = torch.zeros((param.shape[0], Kp), dtype=torch.float32, device=param.device)
     return g
 
 
@@ -52,54 +64,43 @@ class _LSTMFn(torch.autograd.Function):
     (B, U) tokens, the input product is a row gather of W_ih^T (keep: per-token fp32 factors or None) and no one-hot row exists."""
 
     @staticmethod
-    def forward(ctx, inp, h0, c0, w_ih, w_hh, b_ih, b_hh, onehot, holder):
+    def forward(ctx, inp, h0, c0, w_ih, w_hh, b_ih, b_hh, onehot, holder, k):
         ctx.set_materialize_grads(False)
         B, U = inp.shape[0], inp.shape[1]
         H = w_hh.shape[1]
         T = inp.dtype if onehot is None else onehot[3]
         need_bwd = any(ctx.needs_input_grad)
-        Whh, Wih = F.wcast(w_hh, T).contiguous(), F.wcast(w_ih, T)
-        bsum = ops.axpby(1.0, b_ih.detach().view(1, -1), 1.0, b_hh.detach().view(1, -1)).view(-1)
+        Wih, Whh, bsum = lstm_weights(holder, k, T)
         if onehot is None:
             I = inp.shape[2]
-            x2 = inp.reshape(B * U, I)
-            Wp = Wih
-            if I % _K_PAD != 0:
-                Kp = (I + _K_PAD - 1) // _K_PAD * _K_PAD
-                xp = torch.zeros((B * U, Kp), dtype=T, device=inp.device)
-                xp[:, :I].copy_(x2)
-                Wp = _derived(holder, "Wih_pad", Wih, lambda w: _pad_k(w, Kp))
-                x2 = xp
-            elif not x2.is_contiguous():
-                x2 = x2.contiguous()
-            Gx, _ = F.linear_fwd(x2, Wp, bsum, out_f32=T != torch.float32)
+            Gx, x2, Wp = dense_gates(inp.reshape(B * U, I), Wih, bsum, holder, k)
             side = (x2, Wp, I)
         else:
+            assert k == 0, "tokens are the first layer's input"
             V, blank, keep = onehot[:3]
             tk = ops._tokens_i32(inp)
-            Gx = ops.onehot_gates_fwd(tk, keep, _derived(holder, "WihT", Wih, lambda w: w.t().contiguous()), bsum, V, blank)
+            Gx = ops.onehot_gates_fwd(tk, keep, F.derived(holder._derived, "WihT", (Wih,), _transposed), bsum, V, blank)
             side = (tk, keep, V, blank)
         h0_ = ops.cast(h0.detach().reshape(B, H), T).contiguous() if h0 is not None else None
         c0_ = ops.cast(c0.detach().reshape(B, H), torch.float32).contiguous() if c0 is not None else None
         Y, hn, cn, saved = ops.lstm_fwd(Gx, Whh, h0_, c0_, B, U, need_bwd)
         if need_bwd:
-            ctx.saved = (Whh, c0_, saved, side, onehot is None, (w_ih, w_hh, b_ih, b_hh), holder,
+            ctx.saved = (Whh, c0_, saved, side, onehot is None, (w_ih, w_hh, b_ih, b_hh), (holder, k),
                          h0.dtype if h0 is not None else None, c0.dtype if c0 is not None else None)
         return Y, hn.view(1, B, H), cn.view(1, B, H)
 
     @staticmethod
     def backward(ctx, dY, dhn, dcn):
-        Whh, c0_, (Hprev, gates, C), side, dense, (w_ih, w_hh, b_ih, b_hh), holder, h0_dt, c0_dt = ctx.saved
+        Whh, c0_, (Hprev, gates, C), side, dense, (w_ih, w_hh, b_ih, b_hh), (holder, k), h0_dt, c0_dt = ctx.saved
         ctx.saved = None
         B, U, H = Hprev.shape
         T = Whh.dtype
-        none = (None,) * 9
         if dY is None and dhn is None and dcn is None:
-            return none
+            return (None,) * 10
         dY_ = ops.cast(dY, T).contiguous() if dY is not None else None
         dhn_ = ops.cast(dhn.reshape(B, H), torch.float32).contiguous() if dhn is not None else None
         dcn_ = ops.cast(dcn.reshape(B, H), torch.float32).contiguous() if dcn is not None else None
-        dG, dh0, dc0 = ops.lstm_bwd(dY_, dhn_, dcn_, _derived(holder, "WhhT", Whh, lambda w: w.t().contiguous()), gates, C, c0_, B, U)
+        dG, dh0, dc0 = ops.lstm_bwd(dY_, dhn_, dcn_, F.derived(holder._derived, f"WhhT{k}", (Whh,), _transposed), gates, C, c0_, B, U)
         # dW_hh += dG^T H_prev over all B U rows, db_hh += colsum(dG): the ordinary wgrad route
         F.linear_bwd(dG, Hprev.view(B * U, H), Whh, None, L.ACT_NONE, None, 1.0, F.gacc(w_hh), F.gacc(b_hh), need_dx=False)
         dx = None
@@ -107,7 +108,7 @@ class _LSTMFn(torch.autograd.Function):
             x2, Wp, I = side
             gW, gWp = F.gacc(w_ih), None
             if gW is not None and Wp.shape[1] != I:
-                gWp = _pad_grad(holder, w_ih, Wp.shape[1])
+                gWp = _pad_grad(holder, k, w_ih, Wp.shape[1])
                 gWp.zero_()
             dxp, _ = F.linear_bwd(dG, x2, Wp, None, L.ACT_NONE, None, 1.0, gWp if gWp is not None else gW, F.gacc(b_ih),
                                   need_dx=ctx.needs_input_grad[0])
@@ -127,27 +128,29 @@ class _LSTMFn(torch.autograd.Function):
             F.flush_deferred()
         dh0 = ops.cast(dh0, h0_dt).view(1, B, H) if (h0_dt is not None and ctx.needs_input_grad[1]) else None
         dc0 = ops.cast(dc0, c0_dt).view(1, B, H) if (c0_dt is not None and ctx.needs_input_grad[2]) else None
-        return (dx, dh0, dc0) + (None,) * 6
+        return (dx, dh0, dc0) + (None,) * 7
 
 
-def lstm_apply(inp, hx, rnn, onehot=None):
-    """The recurrence on `inp` with the parameters of `rnn` (an LSTM below); hx = (h0, c0), each (1, B, H) or (B, H), or None."""
+def lstm_apply(inp, hx, rnn, onehot=None, k=0):
+    """The recurrence on `inp` with the parameters of layer k of `rnn` (a module whose ``.rnn`` is an _LSTMParams: an LSTM below);
+    hx = (h0, c0), each (1, B, H), (B, H) or None, or None."""
     h0, c0 = hx if hx is not None else (None, None)
     p = rnn.rnn
-    return _LSTMFn.apply(inp, h0, c0, p.weight_ih_l0, p.weight_hh_l0, p.bias_ih_l0, p.bias_hh_l0, onehot, p)
+    return _LSTMFn.apply(inp, h0, c0, *(getattr(p, f"{n}_l{k}") for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")), onehot, p, k)
 
 
 class _LSTMParams(nn.Module):
-    """torch.nn.LSTM's parameters of one unidirectional layer: names, shapes, order and default initialisation."""
+    """torch.nn.LSTM's parameters of a unidirectional stack: names, shapes, order and default initialisation."""
 
-    def __init__(self, input_size, hidden_size):
+    def __init__(self, input_size, hidden_size, num_layers=1):
         super().__init__()
         self.input_size, self.hidden_size = input_size, hidden_size
-        self.weight_ih_l0 = nn.Parameter(torch.empty(4 * hidden_size, input_size))
-        self.weight_hh_l0 = nn.Parameter(torch.empty(4 * hidden_size, hidden_size))
-        self.bias_ih_l0 = nn.Parameter(torch.empty(4 * hidden_size))
-        self.bias_hh_l0 = nn.Parameter(torch.empty(4 * hidden_size))
-        self._derived = {}                   # images derived from the weights (_derived above); not part of the state_dict
+        for k in range(num_layers):
+            setattr(self, f"weight_ih_l{k}", nn.Parameter(torch.empty(4 * hidden_size, input_size if k == 0 else hidden_size)))
+            setattr(self, f"weight_hh_l{k}", nn.Parameter(torch.empty(4 * hidden_size, hidden_size)))
+            setattr(self, f"bias_ih_l{k}", nn.Parameter(torch.empty(4 * hidden_size)))
+            setattr(self, f"bias_hh_l{k}", nn.Parameter(torch.empty(4 * hidden_size)))
+        self._derived = {}                   # images of the parameters (functional.derived); not part of the state_dict
         k = 1.0 / math.sqrt(hidden_size)
         for p in self.parameters():
             nn.init.uniform_(p, -k, k)
@@ -192,7 +195,7 @@ class LSTM(nn.Module):
         if lengths is not None:
             raise NotImplementedError("LSTM: packed / length-masked sequences are not used by the SummaryMixing recipes")
         if not x.is_cuda:
-            raise RuntimeError("summarymixing_amd kernels run on the GPU only (no CPU fallback)")
+            raise RuntimeError(ops.NO_CPU)
         if self.reshape and x.ndim == 4:
             x = x.reshape(x.shape[0], x.shape[1], x.shape[2] * x.shape[3])
         if x.dim() != 3 or x.shape[2] != self.rnn.input_size:

@@ -12,7 +12,7 @@ from ... import functional as F
 from ... import ops
 from ..embedding import Embedding
 from ..linear import Linear
-from ..RNN import LSTM, _derived
+from ..RNN import LSTM, _transposed, lstm_weights
 from .transducer_joint import Transducer_joint
 
 
@@ -41,7 +41,7 @@ def _weights(enc, emb, dec, proj_dec, tjoint, transducer_lin):
         raise TypeError("greedy_decode: emb, dec, proj_dec, tjoint and transducer_lin must be this package's Embedding, LSTM, Linear, "
                         "Transducer_joint and Linear")
     if not enc.is_cuda:
-        raise RuntimeError("summarymixing_amd kernels run on the GPU only (no CPU fallback)")
+        raise RuntimeError(ops.NO_CPU)
     if enc.dim() != 3:
         raise ValueError(f"greedy_decode: enc (B, T, J) expected, got {tuple(enc.shape)}")
     ops.dt(enc)
@@ -59,10 +59,8 @@ def _weights(enc, emb, dec, proj_dec, tjoint, transducer_lin):
         raise NotImplementedError(f"greedy_decode: no kernel for H {H}, J {J}, V {V} (H a multiple of 32 in [32, 4096], J a multiple "
                                   "of 64 in [64, 832], V >= 2)")
     DT = enc.dtype
-    p = dec.rnn
-    WihT = _derived(p, "WihT", F.wcast(p.weight_ih_l0, DT), lambda w: w.t().contiguous())
-    bsum = ops.axpby(1.0, p.bias_ih_l0.detach().view(1, -1), 1.0, p.bias_hh_l0.detach().view(1, -1)).view(-1)
-    return dict(WihT=WihT, bias=bsum, Whh=F.wcast(p.weight_hh_l0, DT).contiguous(), Wproj=F.wcast(Wp, DT).contiguous(),
+    Wih, Whh, bsum = lstm_weights(dec.rnn, 0, DT)
+    return dict(WihT=F.derived(dec.rnn._derived, "WihT", (Wih,), _transposed), bias=bsum, Whh=Whh, Wproj=F.wcast(Wp, DT).contiguous(),
                 Wlin=F.wcast(Wl, DT).contiguous(), blin=bl.detach().float().contiguous() if bl is not None else None,
                 act=tjoint.act, blank=emb.blank_id)
 
@@ -146,7 +144,7 @@ class CapturedGreedy:
         if tuple(enc.shape) != tuple(self.enc.shape) or enc.dtype != self.enc.dtype:
             raise ValueError(f"CapturedGreedy: captured for {tuple(self.enc.shape)} {self.enc.dtype}, got {tuple(enc.shape)} {enc.dtype}")
         if not enc.is_cuda:
-            raise RuntimeError("summarymixing_amd kernels run on the GPU only (no CPU fallback)")
+            raise RuntimeError(ops.NO_CPU)
         self.enc.copy_(enc)
         if lengths is None:
             self.in_len.fill_(self.T)

@@ -38,7 +38,7 @@ def prediction_network(tokens_bos, emb, dec, proj_dec, emb_dropout=0.0, dec_drop
     if not (isinstance(emb, Embedding) and isinstance(dec, LSTM) and isinstance(proj_dec, Linear)):
         raise TypeError("prediction_network: emb, dec and proj_dec must be this package's Embedding, LSTM and Linear")
     if not tokens_bos.is_cuda:
-        raise RuntimeError("summarymixing_amd kernels run on the GPU only (no CPU fallback)")
+        raise RuntimeError(ops.NO_CPU)
     if tokens_bos.dim() != 2 or tokens_bos.dtype.is_floating_point:
         raise ValueError(f"prediction_network: integer tokens (B, U+1) expected, got {tuple(tokens_bos.shape)} {tokens_bos.dtype}")
     if dec.rnn.input_size != emb.embedding_dim:

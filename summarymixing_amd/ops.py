@@ -12,6 +12,7 @@ import torch
 from . import _lib as L
 
 _DT = {torch.float32: L.F32, torch.bfloat16: L.BF16}
+NO_CPU = "summarymixing_amd kernels run on the GPU only (no CPU fallback)"
 
 
 def dt(t):
@@ -74,7 +75,7 @@ def _es(t):
 def _mat(t):
     """(ptr, ld) of a 2-D view with unit inner stride."""
     assert t.dim() == 2 and (t.shape[1] == 1 or t.stride(1) == 1), f"need a (rows, cols) view with unit col stride, got {t.shape} {t.stride()}"
-    assert t.is_cuda, "summarymixing_amd kernels run on the GPU only (no CPU fallback)"
+    assert t.is_cuda, NO_CPU
     return _p(t), (t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1]))
 
 
@@ -971,7 +972,7 @@ def transducer_gemm_grad(H2, W, bias, targets, lse, gb, gy, B, T, U1, blank, row
 
 # ---- prediction network (csrc/lstm.hip): one-hot Embedding rows, the one-hot input route of the LSTM, the recurrence and its BPTT.
 def _tokens_i32(tokens):
-    assert tokens.is_cuda, "summarymixing_amd kernels run on the GPU only (no CPU fallback)"
+    assert tokens.is_cuda, NO_CPU
     return tokens.reshape(-1).to(torch.int32).contiguous()
 
 
@@ -1069,7 +1070,7 @@ def lstm_step(x, Wih, Whh, bias, h, c, h_out=None, c_out=None, tokens=None):
     -> (h' (B, H), c' (B, H) fp32), written into h_out / c_out when given: buffers DISTINCT from h, c and x."""
     H, I = Whh.shape[1], Wih.shape[1]
     T, dev = Whh.dtype, Whh.device
-    assert Whh.is_cuda, "summarymixing_amd kernels run on the GPU only (no CPU fallback)"
+    assert Whh.is_cuda, NO_CPU
     assert Wih.dtype == T and x.dtype == T and Wih.is_contiguous() and Whh.is_contiguous() and Wih.shape[0] == 4 * H and x.shape[1] == I
     assert bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == 4 * H
     B = x.shape[0] if tokens is None else tokens.numel()
@@ -1126,7 +1127,7 @@ def greedy_decode(enc, in_len, WihT, bias, Whh, Wproj, Wlin, blin, state, logp, 
     h, c, pdec, seen = state
     H, V = Whh.shape[1], Wlin.shape[0]
     dev, DT = enc.device, enc.dtype
-    assert enc.is_cuda, "summarymixing_amd kernels run on the GPU only (no CPU fallback)"
+    assert enc.is_cuda, NO_CPU
     assert all(w.dtype == DT and w.is_contiguous() for w in (Whh, Wproj, Wlin, h, pdec)) and WihT.dtype == DT and WihT.stride(1) == 1
     assert all(t.dtype == torch.float32 and t.is_contiguous() for t in (bias, c, logp) + ((blin,) if blin is not None else ()))
     assert seen.dtype == torch.int32 and (in_len is None or (in_len.dtype == torch.int32 and in_len.is_contiguous()))

@@ -254,3 +254,22 @@ def test_the_training_lattice_walks_the_same_path():
                 u += 1
         assert walked == hyps[b], b
     assert checked == B * T
+
+
+# ---- 10. the decoder's LSTM step is the prediction network's
+@pytest.mark.parametrize("dtype", [F32, BF16], ids=["f32", "bf16"])
+def test_the_final_state_is_the_prediction_networks_on_the_hypothesis(dtype):
+    """Row by row, [blank] + hyp through lstm_apply's one-hot route (no dropout) ends on the decoder's final (h, c), bit for bit:
+    csrc/greedy.hip's masked step and csrc/lstm.hip compute one cell from one one-hot gate input (csrc/lstm_tile.h)."""
+    from summarymixing_amd.nnet.RNN import lstm_apply
+    mods, enc, p, enc_cpu, blank = _setup("small", dtype)
+    emb, dec = mods[:2]
+    r = _decode("small", dtype)
+    hyps, _ = _lists(r)
+    assert sum(len(h) for h in hyps) > 0
+    for b, hyp in enumerate(hyps):
+        tb = torch.tensor([[blank] + hyp], dtype=torch.long, device="cuda")
+        with torch.no_grad():
+            y, hn, cn = lstm_apply(tb, None, dec, onehot=(emb.num_embeddings, blank, None, dtype))
+        assert torch.equal(y[0, len(hyp)], r.state.h[b]) and torch.equal(hn[0, 0], r.state.h[b]), b
+        assert torch.equal(cn[0, 0], r.state.c[b]), b

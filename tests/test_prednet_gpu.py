@@ -309,3 +309,44 @@ def test_whole_head_in_one_step_against_fp64():
     errs.update({k: rel_err(v, ref[k]) for k, v in _grads(dec, proj).items()})
     report("prediction_network whole head f32", errs)
     assert all(v <= tol for v in errs.values()), errs
+
+
+# ---- the weight images of the parameter holder (functional.derived) ------------------------------------------------------------
+@pytest.mark.parametrize("name", ["WihT", "bsum0"])
+def test_a_weight_image_is_kept_until_its_source_changes(name):
+    """Kept between calls; rebuilt after an in-place change of a source and after functional.weights_changed(); inside a graph
+    capture nothing is stored on the holder."""
+    from summarymixing_amd import functional as F
+    from summarymixing_amd.nnet.RNN import lstm_apply
+    V, H = 9, 32
+    emb, dec, _ = _modules(V, H, 8, 0, F32, seed=11)
+    p = dec.rnn
+    tokens = _tokens(2, 3, V, 0, 12).cuda()
+    if name == "WihT":
+        src, fresh = p.weight_ih_l0, lambda: p.weight_ih_l0.detach().t().contiguous()
+    else:
+        src, fresh = p.bias_hh_l0, lambda: p.bias_ih_l0.detach() + p.bias_hh_l0.detach()
+
+    def run():
+        with torch.no_grad():
+            lstm_apply(tokens, None, dec, onehot=(V, 0, None, F32))
+
+    def image():
+        run()
+        return p._derived[name][2]
+
+    a = image()
+    assert image() is a and torch.equal(a, fresh())
+    with torch.no_grad():
+        src.add_(1)
+    b = image()
+    assert b is not a and torch.equal(b, fresh()) and not torch.equal(b, a)
+    F.weights_changed()
+    c = image()
+    assert c is not b and torch.equal(c, fresh())
+    p._derived.clear()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        run()
+    assert not p._derived
+    assert torch.equal(image(), fresh())

@@ -294,3 +294,31 @@ def test_captured_step_replays_the_eager_bits(dtype):
             hA.copy_(hB)
             cA.copy_(cB)
     assert torch.equal(hB, hx[0]) and torch.equal(cB, hx[1])
+
+
+# ---- the parameter holder is nnet.RNN's ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("re_init", [False, True], ids=["uniform", "orthogonal"])
+def test_one_layer_holder_has_the_lstms_state_dict(re_init):
+    """A one-layer RNNLM's rnn.rnn and an LSTM's rnn: the same keys, shapes and - the seed and the draws before them being the same -
+    values."""
+    from summarymixing_amd.lobes.models.RNNLM import RNNLM
+    from summarymixing_amd.nnet.RNN import LSTM
+    V, E, H = 50, 32, 64
+    torch.manual_seed(7)
+    lm = RNNLM(V, embedding_dim=E, rnn_layers=1, rnn_neurons=H, rnn_re_init=re_init, dnn_neurons=32)
+    torch.manual_seed(7)
+    torch.nn.Embedding(V, E, padding_idx=0)                    # (the table RNNLM draws before its LSTM)
+    dec = LSTM(H, input_size=E, re_init=re_init)
+    a, b = lm.rnn.rnn.state_dict(), dec.rnn.state_dict()
+    assert type(lm.rnn.rnn) is type(dec.rnn) and list(a) == list(b) == ["weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0"]
+    assert all(a[k].shape == b[k].shape and torch.equal(a[k], b[k]) for k in a)
+
+
+def test_two_layer_holder_has_torchs_keys():
+    from summarymixing_amd.lobes.models.RNNLM import RNNLM
+    V, E, H = 50, 32, 64
+    lm = RNNLM(V, embedding_dim=E, rnn_layers=2, rnn_neurons=H, dnn_neurons=32)
+    ref = torch.nn.LSTM(E, H, num_layers=2, batch_first=True).state_dict()
+    sd = lm.rnn.rnn.state_dict()
+    assert list(sd) == list(ref) == [f"{n}_l{k}" for k in (0, 1) for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+    assert all(sd[k].shape == ref[k].shape for k in sd)

@@ -23,6 +23,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from summarymixing_amd import ops  # noqa: E402
 from summarymixing_amd.lobes.models.RNNLM import RNNLM  # noqa: E402
 from summarymixing_amd.nnet import LSTM  # noqa: E402
+from summarymixing_amd.nnet.RNN import lstm_weights  # noqa: E402
 
 V, E, H, L, D = 1000, 128, 2048, 2, 512
 BATCHES = [1, 10, 80]
@@ -81,7 +82,7 @@ def bench_point(B, dtype, reps, warmup, inner):
         y, st["torch"] = ref(x, st.get("torch"))
         lm._head(y.reshape(B, H), dtype)
 
-    Wl = [lm._layer(k, dtype) for k in range(L)]
+    Wl = [lstm_weights(p, k, dtype) for k in range(L)]
     tk32 = tok.to(torch.int32)
     bufs = [(torch.randn(B, H, device="cuda").to(dtype), torch.randn(B, H, device="cuda"), torch.empty(B, H, device="cuda", dtype=dtype),
              torch.empty(B, H, device="cuda")) for _ in range(L)]
