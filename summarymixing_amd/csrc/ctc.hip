@@ -32,9 +32,13 @@ __global__ __launch_bounds__(256) void log_softmax_fwd_kernel(const T* __restric
   float s = 0.f;
   for (int c = lane; c < V; c += 64) s += expf(to_f32(x[c]) - m);
   s = wave_sum(s);
-  const float lz = m + logf(s);
+  // x - (m + log s) with the sum and the difference in fp64, rounded once.  In fp32 the sum m + log s rounds at eps |m|, which is
+  // all that is left of an entry near the maximum (|y| << |m|) once the logits are large.  Writing (x - m) - log s in fp32 does
+  // not help: the library is built with -ffast-math and the compiler reassociates it back to x - (m + log s), hoisting the sum
+  // out of the loop.  The two fp64 operations per entry hide behind the loads (the kernel reads the row twice).
+  const double lz = (double)m + (double)logf(s);
   T* y = Y + (long)row * ldy;
-  for (int c = lane; c < V; c += 64) y[c] = from_f32<T>(to_f32(x[c]) - lz);
+  for (int c = lane; c < V; c += 64) y[c] = from_f32<T>((float)((double)to_f32(x[c]) - lz));
 }
 
 // dX = dY - exp(Y) * sum_v dY   (Y = the log-probabilities the forward produced)

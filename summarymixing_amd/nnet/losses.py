@@ -28,13 +28,18 @@ class _CTC(torch.autograd.Function):
 
 def ctc_loss(log_probs, targets, input_lens, target_lens, blank_index, reduction="mean"):
     """speechbrain.nnet.losses.ctc_loss.  log_probs (B, T, V) log-softmax outputs (CUDA, fp32 or bf16); targets
-    (B, S) integer tokens (padded); input_lens / target_lens RELATIVE lengths in (0, 1] as everywhere in SpeechBrain."""
+    (B, S) integer tokens (padded); input_lens / target_lens RELATIVE lengths in (0, 1] as everywhere in SpeechBrain.
+    targets of shape (B, 0) (no label in the whole batch) are accepted: every target is empty and the loss of an utterance is
+    -sum_{t < T_b} log_probs[b, t, blank], as torch has it.  An utterance without an alignment (too few frames for its labels,
+    no frame at all) has loss 0 and gradient 0 (zero_infinity=True)."""
     if not log_probs.is_cuda:
         raise RuntimeError("summarymixing_amd.nnet.losses.ctc_loss runs on the GPU only (no CPU fallback)")
     B, T, V = log_probs.shape
     in_len = (input_lens.to(log_probs.device) * T).round().to(torch.int32)
     tgt_len = (target_lens.to(log_probs.device) * targets.shape[1]).round().to(torch.int32)
     tg = targets.to(device=log_probs.device, dtype=torch.int32).contiguous()
+    if tg.shape[1] == 0:                             # a (B, 0) tensor has no storage to point the kernels at: one column that
+        tg = tg.new_zeros((B, 1))                    # is never read (every tgt_len is round(rel * 0) = 0)
     nll = _CTC.apply(log_probs, tg, in_len, tgt_len, int(blank_index))
     if reduction == "mean":                          # torch: each loss / target length (>= 1), then the batch mean
         return (nll / tgt_len.clamp(min=1).to(nll.dtype)).mean()
