@@ -744,7 +744,9 @@ int smx_stream_advance(int dtype, uint64_t* counter, const void* table, int64_t 
                        void* stream);
 
 /* ---- Slot streaming: B independent streams, one per batch slot, in one fixed step of B x C rows --------------------------------
- * The lockstep calls above with per-slot state.  Row t of slot b is row b * C + t of every (B*C, .) operand.  counters (B,) int64
+ * The lockstep calls above with per-slot state: smx_slot_summary and smx_dwconv1d_glu_slots run the SAME kernel bodies as
+ * smx_stream_summary and smx_dwconv1d_glu_stream (a second instantiation, not a copy), which differ only in who holds which rows,
+ * where the chunk index comes from and the fresh-state rule below.  Row t of slot b is row b * C + t of every (B*C, .) operand.  counters (B,) int64
  * holds each slot's chunk index c (shared by all layers); counter 0 means fresh state: chunk 0 reads no ring slot, no running sum
  * and no convolution state, so a slot starts a new stream by counters[b] = 0 alone (smx_slot_begin) and no state buffer is
  * cleared.  valid (B,) int32 holds the frames of slot b in this step, 0 .. C: C = a full chunk, 1 .. C-1 = the stream's last,
@@ -752,7 +754,7 @@ int smx_stream_advance(int dtype, uint64_t* counter, const void* table, int64_t 
  * (they may hold NaN), and output rows at and beyond valid[b] are not written.  counters / valid / start are device arrays, so a
  * captured step stays valid on replay.  A step is smx_slot_begin, the layers, smx_slot_advance.
  * smx_slot_summary: smx_stream_summary per slot: window of chunk counters[b], frame count min(c, left) * C + valid[b]; for left = -1
- *   the running sum is written, not added to, at chunk 0.  Same fixed summation order: a full chunk gives the bits of
+ *   the running sum is written, not added to, at chunk 0.  One body, so one fixed summation order: a full chunk gives the bits of
  *   smx_stream_summary on the same inputs.  dtype F32 | BF16, D % 8 == 0, 1 <= C <= 64, -1 <= left <= 32, B <= 65535.
  * smx_dwconv1d_glu_slots: smx_dwconv1d_glu_stream per slot with C_cur = valid[b]: the state (B, H, 2D) reads as zero at chunk 0, and
  *   is rewritten in place with the last H rows of [state; chunk[:valid[b]]] (not at all for valid[b] == 0).  dtype F32 | BF16,

@@ -822,6 +822,17 @@ class DynChunkSlots:
         return ops.slot_summary(x, out, B, T, self.left_context, self.ring, self.counters, self.valid)
 
 
+class ConvStream:
+    """The depthwise convolution's streaming state: `state` (B, (k-1)/2, 2d), compute dtype, the last pre-GLU rows of each stream;
+    slot streaming adds the slots' device `valid` / `counters` (those of DynChunkSlots).  Passed as conv_module_fwd's conv_state."""
+
+    def __init__(self, state, valid=None, counters=None):
+        self.state, self.slots = state, () if valid is None else (valid, counters)
+
+    def conv(self, p, w, bias, B, T, D, k):
+        return (ops.dwconv_slots if self.slots else ops.dwconv_stream)(p, w, bias, self.state, *self.slots, B, T, D, k)
+
+
 class ExpDecaySummary:
     """SummaryMixing-expdecay without a sum_mask: (M s) / rowsum(M) with M_ij = decay^|i-j| is a two-sided exponential filter, run by
     the O(T) kernels (smx_expdecay_mean_*); M is symmetric, so the transposed operator is M (x / rowsum(M))."""
@@ -1286,15 +1297,12 @@ def ffn_module_fwd(x, P, act, need_bwd, dtype, alpha=0.5, p=0.0, pre_ln=None, ln
     bwd.pre = (alpha, None, d2)          # what this block does first to its incoming gradient: alpha * D2(dy)
     return ret(bwd)
 
-def conv_module_fwd(x, P, act, mask, B, T, need_bwd, dtype, chunk=0, residual=True, p=0.0, pre_ln=None, ln_next=None,
-                    conv_state=None, conv_slots=None):
+def conv_module_fwd(x, P, act, mask, B, T, need_bwd, dtype, chunk=0, residual=True, p=0.0, pre_ln=None, ln_next=None, conv_state=None):
     """y = [x +] mask * Linear(act(LN(dwconv(GLU(pw(LN(x)))))))   (Conformer.py:314-331,532-534).
     pre_ln / ln_next: as in ffn_module_fwd (the module's first LayerNorm done by the producer of x; the LayerNorm that
     follows the module done in the out-projection's epilogue).
-    conv_state: streaming inference - x is one chunk of T frames of B streams, the depthwise conv reads its left context from
-    this (B, (k-1)/2, 2d) state and updates it (ops.dwconv_stream).
-    conv_slots: slot streaming - (valid, counters), the device arrays of functional.DynChunkSlots: each of the B slots runs its own
-    stream at its own chunk (ops.dwconv_slots), T = C rows per slot of which valid[b] are real."""
+    conv_state: streaming inference - a ConvStream: x is one chunk of T frames of B streams (slot streaming: T = C rows per slot, of
+    which valid[b] are real); the depthwise conv reads its left context from that state and updates it."""
     d = x.shape[1]
     if SP.enabled():
         r = _conv_module_fwd_sp(x, P, act, mask, B, T, need_bwd, dtype, chunk, residual, p)
@@ -1304,15 +1312,13 @@ def conv_module_fwd(x, P, act, mask, B, T, need_bwd, dtype, chunk=0, residual=Tr
     p_, _ = linear_fwd(h, Wp, P["bp"], wparam=P["Wp"])
     k = P["wd"].shape[-1]
     wd = P["wd"].detach().reshape(d, k)
+    bd = P["bd"].detach() if P["bd"] is not None else None
     if conv_state is None:
-        c = ops.dwconv_fwd(p_, wd, P["bd"].detach() if P["bd"] is not None else None, B, T, d, k, True, L.PAD_ZERO, chunk)
+        c = ops.dwconv_fwd(p_, wd, bd, B, T, d, k, True, L.PAD_ZERO, chunk)
+    elif need_bwd:
+        raise NotImplementedError("streaming convolution: inference only")
     else:
-        if need_bwd:
-            raise NotImplementedError("streaming convolution: inference only")
-        if conv_slots is None:
-            c = ops.dwconv_stream(p_, wd, P["bd"].detach() if P["bd"] is not None else None, conv_state, B, T, d, k)
-        else:
-            c = ops.dwconv_slots(p_, wd, P["bd"].detach() if P["bd"] is not None else None, conv_state, *conv_slots, B, T, d, k)
+        c = conv_state.conv(p_, wd, bd, B, T, d, k)
     a, ln2_b = ln_fwd(c, P["ln2_w"], P["ln2_b"], 1e-5, need_bwd, act)      # LN + activation fused
     Wo = wcast(P["Wo"], dtype)
     dr = (p, ops.new_dropout_seed()) if p > 0.0 else None   # Linear -> Dropout -> * mask (+ x): one epilogue
@@ -1327,8 +1333,7 @@ def conv_module_fwd(x, P, act, mask, B, T, need_bwd, dtype, chunk=0, residual=Tr
         dc = (dgrad_ln_bwd(ln2_b, dz_in, a, Wo, P["Wo"], P["bo"], packed=False, dz_ready=True) if dz_in is not None else
               dgrad_ln_bwd(ln2_b, dy, a, Wo, P["Wo"], P["bo"], mask=mask, packed=False, drop=dr))
         gwd = gacc(P["wd"])
-        dp, _ = dwconv_bwd_deferred(dc, p_, wd, P["bd"].detach() if P["bd"] is not None else None, gwd.view(d, k),
-                                    gacc(P["bd"]), B, T, d, k, True, L.PAD_ZERO, chunk)
+        dp, _ = dwconv_bwd_deferred(dc, p_, wd, bd, gwd.view(d, k), gacc(P["bd"]), B, T, d, k, True, L.PAD_ZERO, chunk)
         return dgrad_ln_bwd(ln1_b, dp, h, Wp, P["Wp"], P["bp"], res=dy if residual else None, second=second)
     # what this block does first to its incoming gradient: D(dy) * mask (nothing to precompute without mask and dropout)
     bwd.pre = (1.0, mask, dr) if (mask is not None or dr is not None) else None

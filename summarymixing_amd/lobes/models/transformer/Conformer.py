@@ -283,16 +283,16 @@ class ConformerEncoderLayer(nn.Module):
         self.norm2 = _LayerNorm(d_model)
         self.drop = nn.Dropout(dropout)
 
-    def make_run(self, B, T, m8, src_mask, chunk, compute_dtype=None, next_layer=None, conv_state=None, conv_slots=None):
+    def make_run(self, B, T, m8, src_mask, chunk, compute_dtype=None, next_layer=None, conv_state=None):
         """compute_dtype: dtype of the GEMM operands when the incoming stream x3 is the float32 residual stream of a bf16
         model (functional.RESIDUAL_F32); None = everything in x3.dtype.
         next_layer: the layer that consumes this one's output inside an encoder stack.  Its first LayerNorm (ffn_module1's) then
         runs in the same pass as this layer's norm2 where the shapes allow (ops.layernorm_fwd_pair: one read of the float32 stream
         for both); run(..., with_post=True) then returns a third value, (LN(y), stats) | None, which the stack hands to the next
         layer's run as `pre_ln`.
-        Streaming inference (forward_streaming): src_mask is a functional.DynChunkStream and conv_state the layer's (B, (k-1)/2, 2d)
-        convolution state; T is then the frames of one chunk.  Slot streaming (forward_slots): src_mask is a functional.DynChunkSlots
-        and conv_slots its (valid, counters); B is the slot count and T the chunk size."""
+        Streaming inference (forward_streaming): src_mask is a functional.DynChunkStream and conv_state a functional.ConvStream over
+        the layer's convolution state; T is then the frames of one chunk.  Slot streaming (forward_slots): src_mask is a
+        functional.DynChunkSlots, conv_state carries the slots' valid / counters as well; B is the slot count and T the chunk size."""
         d_act = self.act
         P1, P2 = _ffn_params(self.ffn_module1), _ffn_params(self.ffn_module2)
         Pc = self.convolution_module.params()
@@ -314,8 +314,7 @@ class ConformerEncoderLayer(nn.Module):
             y2_3, bcell, post2 = cell(h.view(B, T, -1), need, res=y1, ln_next=(Pc["ln1_w"], Pc["ln1_b"], 1e-5))   # :512-530
             y2 = ops.rows2d(y2_3)
             y3, bconv, post3 = F.conv_module_fwd(y2, Pc, d_act, m8, B, T, need, dtype, chunk, p=pd, pre_ln=post2,
-                                                 ln_next=(P2["ln_w"], P2["ln_b"], 1e-5), conv_state=conv_state,
-                                                 conv_slots=conv_slots)                                           # :532-534
+                                                 ln_next=(P2["ln_w"], P2["ln_b"], 1e-5), conv_state=conv_state)   # :532-534
             # (norm2's output is the layer output = the next layer's residual stream: stream dtype, 4th element of ln_next)
             # (inside a stack: where norm2 rides in the second FFN's down-projection, the NEXT layer's first LayerNorm can ride with it)
             y4, bf2, post4, post_next = F.ffn_module_fwd(y3, P2, d_act, need, dtype, p=pd, pre_ln=post3, ln_next=(n2.weight, n2.bias, n2.eps, True),
@@ -383,34 +382,35 @@ class ConformerEncoderLayer(nn.Module):
         _stream_refuse(self, dynchunktrain_config)
         return ConformerEncoderLayerStreamingContext(dynchunktrain_config=dynchunktrain_config)
 
-    def _stream_alloc(self, ctx, B, compute, device, counter):
+    def _state_alloc(self, cfg, B, compute, device, new):
+        """-> (ring | None, convolution state) of B streams: the float32 per-chunk sums ((B, left, s); (B, s) running sums for an
+        unlimited left context; none for left 0) and the (B, (k-1)/2, 2 d) pre-GLU rows.  new: torch.zeros (lockstep reads its state
+        as stored) or torch.empty (a slot never reads state before it wrote it)."""
         d = self.norm1.norm.weight.shape[0]
         sdim = self.mha_layer.local_proj_out_dim if self.mode == "SummaryMixing-fast" else self.mha_layer.summary_out_dim
-        left = ctx.dynchunktrain_config.left_context_size
-        ring = (torch.zeros((B, sdim), dtype=torch.float32, device=device) if left is None else
-                torch.zeros((B, left, sdim), dtype=torch.float32, device=device) if left > 0 else None)
-        ctx.summary = F.DynChunkStream(ring, counter, ctx.dynchunktrain_config.chunk_size, left)
-        H = (self.convolution_module.kernel_size - 1) // 2
-        ctx.dcconv_state = torch.zeros((B, H, 2 * d), dtype=compute, device=device)
+        left = cfg.left_context_size
+        ring = (new((B, sdim), dtype=torch.float32, device=device) if left is None else
+                new((B, left, sdim), dtype=torch.float32, device=device) if left > 0 else None)
+        return ring, new((B, (self.convolution_module.kernel_size - 1) // 2, 2 * d), dtype=compute, device=device)
+
+    def _stream_alloc(self, ctx, B, compute, device, counter):
+        cfg = ctx.dynchunktrain_config
+        ring, ctx.dcconv_state = self._state_alloc(cfg, B, compute, device, torch.zeros)
+        ctx.summary = F.DynChunkStream(ring, counter, cfg.chunk_size, cfg.left_context_size)
         ctx.counter, ctx.batch_size, ctx.dtype, ctx.device = counter, B, compute, torch.device(device)
 
     def _stream_run(self, ctx, B, C_cur, compute_dtype=None, next_layer=None):
         return self.make_run(B, C_cur, None, ctx.summary, 0, compute_dtype=compute_dtype, next_layer=next_layer,
-                             conv_state=ctx.dcconv_state)
+                             conv_state=F.ConvStream(ctx.dcconv_state))
 
     def _slot_alloc(self, lc, enc_ctx, B, compute, device):
-        d = self.norm1.norm.weight.shape[0]
-        sdim = self.mha_layer.local_proj_out_dim if self.mode == "SummaryMixing-fast" else self.mha_layer.summary_out_dim
-        left = lc.dynchunktrain_config.left_context_size
-        ring = (torch.empty((B, sdim), dtype=torch.float32, device=device) if left is None else
-                torch.empty((B, left, sdim), dtype=torch.float32, device=device) if left > 0 else None)
-        lc.summary = F.DynChunkSlots(ring, enc_ctx.counters, enc_ctx.valid, lc.dynchunktrain_config.chunk_size, left)
-        H = (self.convolution_module.kernel_size - 1) // 2
-        lc.dcconv_state = torch.empty((B, H, 2 * d), dtype=compute, device=device)   # (never read before a slot writes it)
+        cfg = lc.dynchunktrain_config
+        ring, lc.dcconv_state = self._state_alloc(cfg, B, compute, device, torch.empty)
+        lc.summary = F.DynChunkSlots(ring, enc_ctx.counters, enc_ctx.valid, cfg.chunk_size, cfg.left_context_size)
 
     def _slot_run(self, lc, enc_ctx, B, C, compute_dtype=None, next_layer=None):
         return self.make_run(B, C, None, lc.summary, 0, compute_dtype=compute_dtype, next_layer=next_layer,
-                             conv_state=lc.dcconv_state, conv_slots=(enc_ctx.valid, enc_ctx.counters))
+                             conv_state=F.ConvStream(lc.dcconv_state, enc_ctx.valid, enc_ctx.counters))
 
     def forward_streaming(self, x, context: ConformerEncoderLayerStreamingContext, pos_embs: torch.Tensor = None):
         """One chunk (B, C_cur, d) of a stream through this layer (reference :539-616).  Returns (output, None); the context

@@ -219,15 +219,18 @@ class TransformerASR(nn.Module):
         first = ec.batch_size is None
         self.encoder._stream_begin(ec, B, C_cur, src.dtype, src.device)
         if first:
-            C, d = ec.dynchunktrain_config.chunk_size, self.custom_src_module.layers[0].w.weight.shape[0]
-            if self.positional_encoding_type == "fixed_abs_sine":
-                ec.pe_table = self.positional_encoding.pe[0]
-                ec.pe = torch.zeros((C, d), dtype=ec.pe_table.dtype, device=src.device)
-                n = min(C, ec.pe_table.shape[0])
+            self._pe_alloc(ec, ec.dynchunktrain_config.chunk_size, src.device)
+            if ec.pe_table is not None:
+                n = min(ec.pe.shape[0], ec.pe_table.shape[0])
                 ec.pe[:n] = ec.pe_table[:n]            # chunk 0's rows; smx_stream_advance writes the later ones
-            else:
-                ec.pe = torch.zeros((C, d), device=src.device)
         return ec
+
+    def _pe_alloc(self, ec, rows, device):
+        """ec.pe = the (rows, d) positional rows of a step, zero; with the fixed sine table, ec.pe_table = it and pe has its dtype."""
+        if self.positional_encoding_type == "fixed_abs_sine":
+            ec.pe_table = self.positional_encoding.pe[0]
+        ec.pe = torch.zeros((rows, self.custom_src_module.layers[0].w.weight.shape[0]), device=device,
+                            dtype=ec.pe_table.dtype if ec.pe_table is not None else None)
 
     def _stream_chunk(self, src, ec):
         """The launches of one chunk step: input projection + the chunk's PE rows, the encoder, the counter / PE advance."""
@@ -273,12 +276,7 @@ class TransformerASR(nn.Module):
                     raise ValueError(f"slot streaming: slot {b} reaches frame {f + v}, beyond max_length "
                                      f"{self.positional_encoding.max_len}")
         if ec.pe is None:
-            B, C, d = ec.slots, ec.dynchunktrain_config.chunk_size, self.custom_src_module.layers[0].w.weight.shape[0]
-            if self.positional_encoding_type == "fixed_abs_sine":
-                ec.pe_table = self.positional_encoding.pe[0]
-                ec.pe = torch.zeros((B * C, d), dtype=ec.pe_table.dtype, device=src.device)
-            else:
-                ec.pe = torch.zeros((B * C, d), device=src.device)
+            self._pe_alloc(ec, ec.slots * ec.dynchunktrain_config.chunk_size, src.device)
         return ec, args
 
     def _slot_chunk(self, src, ec):

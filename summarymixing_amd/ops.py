@@ -476,17 +476,22 @@ def chunk_mean(s, out, B, T, chunk, left, reverse=False):
     return out
 
 
-def stream_summary(s, out, B, C_cur, C, left, ring, counter):
-    """Streaming DynChunk summary of one chunk (smx_stream_summary): out (B*C_cur, D) rows = the window mean of chunk `counter`;
-    the chunk's float32 sums go into `ring` ((B, left, D); (B, D) running sums for left = None; unused for left = 0)."""
+def _chunk_summary(name, s, out, B, T, ptrs, dims, left):
+    """The launch stream_summary and slot_summary share (smx_<name>; T rows per stream; ptrs / dims: each one's state and sizes)."""
     D = s.shape[1]
     ps, lds = _mat(s)
     po, ldo = _mat(out)
-    tok = _pb(f"stream_summary ({B},{C_cur},{D})", 2 * B * C_cur * D * _es(s))
-    L.check(L.lib().smx_stream_summary(dt(s), ps, lds, po, ldo, _p(ring), _p(counter), B, C_cur, C, D, -1 if left is None else left,
-                                       _stream()), "smx_stream_summary")
+    tok = _pb(f"{name} ({B},{T},{D})", 2 * B * T * D * _es(s))
+    L.check(getattr(L.lib(), "smx_" + name)(dt(s), ps, lds, po, ldo, *map(_p, ptrs), B, *dims, D, -1 if left is None else left,
+                                            _stream()), "smx_" + name)
     _pe(tok)
     return out
+
+
+def stream_summary(s, out, B, C_cur, C, left, ring, counter):
+    """Streaming DynChunk summary of one chunk (smx_stream_summary): out (B*C_cur, D) rows = the window mean of chunk `counter`;
+    the chunk's float32 sums go into `ring` ((B, left, D); (B, D) running sums for left = None; unused for left = 0)."""
+    return _chunk_summary("stream_summary", s, out, B, C_cur, (ring, counter), (C_cur, C), left)
 
 
 def expdecay_mean(s, out, B, T, decay, reverse=False):
@@ -652,17 +657,22 @@ def dwconv_fwd(p, w, bias, B, T, D, k, glu, pad_mode=L.PAD_ZERO, chunk=0, gate=N
     return y
 
 
+def _chunk_dwconv(kind, p, w, bias, state, slots, B, T, D, k):
+    """The launch dwconv_stream and dwconv_slots share (smx_dwconv1d_glu_<kind>; T rows per stream; slots: () | (valid, counters))."""
+    assert state.dtype == p.dtype and state.is_contiguous() and state.shape == (B, (k - 1) // 2, 2 * D)
+    y = torch.empty((B * T, D), dtype=p.dtype, device=p.device)
+    pp, ldp = _mat(p)
+    tok = _pb(f"dwconv_{kind} ({B},{T},{D}) k={k}", 3 * B * T * D * _es(p))
+    L.check(getattr(L.lib(), "smx_dwconv1d_glu_" + kind)(dt(p), pp, ldp, _p(w), _p(bias), _p(state), _p(y), D, *map(_p, slots), B, T, D,
+                                                         k, _stream()), "smx_dwconv1d_glu_" + kind)
+    _pe(tok)
+    return y
+
+
 def dwconv_stream(p, w, bias, state, B, C_cur, D, k):
     """GLU + depthwise conv over one chunk of B streams (smx_dwconv1d_glu_stream): rows before the chunk come from `state`
     ((B, (k-1)/2, 2D), compute dtype), which the kernel then replaces in place with the chunk's last (k-1)/2 pre-GLU rows."""
-    assert state.dtype == p.dtype and state.is_contiguous() and state.shape == (B, (k - 1) // 2, 2 * D)
-    y = torch.empty((B * C_cur, D), dtype=p.dtype, device=p.device)
-    pp, ldp = _mat(p)
-    tok = _pb(f"dwconv_stream ({B},{C_cur},{D}) k={k}", 3 * B * C_cur * D * _es(p))
-    L.check(L.lib().smx_dwconv1d_glu_stream(dt(p), pp, ldp, _p(w), _p(bias), _p(state), _p(y), D, B, C_cur, D, k, _stream()),
-            "smx_dwconv1d_glu_stream")
-    _pe(tok)
-    return y
+    return _chunk_dwconv("stream", p, w, bias, state, (), B, C_cur, D, k)
 
 
 def stream_advance(counter, table, pe, C):
@@ -677,27 +687,13 @@ def stream_advance(counter, table, pe, C):
 def slot_summary(s, out, B, C, left, ring, counters, valid):
     """Per-slot streaming DynChunk summary (smx_slot_summary): s / out (B*C, D), slot b's rows b*C .. b*C + valid[b] - 1 = the window
     mean of its chunk counters[b]; `valid` (B,) int32 and `counters` (B,) int64 on the device.  Slots with valid 0 are untouched."""
-    D = s.shape[1]
-    ps, lds = _mat(s)
-    po, ldo = _mat(out)
-    tok = _pb(f"slot_summary ({B},{C},{D})", 2 * B * C * D * _es(s))
-    L.check(L.lib().smx_slot_summary(dt(s), ps, lds, po, ldo, _p(ring), _p(counters), _p(valid), B, C, D, -1 if left is None else left,
-                                     _stream()), "smx_slot_summary")
-    _pe(tok)
-    return out
+    return _chunk_summary("slot_summary", s, out, B, C, (ring, counters, valid), (C,), left)
 
 
 def dwconv_slots(p, w, bias, state, valid, counters, B, C, D, k):
     """GLU + depthwise conv of one slot step (smx_dwconv1d_glu_slots): dwconv_stream per slot with C_cur = valid[b]; the state reads
     as zero where counters[b] == 0 and is left untouched where valid[b] == 0."""
-    assert state.dtype == p.dtype and state.is_contiguous() and state.shape == (B, (k - 1) // 2, 2 * D)
-    y = torch.empty((B * C, D), dtype=p.dtype, device=p.device)
-    pp, ldp = _mat(p)
-    tok = _pb(f"dwconv_slots ({B},{C},{D}) k={k}", 3 * B * C * D * _es(p))
-    L.check(L.lib().smx_dwconv1d_glu_slots(dt(p), pp, ldp, _p(w), _p(bias), _p(state), _p(y), D, _p(valid), _p(counters), B, C, D, k,
-                                           _stream()), "smx_dwconv1d_glu_slots")
-    _pe(tok)
-    return y
+    return _chunk_dwconv("slots", p, w, bias, state, (valid, counters), B, C, D, k)
 
 
 def slot_begin(counters, start, table, pe, B, C, D):

@@ -14,32 +14,40 @@ import torch
 from .lobes.models.transformer.TransformerASR import EncoderWrapper
 
 
-class CapturedStreamStep:
-    """step(chunk) = encode_streaming(chunk, context) as one graph replay.  chunk: (B, C, F) on the device, dtype `dtype`.  The
-    returned tensor is a static buffer, overwritten by the next step.  A short final chunk runs eagerly on the same context
-    (finish).  The graph is captured on one stream (thread_local capture mode) and has no parallel branches."""
+class _CapturedStep:
+    """The capture recipe both steps share.  The static input buffer; `warm_up(x)`, a step on a scratch context on a side stream
+    (allocates weight shadows and workspaces outside the capture; the real context is untouched); `begin(x)` validates and allocates
+    the real context's state without a launch and returns the encoder context; then the launches of `chunk(x, ec)` are captured on
+    one stream (thread_local capture mode): the graph has no parallel branches, and capture does not advance the context."""
 
-    def __init__(self, wrapper, context, B, C, dtype=torch.float32, device=None):
-        asr = wrapper.transformer if isinstance(wrapper, EncoderWrapper) else wrapper
+    def __init__(self, asr, context, B, C, dtype, device, warm_up, begin, chunk):
         self.asr, self.context, self.B, self.C = asr, context, B, C
-        if C != context.dynchunktrain_config.chunk_size:
-            raise ValueError(f"CapturedStreamStep: C={C} differs from the context's chunk_size")
         lin = asr.custom_src_module.layers[0].w
         device = device or lin.weight.device
         self.x = torch.zeros((B, C, lin.weight.shape[1]), dtype=dtype, device=device)
-        # warm-up on a scratch context (allocates weight shadows and workspaces outside the capture; the real context is untouched)
-        scratch = asr.make_streaming_context(context.dynchunktrain_config)
         side = torch.cuda.Stream(device)
         side.wait_stream(torch.cuda.current_stream(device))
         with torch.cuda.stream(side):
-            asr.encode_streaming(self.x, scratch)
+            warm_up(self.x)
         torch.cuda.current_stream(device).wait_stream(side)
-        ec = asr._stream_begin(self.x, context)            # validates and allocates the real context's state (no launch)
+        self._ec = begin(self.x)
         torch.cuda.synchronize(device)
         self.graph = torch.cuda.CUDAGraph()
         with torch.no_grad(), torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-            self.y = asr._stream_chunk(self.x, ec)
-        self._ec = ec
+            self.y = chunk(self.x, self._ec)
+
+
+class CapturedStreamStep(_CapturedStep):
+    """step(chunk) = encode_streaming(chunk, context) as one graph replay.  chunk: (B, C, F) on the device, dtype `dtype`.  The
+    returned tensor is a static buffer, overwritten by the next step.  A short final chunk runs eagerly on the same context
+    (finish)."""
+
+    def __init__(self, wrapper, context, B, C, dtype=torch.float32, device=None):
+        asr, cfg = wrapper.transformer if isinstance(wrapper, EncoderWrapper) else wrapper, context.dynchunktrain_config
+        if C != cfg.chunk_size:
+            raise ValueError(f"CapturedStreamStep: C={C} differs from the context's chunk_size")
+        super().__init__(asr, context, B, C, dtype, device, lambda x: asr.encode_streaming(x, asr.make_streaming_context(cfg)),
+                         lambda x: asr._stream_begin(x, context), asr._stream_chunk)
 
     def step(self, chunk):
         """One full chunk (B, C, F) through the captured step."""
@@ -56,35 +64,20 @@ class CapturedStreamStep:
         return self.asr.encode_streaming(chunk, self.context)
 
 
-class CapturedSlotStep:
+class CapturedSlotStep(_CapturedStep):
     """step(chunk, valid, start) = encode_slots(chunk, valid, start, context) as one graph replay.  chunk: (B, C, F) on the device,
     dtype `dtype`; valid / start: host sequences of B ints / bools, validated and staged into the context's static device buffers
     before the replay.  The returned tensor is a static buffer, overwritten by the next step; rows at and beyond valid[b] are
-    unspecified.  A stream's short last chunk runs through the same graph (valid expresses it).  Capture runs after a warm-up on a
-    scratch context and does not advance the context; the graph is captured on one stream and has no parallel branches."""
+    unspecified.  A stream's short last chunk runs through the same graph (valid expresses it)."""
 
     def __init__(self, wrapper, context, B, C, dtype=torch.float32, device=None):
-        asr = wrapper.transformer if isinstance(wrapper, EncoderWrapper) else wrapper
-        self.asr, self.context, self.B, self.C = asr, context, B, C
-        if C != context.dynchunktrain_config.chunk_size or B != context.encoder_context.slots:
+        asr, cfg = wrapper.transformer if isinstance(wrapper, EncoderWrapper) else wrapper, context.dynchunktrain_config
+        if C != cfg.chunk_size or B != context.encoder_context.slots:
             raise ValueError(f"CapturedSlotStep: (B, C) = ({B}, {C}) differs from the context's ({context.encoder_context.slots}, "
-                             f"{context.dynchunktrain_config.chunk_size})")
-        lin = asr.custom_src_module.layers[0].w
-        device = device or lin.weight.device
-        self.x = torch.zeros((B, C, lin.weight.shape[1]), dtype=dtype, device=device)
-        # warm-up on a scratch context (allocates weight shadows and workspaces outside the capture; the real context is untouched)
-        scratch = asr.make_slot_context(context.dynchunktrain_config, B)
-        side = torch.cuda.Stream(device)
-        side.wait_stream(torch.cuda.current_stream(device))
-        with torch.cuda.stream(side):
-            asr.encode_slots(self.x, [C] * B, [True] * B, scratch)
-        torch.cuda.current_stream(device).wait_stream(side)
-        ec, _ = asr._slot_begin(self.x, [0] * B, [False] * B, context)   # validates and allocates the real context (no launch)
-        torch.cuda.synchronize(device)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.no_grad(), torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-            self.y = asr._slot_chunk(self.x, ec)
-        self._ec = ec
+                             f"{cfg.chunk_size})")
+        super().__init__(asr, context, B, C, dtype, device,
+                         lambda x: asr.encode_slots(x, [C] * B, [True] * B, asr.make_slot_context(cfg, B)),
+                         lambda x: asr._slot_begin(x, [0] * B, [False] * B, context)[0], asr._slot_chunk)
 
     def step(self, chunk, valid, start):
         """One slot step (B, C, F) through the captured graph."""
