@@ -398,26 +398,35 @@ size_t smx_layernorm_bwd_workspace(int N, int D);
  * glu=0: u = P (ldp >= D).  pad SMX_PAD_ZERO (Conformer) | SMX_PAD_REFLECT (Branchformer CSGU).
  * chunk > 0: Dynamic Chunk Convolution (Conformer.py:190-313): inputs at or beyond the end of the output
  * frame's own chunk read as zero.  gate != NULL: Y *= gate (CSGU x1*x2).  w (D,k) fp32, bias (D) fp32. */
-int smx_dwconv1d_glu_fwd(int dtype, const void* P, int64_t ldp, const float* w, const float* bias,
-                         const void* gate, int64_t ldg, void* Y, int64_t ldy, int B, int T, int D, int k, int glu,
-                         int pad_mode, int chunk, void* stream);
-/* Same with an inverted dropout of the output fused in (mask index = global row * D + channel, as smx_dropout on Y):
- * the CSGU's own dropout (upstream ConvolutionalSpatialGatingUnit.forward).  Only the rolling CSGU kernel carries it
- * (bf16, k = 31, gate, reflect padding, D % 64 == 0, aligned rows); SMX_EUNSUPPORTED otherwise - run smx_dropout. */
-int smx_dwconv1d_glu_fwd_drop(int dtype, const void* P, int64_t ldp, const float* w, const float* bias,
-                              const void* gate, int64_t ldg, void* Y, int64_t ldy, int B, int T, int D, int k, int glu,
-                              int pad_mode, int chunk, float drop_p, uint64_t drop_seed, const uint64_t* epoch, void* stream);
-/* dP (same shape as P), dw/dbias += ; dgate optional (= dY * conv).  workspace: smx_dwconv1d_glu_bwd_workspace bytes
- * (per-block partial tap gradients of the fast path, reduced in a fixed order; NULL selects the generic kernel).
- * dw == NULL (and dbias == NULL): the partial rows [smx_dwconv1d_glu_bwd_partial_rows][D][k+1] (taps, then the bias term)
- * stay in the workspace for smx_reduce_jobs (two jobs with src_ld = k+1); SMX_EUNSUPPORTED outside the k = 31 path. */
-size_t smx_dwconv1d_glu_bwd_workspace(int B, int T, int D, int k);
-/* how many partial rows the call below leaves in the workspace for these arguments (the nsrc of the two reduction jobs) */
-int smx_dwconv1d_glu_bwd_partial_rows(int dtype, int B, int T, int D, int k, int glu, int pad_mode, int chunk, int has_gate);
-int smx_dwconv1d_glu_bwd(int dtype, const void* dY, int64_t lddy, const void* P, int64_t ldp, const float* w,
-                         const float* bias, const void* gate, int64_t ldg, void* dP, int64_t lddp, void* dgate,
-                         int64_t lddg, float* dw, float* dbias, int B, int T, int D, int k, int glu, int pad_mode,
-                         int chunk, void* workspace, void* stream);
+/* One descriptor for both directions (zero it, then set what the call uses); the backward reads dY through Y / ldy.
+ * drop_p > 0 (forward): inverted dropout of Y fused in (mask index = global row * D + channel, as smx_dropout on Y) - the CSGU's
+ * own dropout (upstream ConvolutionalSpatialGatingUnit.forward); SMX_EUNSUPPORTED off the rolling CSGU route - run smx_dropout. */
+typedef struct smx_dwconv_args {
+  int32_t dtype;       int32_t glu;
+  const void* P;       int64_t ldp;
+  const float* w;      const float* bias;
+  const void* gate;    int64_t ldg;          /* or NULL                                                                     */
+  void* Y;             int64_t ldy;          /* forward: the output; backward: dY (read only)                               */
+  void* dP;            int64_t lddp;         /* backward: same shape as P                                                   */
+  void* dgate;         int64_t lddg;         /* backward: = dY * conv, with gate                                            */
+  float* dw;           float* dbias;         /* backward: += ; both NULL = leave the partial rows in the workspace          */
+  void* workspace;                           /* backward: smx_dwconv1d_glu_bwd_workspace bytes, or NULL                     */
+  int32_t B, T, D, k, pad_mode, chunk;
+  float drop_p;        int32_t pad_;
+  uint64_t drop_seed;  const uint64_t* epoch;
+} smx_dwconv_args;
+/* The kernel family a call gets and its launch: route SMX_DW_*; chunked = Dynamic Chunk Convolution; deferrable
+ * (backward): dw == NULL may leave the partial_rows rows [D][k+1] (taps, then the bias term) in the workspace; grid of the main
+ * kernel (grid[0] == 0: empty shape, no launch); rolling routes: seg frames per wave segment, nseg segments per utterance. */
+enum { SMX_DW_TILED = 0, SMX_DW_WINDOW = 1, SMX_DW_ROLL = 2, SMX_DW_ROLL_CSGU = 3 };
+typedef struct smx_dwconv_plan { int32_t route, chunked, deferrable, partial_rows, grid[3], seg, nseg, pad_; } smx_dwconv_plan;
+int smx_dwconv_fwd(const smx_dwconv_args* a, void* stream);
+/* dw / dbias += the partial tap gradients in `workspace`, reduced in a fixed order (NULL: the tiled kernel with atomics).  dw == NULL:
+ * the plan's partial_rows rows stay there for smx_reduce_jobs (two jobs with src_ld = k+1); SMX_EUNSUPPORTED if not deferrable. */
+int smx_dwconv_bwd(const smx_dwconv_args* a, void* stream);
+/* The checks and the decision of the two calls above for this descriptor, without a launch (needs no GPU). */
+int smx_dwconv_plan_query(const smx_dwconv_args* a, int backward, smx_dwconv_plan* plan);
+size_t smx_dwconv1d_glu_bwd_workspace(int B, int T, int D, int k);   /* bytes that hold the partial rows of every route */
 
 /* ---- front-end (arithmetic lives in un-vendored SpeechBrain: parity unpinned, spec = oracle) ----
  * Log-mel filterbank (speechbrain.lobes.features.Fbank, ...transducer.yaml:171-175):
@@ -695,7 +704,7 @@ int smx_expdecay_mean_sharded(int dtype, const void* S, int64_t lds, void* out, 
 
 /* Device step counter (one uint64 in device memory) - an explicit ARGUMENT of every call that uses it, never library
  * state: `epoch` of smx_dropout / smx_masked_mean_bwd(_act) / smx_act_mask_bwd / smx_layernorm_bwd (dX2) /
- * smx_dwconv1d_glu_fwd_drop, smx_epilogue.epoch of the GEMMs, `step_dev` of smx_adamw_step.  With a non-NULL counter a
+ * smx_dwconv_args.epoch, smx_epilogue.epoch of the GEMMs, `step_dev` of smx_adamw_step.  With a non-NULL counter a
  * fused / standalone dropout mixes the counter's current value into its seed and smx_adamw_step with step <= 0 takes its
  * bias-correction step from it: a whole training step can then be captured ONCE in a hipGraph (all kernel arguments
  * constant) and replayed - masks and bias correction still advance, because the counter does (smx_step_counter_add is
@@ -728,7 +737,7 @@ int smx_clip_factor(const float* sumsq, float max_norm, float inv_scale, float* 
  *   float32 sums go into the state: ring (B, left, D) float32, slot c % left (left = -1: ring (B, D) is a running sum; left = 0:
  *   ring unused, may be NULL).  Fixed summation order, no atomics.  dtype F32 | BF16, D % 8 == 0, 1 <= C_cur <= C <= 64,
  *   -1 <= left <= 32.
- * smx_dwconv1d_glu_stream: smx_dwconv1d_glu_fwd's u / Y (glu = 1, zero padding, bias) over one chunk with Dynamic Chunk Convolution.
+ * smx_dwconv1d_glu_stream: smx_dwconv_fwd's u / Y (glu = 1, zero padding, bias) over one chunk with Dynamic Chunk Convolution.
  *   P (B*C_cur, 2D) pre-GLU rows of the chunk; state (B, H, 2D), H = (k-1)/2, contiguous, compute dtype: the last H pre-GLU rows
  *   before the chunk (zeros before the first: the full forward's zero padding at t < 0).  Y[b, t] reads X = [state; chunk] at
  *   t .. t + k - 1, zero at and beyond the chunk's end.  The state is rewritten IN PLACE with the last H rows of [state; chunk]

@@ -21,6 +21,7 @@ EPI_LN_BWD = 4
 EPI_LN_FWD = 8
 IO_RES_F32, IO_LNX_F32, IO_LNFY_F32 = 1, 2, 4
 PAD_ZERO, PAD_REFLECT = 0, 1
+DW_TILED, DW_WINDOW, DW_ROLL, DW_ROLL_CSGU = 0, 1, 2, 3
 ACTS = {"none": ACT_NONE, "identity": ACT_NONE, "gelu": ACT_GELU, "swish": ACT_SWISH,
         "leaky_relu": ACT_LEAKY_RELU, "relu": ACT_RELU}
 
@@ -95,6 +96,20 @@ class LnBwd(ctypes.Structure):
                 ("zact", ctypes.c_int32), ("N", ctypes.c_int32), ("D", ctypes.c_int32), ("pad_", ctypes.c_int32)]
 
 
+class DwconvArgs(ctypes.Structure):
+    """smx_dwconv_args of include/smx.h (Y / ldy carry dY in the backward)."""
+    _fields_ = [("dtype", ctypes.c_int32), ("glu", ctypes.c_int32), ("P", c_vp), ("ldp", c_i64), ("w", c_vp), ("bias", c_vp), ("gate", c_vp),
+                ("ldg", c_i64), ("Y", c_vp), ("ldy", c_i64), ("dP", c_vp), ("lddp", c_i64), ("dgate", c_vp), ("lddg", c_i64), ("dw", c_vp),
+                ("dbias", c_vp), ("workspace", c_vp)] + [(n, ctypes.c_int32) for n in ("B", "T", "D", "k", "pad_mode", "chunk")] + [
+                ("drop_p", c_f), ("pad_", ctypes.c_int32), ("drop_seed", ctypes.c_uint64), ("epoch", c_vp)]
+
+
+class DwconvPlan(ctypes.Structure):
+    """smx_dwconv_plan of include/smx.h: the route and geometry smx_dwconv_fwd / _bwd take (smx_dwconv_plan_query)."""
+    _fields_ = [(n, ctypes.c_int32 * 3 if n == "grid" else ctypes.c_int32)
+                for n in ("route", "chunked", "deferrable", "partial_rows", "grid", "seg", "nseg", "pad_")]
+
+
 # name -> (restype, argtypes); mirrors include/smx.h one to one (tests/test_abi.py checks the export list)
 SIGNATURES = {
     "smx_version": (c_i, []),
@@ -144,14 +159,10 @@ SIGNATURES = {
     "smx_layernorm_fwd": (c_i, [ctypes.POINTER(LnFwd), c_vp]),
     "smx_layernorm_bwd_workspace": (c_sz, [c_i, c_i]),
     "smx_layernorm_bwd": (c_i, [ctypes.POINTER(LnBwd), c_vp]),
-    "smx_dwconv1d_glu_fwd": (c_i, [c_i, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i, c_i, c_i, c_i, c_i,
-                                   c_i, c_i, c_vp]),
-    "smx_dwconv1d_glu_fwd_drop": (c_i, [c_i, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i, c_i, c_i, c_i, c_i,
-                                        c_i, c_i, c_f, ctypes.c_uint64, c_vp, c_vp]),
+    "smx_dwconv_fwd": (c_i, [ctypes.POINTER(DwconvArgs), c_vp]),
+    "smx_dwconv_bwd": (c_i, [ctypes.POINTER(DwconvArgs), c_vp]),
+    "smx_dwconv_plan_query": (c_i, [ctypes.POINTER(DwconvArgs), c_i, ctypes.POINTER(DwconvPlan)]),
     "smx_dwconv1d_glu_bwd_workspace": (c_sz, [c_i, c_i, c_i, c_i]),
-    "smx_dwconv1d_glu_bwd_partial_rows": (c_i, [c_i] * 9),
-    "smx_dwconv1d_glu_bwd": (c_i, [c_i, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64,
-                                   c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_vp, c_vp]),
     "smx_dft_frames": (c_i, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i, c_i, c_i, c_i, c_i, c_i, c_vp]),
     "smx_frame_window": (c_i, [c_vp, c_i64, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_vp]),
     "smx_fbank_workspace": (c_sz, [c_i, c_i, c_i]),

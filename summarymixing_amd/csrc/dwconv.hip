@@ -570,101 +570,92 @@ __global__ __launch_bounds__(256) void dw_partials_reduce_kernel(const float* __
 
 using namespace smx;
 
-// does a rolling register-window path (dwconv_roll.h) take this call?  1 = GLU + zero padding (bf16 and fp32),
-// 2 = CSGU gate + reflect padding (bf16)
-static int roll_kind(int dtype, int T, int D, int k, int glu, int pad_mode, int chunk, bool has_gate) {
-  if (k != 31 || D % 64 != 0) return 0;
-  // (Dynamic Chunk Convolution, chunk > 0, is part of the GLU kernels)
-  if (glu && !has_gate && pad_mode == SMX_PAD_ZERO) return 1;
-  if (chunk <= 0 && !glu && has_gate && pad_mode == SMX_PAD_REFLECT && dtype == SMX_BF16 && T > 15) return 2;
-  return 0;
+// ---- host side.  dw_plan is the only place that looks at k, D, alignment, padding, gate, chunk, dtype and workspace: it
+// names the route and the launch geometry or refuses; smx_dwconv_fwd / smx_dwconv_bwd launch what it names and
+// smx_dwconv_plan_query hands it out (DESIGN.md "Depthwise conv routes").
+static int tiles_of(int n, int tile) { return (n + tile - 1) / tile; }
+
+// partial rows of the tiled and window backward: ~1024 persistent blocks in total, at most one per (batch, time tile)
+static long tiled_rows(int B, int T, int D) {
+  const long total = (long)B * tiles_of(T, DW_TT), gy = tiles_of(1024, tiles_of(D, DW_CT));
+  return gy < total ? gy : total;
 }
 
-static int dwconv_fwd_impl(int dtype, const void* P, int64_t ldp, const float* w, const float* bias, const void* gate, int64_t ldg,
-                           void* Y, int64_t ldy, int B, int T, int D, int k, int glu, int pad_mode, int chunk, float drop_p,
-                           uint64_t drop_seed, const uint64_t* epoch, void* stream);
-
-extern "C" int smx_dwconv1d_glu_fwd(int dtype, const void* P, int64_t ldp, const float* w, const float* bias,
-                                    const void* gate, int64_t ldg, void* Y, int64_t ldy, int B, int T, int D, int k,
-                                    int glu, int pad_mode, int chunk, void* stream) {
-  return dwconv_fwd_impl(dtype, P, ldp, w, bias, gate, ldg, Y, ldy, B, T, D, k, glu, pad_mode, chunk, 0.f, 0, nullptr, stream);
+// every operand of the call has a row stride that is a multiple of v elements and a 16-byte aligned base
+static bool dw_aligned(const smx_dwconv_args& a, bool bwd, int v) {
+  auto ok = [v](const void* p, int64_t ld) { return ld % v == 0 && aligned16(p); };
+  return ok(a.P, a.ldp) && ok(a.Y, a.ldy) && (!a.gate || ok(a.gate, a.ldg)) &&
+         (!bwd || (ok(a.dP, a.lddp) && (!a.gate || ok(a.dgate, a.lddg))));
 }
 
-extern "C" int smx_dwconv1d_glu_fwd_drop(int dtype, const void* P, int64_t ldp, const float* w, const float* bias,
-                                         const void* gate, int64_t ldg, void* Y, int64_t ldy, int B, int T, int D, int k,
-                                         int glu, int pad_mode, int chunk, float drop_p, uint64_t drop_seed, const uint64_t* epoch, void* stream) {
-  SMX_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "smx_dwconv1d_glu_fwd_drop: 0 <= drop_p < 1");
-  return dwconv_fwd_impl(dtype, P, ldp, w, bias, gate, ldg, Y, ldy, B, T, D, k, glu, pad_mode, chunk, drop_p, drop_seed, epoch, stream);
+static int dw_plan(const smx_dwconv_args& a, bool bwd, smx_dwconv_plan* pl) {
+  const char* who = bwd ? "smx_dwconv_bwd" : "smx_dwconv_fwd";
+  memset(pl, 0, sizeof(*pl));
+  SMX_REQUIRE(a.P && a.w && a.Y && (!bwd || (a.dP && (a.dw || a.workspace))), "%s: null pointer", who);
+  SMX_REQUIRE(a.k >= 1 && a.k <= DW_KMAX && (a.k & 1), "%s: k=%d must be odd and <= %d", who, a.k, DW_KMAX);
+  if (bwd) SMX_REQUIRE((a.gate == nullptr) == (a.dgate == nullptr), "%s: gate and dgate go together", who);
+  else {
+    SMX_REQUIRE(a.drop_p >= 0.f && a.drop_p < 1.f, "%s: 0 <= drop_p < 1", who);
+    SMX_REQUIRE(a.pad_mode != SMX_PAD_REFLECT || (a.k - 1) / 2 < a.T, "%s: reflect pad needs (k-1)/2 < T", who);
+  }
+  if (a.B <= 0 || a.T <= 0 || a.D <= 0) return SMX_OK;              // (grid[0] == 0: nothing to launch)
+  const bool bf = a.dtype == SMX_BF16, zero = a.pad_mode == SMX_PAD_ZERO, ws = !bwd || a.workspace;
+  const int vw = bf ? 8 : 4;
+  pl->chunked = a.chunk > 0;
+  pl->route = SMX_DW_TILED;
+  // the rolling kernels (dwconv_roll.h); the bf16 ones move 16-byte pieces (LDS-DMA in, dwordx4 out)
+  if (a.k == 31 && a.D % 64 == 0 && ws && (!bf || dw_aligned(a, bwd, 8))) {
+    // (Dynamic Chunk Convolution, chunk > 0, is part of the GLU kernels)
+    if (a.glu && !a.gate && zero) pl->route = SMX_DW_ROLL;
+    else if (!pl->chunked && !a.glu && a.gate && !zero && bf && a.T > 15) pl->route = SMX_DW_ROLL_CSGU;
+  }
+  if (pl->route == SMX_DW_TILED && a.k == 31 && !pl->chunked && a.D % vw == 0 && ws && dw_aligned(a, bwd, vw) && (zero || a.T > 15))
+    pl->route = SMX_DW_WINDOW;
+  const int ctiles = tiles_of(a.D, DW_CT);
+  if (pl->route >= SMX_DW_ROLL) {
+    auto mx = [](int64_t x, int64_t y) { return x > y ? x : y; };
+    const int64_t ldmax = mx(mx(mx(a.ldp, a.ldy), a.ldg), bwd ? mx(a.lddp, a.lddg) : 0);
+    SMX_REQUIRE((long)a.T * ldmax * 4 < (1L << 31), "%s: utterance span >= 2 GB", who);
+    roll_geometry(a.B, a.T, a.D, &pl->seg, &pl->nseg, &pl->partial_rows);
+    pl->grid[0] = 8 * (a.D / 64) * tiles_of(pl->partial_rows, 8);
+  } else {
+    pl->partial_rows = (int)tiled_rows(a.B, a.T, a.D);
+    if (!bwd) pl->grid[0] = ctiles, pl->grid[1] = tiles_of(a.T, DW_TT), pl->grid[2] = a.B;
+    else if (pl->route == SMX_DW_WINDOW) pl->grid[0] = 8 * ctiles * tiles_of(pl->partial_rows, 8);
+    else pl->grid[0] = ctiles, pl->grid[1] = pl->partial_rows;
+  }
+  for (int& g : pl->grid) g = g ? g : 1;
+  if (!bwd && a.drop_p > 0.f && pl->route != SMX_DW_ROLL_CSGU)
+    return fail(SMX_EUNSUPPORTED, "%s: fused output dropout needs the rolling CSGU kernel", who);
+  // the tiled kernel keeps no partial rows for a later reduction (without a workspace its tap gradients are atomics)
+  pl->deferrable = bwd && pl->route != SMX_DW_TILED;
+  if (bwd && !a.dw && !pl->deferrable)
+    return fail(SMX_EUNSUPPORTED, "%s: dw == NULL (deferred reduction) needs the window or a rolling route", who);
+  return SMX_OK;
 }
 
-static int dwconv_fwd_impl(int dtype, const void* P, int64_t ldp, const float* w, const float* bias, const void* gate, int64_t ldg,
-                           void* Y, int64_t ldy, int B, int T, int D, int k, int glu, int pad_mode, int chunk, float drop_p,
-                           uint64_t drop_seed, const uint64_t* epoch, void* stream) {
-  SMX_REQUIRE(P && w && Y, "smx_dwconv1d_glu_fwd: null pointer");
-  SMX_REQUIRE(k >= 1 && k <= DW_KMAX && (k & 1), "smx_dwconv1d_glu_fwd: k=%d must be odd and <= %d", k, DW_KMAX);
-  SMX_REQUIRE(pad_mode != SMX_PAD_REFLECT || (k - 1) / 2 < T, "smx_dwconv1d_glu_fwd: reflect pad needs (k-1)/2 < T");
-  if (B <= 0 || T <= 0 || D <= 0) return SMX_OK;
+static DwParams dw_params(const smx_dwconv_args& a, bool bwd, int route) {
   DwParams p;
   memset(&p, 0, sizeof(p));
-  p.P = P; p.ldp = ldp; p.w = w; p.bias = bias; p.gate = gate; p.ldg = ldg; p.Y = Y; p.ldy = ldy;
-  p.B = B; p.T = T; p.D = D; p.k = k; p.glu = glu; p.pad_mode = pad_mode; p.chunk = chunk;
-  dim3 grid((D + DW_CT - 1) / DW_CT, (T + DW_TT - 1) / DW_TT, B);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int vw = dtype == SMX_BF16 ? 8 : 4;
-  const bool fast = k == 31 && chunk <= 0 && D % vw == 0 && ldp % vw == 0 && ldy % vw == 0 && aligned16(P) && aligned16(Y) &&
-                    (gate == nullptr || (ldg % vw == 0 && aligned16(gate))) && (pad_mode == SMX_PAD_ZERO || T > 15);
-  int rk = roll_kind(dtype, T, D, k, glu, pad_mode, chunk, gate != nullptr);
-  // the bf16 kernels move 16-byte pieces (LDS-DMA in, dwordx4 out): rows and bases must be 16-byte aligned, else tiled
-  if (rk && dtype == SMX_BF16 && !(ldp % 8 == 0 && ldy % 8 == 0 && aligned16(P) && aligned16(Y) &&
-                                   (gate == nullptr || (ldg % 8 == 0 && aligned16(gate))))) rk = 0;
-  if (rk) {
-    const long ldmax = ldp > ldy ? (ldp > ldg ? ldp : ldg) : (ldy > ldg ? ldy : ldg);
-    SMX_REQUIRE((long)T * ldmax * 4 < (1L << 31), "smx_dwconv1d_glu_fwd: utterance span >= 2 GB (SMX_DWROLL=0 selects the tiled kernel)");
-    int seg, nseg, gy;
-    roll_geometry(B, T, D, &seg, &nseg, &gy);
-    dim3 g1((unsigned)(8 * (D / 64) * ((gy + 7) / 8)));
-    if (drop_p > 0.f && rk != 2) return fail(SMX_EUNSUPPORTED, "smx_dwconv1d_glu_fwd_drop: fused output dropout needs the rolling CSGU kernel");
-    if (rk == 2) {
-      p.dthresh = (unsigned)((double)drop_p * 4294967296.0); p.dscale = 1.f / (1.f - drop_p); p.dseed = drop_seed; p.epoch = epoch;
-      hipLaunchKernelGGL(dwconv_rollc_fwd, g1, dim3(256), 0, s, p, seg, nseg, gy);
-    }
-    else if (dtype == SMX_BF16) {
-      if (chunk > 0) hipLaunchKernelGGL((dwconv_rolls_fwd<true>), g1, dim3(256), 0, s, p, seg, nseg, gy);
-      else hipLaunchKernelGGL((dwconv_rolls_fwd<false>), g1, dim3(256), 0, s, p, seg, nseg, gy);
-    } else if (chunk > 0) hipLaunchKernelGGL((dwconv_roll_fwd<float, true>), g1, dim3(256), 0, s, p, seg, nseg, gy);
-    else hipLaunchKernelGGL((dwconv_roll_fwd<float, false>), g1, dim3(256), 0, s, p, seg, nseg, gy);
-  } else if (drop_p > 0.f) {
-    return fail(SMX_EUNSUPPORTED, "smx_dwconv1d_glu_fwd_drop: fused output dropout needs the rolling CSGU kernel");
-  } else if (fast) {
-    if (gate) {
-      if (dtype == SMX_BF16) hipLaunchKernelGGL((dwconv_fwd_fast<bf16_t, 31, true>), grid, dim3(256), 0, s, p);
-      else hipLaunchKernelGGL((dwconv_fwd_fast<float, 31, true>), grid, dim3(256), 0, s, p);
-    } else {
-      if (dtype == SMX_BF16) hipLaunchKernelGGL((dwconv_fwd_fast<bf16_t, 31, false>), grid, dim3(256), 0, s, p);
-      else hipLaunchKernelGGL((dwconv_fwd_fast<float, 31, false>), grid, dim3(256), 0, s, p);
-    }
-  } else if (dtype == SMX_BF16) hipLaunchKernelGGL((dwconv_fwd_kernel<bf16_t>), grid, dim3(256), 0, s, p);
-  else hipLaunchKernelGGL((dwconv_fwd_kernel<float>), grid, dim3(256), 0, s, p);
-  return check_launch("smx_dwconv1d_glu_fwd");
-}
-
-static long tiled_rows(int B, int T, int D) {
-  const int tiles_t = (T + DW_TT - 1) / DW_TT, ctiles = (D + DW_CT - 1) / DW_CT;
-  long total = (long)B * tiles_t, gy = (1024 + ctiles - 1) / ctiles;
-  if (gy > total) gy = total;
-  if (gy < 1) gy = 1;
-  return gy;
-}
-
-extern "C" int smx_dwconv1d_glu_bwd_partial_rows(int dtype, int B, int T, int D, int k, int glu, int pad_mode, int chunk,
-                                                 int has_gate) {
-  if (B <= 0 || T <= 0 || D <= 0) return 0;
-  if (roll_kind(dtype, T, D, k, glu, pad_mode, chunk, has_gate != 0)) {
-    int seg, nseg, gy;
-    roll_geometry(B, T, D, &seg, &nseg, &gy);
-    return gy;
+  p.P = a.P; p.ldp = a.ldp; p.w = a.w; p.bias = a.bias; p.gate = a.gate; p.ldg = a.ldg; p.Y = a.Y; p.ldy = a.ldy;
+  p.B = a.B; p.T = a.T; p.D = a.D; p.k = a.k; p.glu = a.glu; p.pad_mode = a.pad_mode; p.chunk = a.chunk;
+  if (bwd) {
+    p.dP = a.dP; p.lddp = a.lddp; p.dgate = a.dgate; p.lddg = a.lddg; p.dw = a.dw; p.dbias = a.dbias;
+  } else if (route == SMX_DW_ROLL_CSGU) {
+    p.dthresh = (unsigned)((double)a.drop_p * 4294967296.0); p.dscale = 1.f / (1.f - a.drop_p); p.dseed = a.drop_seed; p.epoch = a.epoch;
   }
-  return (int)tiled_rows(B, T, D);
+  return p;
+}
+
+// f(tag) with tag.value = b as a constant: the bool template arguments of the launch sites
+template <typename F>
+static inline void dw_flag(bool b, F&& f) {
+  if (b) f(std::true_type()); else f(std::false_type());
+}
+
+extern "C" int smx_dwconv_plan_query(const smx_dwconv_args* a, int backward, smx_dwconv_plan* plan) {
+  SMX_REQUIRE(a && plan, "smx_dwconv_plan_query: null pointer");
+  return dw_plan(*a, backward != 0, plan);
 }
 
 extern "C" size_t smx_dwconv1d_glu_bwd_workspace(int B, int T, int D, int k) {
@@ -678,93 +669,71 @@ extern "C" size_t smx_dwconv1d_glu_bwd_workspace(int B, int T, int D, int k) {
   return (size_t)gy * D * (k + 1) * sizeof(float);
 }
 
-extern "C" int smx_dwconv1d_glu_bwd(int dtype, const void* dY, int64_t lddy, const void* P, int64_t ldp, const float* w,
-                                    const float* bias, const void* gate, int64_t ldg, void* dP, int64_t lddp,
-                                    void* dgate, int64_t lddg, float* dw, float* dbias, int B, int T, int D, int k,
-                                    int glu, int pad_mode, int chunk, void* workspace, void* stream) {
-  SMX_REQUIRE(dY && P && w && dP && (dw || workspace), "smx_dwconv1d_glu_bwd: null pointer");
-  SMX_REQUIRE(k >= 1 && k <= DW_KMAX && (k & 1), "smx_dwconv1d_glu_bwd: k=%d must be odd and <= %d", k, DW_KMAX);
-  SMX_REQUIRE((gate == nullptr) == (dgate == nullptr), "smx_dwconv1d_glu_bwd: gate and dgate go together");
-  if (B <= 0 || T <= 0 || D <= 0) return SMX_OK;
-  DwParams p;
-  memset(&p, 0, sizeof(p));
-  p.P = P; p.ldp = ldp; p.w = w; p.bias = bias; p.gate = gate; p.ldg = ldg; p.Y = const_cast<void*>(dY); p.ldy = lddy;
-  p.dP = dP; p.lddp = lddp; p.dgate = dgate; p.lddg = lddg; p.dw = dw; p.dbias = dbias;
-  p.B = B; p.T = T; p.D = D; p.k = k; p.glu = glu; p.pad_mode = pad_mode; p.chunk = chunk;
-  const int tiles_t = (T + DW_TT - 1) / DW_TT;
-  const int ctiles = (D + DW_CT - 1) / DW_CT;
-  long total = (long)B * tiles_t;
-  long gy = (1024 + ctiles - 1) / ctiles;          // ~1024 persistent blocks in total
-  if (gy > total) gy = total;
-  if (gy < 1) gy = 1;
-  dim3 grid(ctiles, (unsigned)gy);
+extern "C" int smx_dwconv_fwd(const smx_dwconv_args* a, void* stream) {
+  SMX_REQUIRE(a, "smx_dwconv_fwd: null descriptor");
+  smx_dwconv_plan pl;
+  if (int rc = dw_plan(*a, false, &pl)) return rc;
+  if (!pl.grid[0]) return SMX_OK;
+  const DwParams p = dw_params(*a, false, pl.route);
+  const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]), blk(256);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int vw = dtype == SMX_BF16 ? 8 : 4;
-  const bool fast = k == 31 && chunk <= 0 && D % vw == 0 && ldp % vw == 0 && lddy % vw == 0 && lddp % vw == 0 &&
-                    aligned16(P) && aligned16(dY) && aligned16(dP) && workspace != nullptr &&
-                    (gate == nullptr || (ldg % vw == 0 && lddg % vw == 0 && aligned16(gate) && aligned16(dgate))) &&
-                    (pad_mode == SMX_PAD_ZERO || T > 15);
-  int rk = workspace ? roll_kind(dtype, T, D, k, glu, pad_mode, chunk, gate != nullptr) : 0;
-  if (rk && dtype == SMX_BF16 && !(ldp % 8 == 0 && lddy % 8 == 0 && lddp % 8 == 0 && aligned16(P) && aligned16(dY) && aligned16(dP) &&
-                                   (gate == nullptr || (ldg % 8 == 0 && lddg % 8 == 0 && aligned16(gate) && aligned16(dgate))))) {
-    // misaligned bf16 operands drop to the tiled kernel, which writes tiled_rows() partial rows - not the rolling count that
-    // smx_dwconv1d_glu_bwd_partial_rows (it sees no pointers) reports for these sizes: a deferred reduction would fold the
-    // wrong number of rows.  Deferred mode therefore refuses; the caller reduces immediately.
-    if (!dw) return fail(SMX_EUNSUPPORTED, "smx_dwconv1d_glu_bwd: deferred reduction needs 16-byte aligned bf16 rows on the rolling path");
-    rk = 0;
+  const bool bf = a->dtype == SMX_BF16;
+  if (pl.route == SMX_DW_ROLL_CSGU) hipLaunchKernelGGL(dwconv_rollc_fwd, grid, blk, 0, s, p, pl.seg, pl.nseg, pl.partial_rows);
+  else if (pl.route == SMX_DW_ROLL) dw_flag(pl.chunked, [&](auto ch) {
+    constexpr bool CH = decltype(ch)::value;
+    if (bf) hipLaunchKernelGGL((dwconv_rolls_fwd<CH>), grid, blk, 0, s, p, pl.seg, pl.nseg, pl.partial_rows);
+    else hipLaunchKernelGGL((dwconv_roll_fwd<float, CH>), grid, blk, 0, s, p, pl.seg, pl.nseg, pl.partial_rows);
+  });
+  else dispatch_dtype(a->dtype, [&](auto tag) {
+    using T = decltype(tag);
+    if (pl.route == SMX_DW_WINDOW) dw_flag(a->gate != nullptr, [&](auto g) {
+      hipLaunchKernelGGL((dwconv_fwd_fast<T, 31, decltype(g)::value>), grid, blk, 0, s, p);
+    });
+    else hipLaunchKernelGGL((dwconv_fwd_kernel<T>), grid, blk, 0, s, p);
+  });
+  return check_launch("smx_dwconv_fwd");
+}
+
+extern "C" int smx_dwconv_bwd(const smx_dwconv_args* a, void* stream) {
+  SMX_REQUIRE(a, "smx_dwconv_bwd: null descriptor");
+  smx_dwconv_plan pl;
+  if (int rc = dw_plan(*a, true, &pl)) return rc;
+  if (!pl.grid[0]) return SMX_OK;
+  const DwParams p = dw_params(*a, true, pl.route);
+  const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]), blk(256);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  float* partial = reinterpret_cast<float*>(a->workspace);
+  const int rows = pl.partial_rows, tiles_t = tiles_of(a->T, DW_TT);
+  const bool bf = a->dtype == SMX_BF16;
+  if (pl.route == SMX_DW_ROLL_CSGU) {
+    hipLaunchKernelGGL(dwconv_rollc_bwd, grid, blk, 0, s, p, pl.seg, pl.nseg, rows, partial);
+    // the gradient of the mirrored virtual frames goes back to frames 1..15 / T-16..T-2 (30 rows per utterance)
+    hipLaunchKernelGGL(dwconv_csgu_fold_kernel, dim3((unsigned)((a->D / 2 + 63) / 64), (unsigned)a->B), dim3(64), 0, s, p);
   }
-  if (rk) {
-    long ldmax = ldp > lddp ? (ldp > lddy ? ldp : lddy) : (lddp > lddy ? lddp : lddy);
-    if (ldg > ldmax) ldmax = ldg;
-    if (lddg > ldmax) ldmax = lddg;
-    SMX_REQUIRE((long)T * ldmax * 4 < (1L << 31), "smx_dwconv1d_glu_bwd: utterance span >= 2 GB (SMX_DWROLL=0 selects the tiled kernel)");
-    int seg, nseg, gr;
-    roll_geometry(B, T, D, &seg, &nseg, &gr);
-    float* partial = reinterpret_cast<float*>(workspace);
-    dim3 g1((unsigned)(8 * (D / 64) * ((gr + 7) / 8)));
 #ifdef SMX_DIAG
-    const int abl = cfg().dwroll_ablate;
+  else if (pl.route == SMX_DW_ROLL && bf && !pl.chunked && cfg().dwroll_ablate == 1)
+    hipLaunchKernelGGL((dwconv_rolls_bwd<1>), grid, blk, 0, s, p, pl.seg, pl.nseg, rows, partial);
+  else if (pl.route == SMX_DW_ROLL && bf && !pl.chunked && cfg().dwroll_ablate == 2)
+    hipLaunchKernelGGL((dwconv_rolls_bwd<2>), grid, blk, 0, s, p, pl.seg, pl.nseg, rows, partial);
 #endif
-    if (rk == 2) {
-      hipLaunchKernelGGL(dwconv_rollc_bwd, g1, dim3(256), 0, s, p, seg, nseg, gr, partial);
-      // the gradient of the mirrored virtual frames goes back to frames 1..15 / T-16..T-2 (30 rows per utterance)
-      hipLaunchKernelGGL(dwconv_csgu_fold_kernel, dim3((unsigned)((D / 2 + 63) / 64), (unsigned)B), dim3(64), 0, s, p);
-    } else if (dtype != SMX_BF16) {
-      if (chunk > 0) hipLaunchKernelGGL((dwconv_roll_bwd<float, true>), g1, dim3(256), 0, s, p, seg, nseg, gr, partial);
-      else hipLaunchKernelGGL((dwconv_roll_bwd<float, false>), g1, dim3(256), 0, s, p, seg, nseg, gr, partial);
-    } else if (chunk > 0) hipLaunchKernelGGL((dwconv_rolls_bwd<0, true>), g1, dim3(256), 0, s, p, seg, nseg, gr, partial);
-#ifdef SMX_DIAG
-    else if (abl == 1) hipLaunchKernelGGL((dwconv_rolls_bwd<1>), g1, dim3(256), 0, s, p, seg, nseg, gr, partial);
-    else if (abl == 2) hipLaunchKernelGGL((dwconv_rolls_bwd<2>), g1, dim3(256), 0, s, p, seg, nseg, gr, partial);
-#endif
-    else hipLaunchKernelGGL((dwconv_rolls_bwd<0>), g1, dim3(256), 0, s, p, seg, nseg, gr, partial);
-    const long W = (long)D * (k + 1);
-    if (dw) hipLaunchKernelGGL(dw_partials_reduce_kernel, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, s, partial, gr, D, k, dw, dbias);
-  } else if (fast) {
-    float* partial = reinterpret_cast<float*>(workspace);
-    dim3 g1((unsigned)(8 * ctiles * ((gy + 7) / 8)));
-    const bool refl = pad_mode == SMX_PAD_REFLECT, gt = gate != nullptr;
-#define DW_BWD(TT, R, G) hipLaunchKernelGGL((dwconv_bwd_fast<TT, 31, R, G>), g1, dim3(256), 0, s, p, tiles_t, partial, (int)gy)
-    if (dtype == SMX_BF16) {
-      if (refl && gt) DW_BWD(bf16_t, true, true); else if (refl) DW_BWD(bf16_t, true, false);
-      else if (gt) DW_BWD(bf16_t, false, true); else DW_BWD(bf16_t, false, false);
-    } else {
-      if (refl && gt) DW_BWD(float, true, true); else if (refl) DW_BWD(float, true, false);
-      else if (gt) DW_BWD(float, false, true); else DW_BWD(float, false, false);
-    }
-#undef DW_BWD
-    const long W = (long)D * (k + 1);
-    // (dw == NULL: the partial rows [gy][D][k + 1] stay in the workspace for a deferred smx_reduce_jobs)
-    if (dw) hipLaunchKernelGGL(dw_partials_reduce_kernel, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, s, partial, (int)gy, D, k, dw, dbias);
-  } else if (!dw) {
-    return fail(SMX_EUNSUPPORTED, "smx_dwconv1d_glu_bwd: dw == NULL (deferred reduction) needs the k = 31 vector path");
-  } else {
-    // generic shapes (k != 31, D % 8 != 0, ...): with a workspace one partial row per workgroup + the fixed-order reduction
-    float* partial = reinterpret_cast<float*>(workspace);
-    if (dtype == SMX_BF16) hipLaunchKernelGGL((dwconv_bwd_kernel<bf16_t>), grid, dim3(256), 0, s, p, tiles_t, partial);
-    else hipLaunchKernelGGL((dwconv_bwd_kernel<float>), grid, dim3(256), 0, s, p, tiles_t, partial);
-    const long W = (long)D * (k + 1);
-    if (partial) hipLaunchKernelGGL(dw_partials_reduce_kernel, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, s, partial, (int)gy, D, k, dw, dbias);
-  }
-  return check_launch("smx_dwconv1d_glu_bwd");
+  else if (pl.route == SMX_DW_ROLL) dw_flag(pl.chunked, [&](auto ch) {
+    constexpr bool CH = decltype(ch)::value;
+    if (bf) hipLaunchKernelGGL((dwconv_rolls_bwd<0, CH>), grid, blk, 0, s, p, pl.seg, pl.nseg, rows, partial);
+    else hipLaunchKernelGGL((dwconv_roll_bwd<float, CH>), grid, blk, 0, s, p, pl.seg, pl.nseg, rows, partial);
+  });
+  else dispatch_dtype(a->dtype, [&](auto tag) {
+    using T = decltype(tag);
+    if (pl.route == SMX_DW_WINDOW) dw_flag(a->pad_mode == SMX_PAD_REFLECT, [&](auto r) {
+      dw_flag(a->gate != nullptr, [&](auto g) {
+        hipLaunchKernelGGL((dwconv_bwd_fast<T, 31, decltype(r)::value, decltype(g)::value>), grid, blk, 0, s, p, tiles_t, partial, rows);
+      });
+    });
+    // generic shapes (k != 31, D % 8 != 0, ...): with a workspace one partial row per workgroup, else atomics
+    else hipLaunchKernelGGL((dwconv_bwd_kernel<T>), grid, blk, 0, s, p, tiles_t, partial);
+  });
+  // fixed-order reduction of the partial rows [rows][D][k + 1]; dw == NULL: they stay in the workspace for smx_reduce_jobs
+  const long W = (long)a->D * (a->k + 1);
+  if (a->dw && partial)
+    hipLaunchKernelGGL(dw_partials_reduce_kernel, dim3((unsigned)((W + 255) / 256)), blk, 0, s, partial, rows, a->D, a->k, a->dw, a->dbias);
+  return check_launch("smx_dwconv_bwd");
 }

@@ -637,20 +637,34 @@ def layernorm_bwd_preact(dy, x, gamma, beta, stats, z, zact, dgamma, dbeta, act=
     return layernorm_bwd(dy, x, gamma, beta, stats, dgamma, dbeta, act=act, ws=ws, dx_out=dx_out, preact=(z, zact))
 
 
+def _dwconv_args(p, w, bias, y, ldy, B, T, D, k, glu, pad_mode, chunk, gate):
+    """The smx_dwconv_args both directions share (y: the forward's output or the backward's dY)."""
+    a = L.DwconvArgs(dtype=dt(p), glu=1 if glu else 0, w=_p(w), bias=_p(bias), Y=y, ldy=ldy, B=B, T=T, D=D, k=k, pad_mode=pad_mode,
+                     chunk=chunk)
+    a.P, a.ldp = _mat(p)
+    if gate is not None:
+        a.gate, a.ldg = _mat(gate)
+    return a
+
+
+def _dwconv_plan(a, backward):
+    """smx_dwconv_plan_query: the plan, or None where the library refuses the descriptor."""
+    plan = L.DwconvPlan()
+    return plan if L.lib().smx_dwconv_plan_query(ctypes.byref(a), backward, ctypes.byref(plan)) == 0 else None
+
+
 def dwconv_fwd(p, w, bias, B, T, D, k, glu, pad_mode=L.PAD_ZERO, chunk=0, gate=None, drop=None):
     """drop = (p, seed): inverted dropout of the output (the CSGU's own), fused where the kernel can (rolling CSGU path),
     else a separate in-place smx_dropout with the same mask."""
     y = torch.empty((B * T, D), dtype=p.dtype, device=p.device)
-    pp, ldp = _mat(p)
-    pg, ldg = (_mat(gate) if gate is not None else (None, 0))
+    a = _dwconv_args(p, w, bias, _p(y), D, B, T, D, k, glu, pad_mode, chunk, gate)
     tok = _pb(f"dwconv_fwd ({B},{T},{D}) k={k}", 3 * B * T * D * _es(p))
     fused = False
     if drop is not None and drop[0] > 0.0 and _CSGU_DROP_FUSE:
-        fused = L.lib().smx_dwconv1d_glu_fwd_drop(dt(p), pp, ldp, _p(w), _p(bias), pg, ldg, _p(y), D, B, T, D, k, 1 if glu else 0,
-                                                  pad_mode, chunk, drop[0], drop[1], _epoch(), _stream()) == 0
-    if not fused:
-        L.check(L.lib().smx_dwconv1d_glu_fwd(dt(p), pp, ldp, _p(w), _p(bias), pg, ldg, _p(y), D, B, T, D, k, 1 if glu else 0,
-                                             pad_mode, chunk, _stream()), "smx_dwconv1d_glu_fwd")
+        a.drop_p, a.drop_seed, a.epoch = drop[0], drop[1], _epoch()
+        fused = _dwconv_plan(a, 0) is not None                     # (refused: the separate pass below)
+        a.drop_p = drop[0] if fused else 0.0
+    L.check(L.lib().smx_dwconv_fwd(ctypes.byref(a), _stream()), "smx_dwconv_fwd")
     _pe(tok)
     if drop is not None and drop[0] > 0.0 and not fused:
         dropout(y, drop[0], drop[1], out=y)
@@ -714,29 +728,26 @@ def slot_advance(counters, valid, B, C):
 
 def dwconv_bwd(dy, p, w, bias, dw, dbias, B, T, D, k, glu, pad_mode=L.PAD_ZERO, chunk=0, gate=None, dgate_out=None, ws=None):
     """ws (caller-owned, smx_dwconv1d_glu_bwd_workspace bytes): the tap / bias partial rows stay in it for a deferred
-    reduce_jobs and dw / dbias are not touched; then returns (dp, dgate, deferred) - deferred False means the shape is outside
-    the partial-row path and the gradients were accumulated into dw / dbias directly."""
+    reduce_jobs and dw / dbias are not touched; then returns (dp, dgate, rows) - the number of partial rows left in ws
+    (smx_dwconv_plan.partial_rows), or 0 where the plan is not deferrable and the gradients went into dw / dbias directly."""
     dp = torch.empty((B * T, p.shape[1]), dtype=p.dtype, device=p.device)
     dgate = None
     if gate is not None:
         dgate = dgate_out if dgate_out is not None else torch.empty((B * T, D), dtype=p.dtype, device=p.device)
-    pdy, lddy = _mat(dy)
-    pp, ldp = _mat(p)
-    pg, ldg = (_mat(gate) if gate is not None else (None, 0))
+    a = _dwconv_args(p, w, bias, *_mat(dy), B, T, D, k, glu, pad_mode, chunk, gate)
+    a.dP, a.lddp, a.dw, a.dbias, a.workspace = _p(dp), dp.shape[1], _p(dw), _p(dbias), _p(ws)
+    if dgate is not None:
+        a.dgate, a.lddg = _mat(dgate)
     tok = _pb(f"dwconv_bwd ({B},{T},{D}) k={k}", 5 * B * T * D * _es(p))
-
-    def call(pdw, pdb, wsp):
-        return L.lib().smx_dwconv1d_glu_bwd(dt(p), pdy, lddy, pp, ldp, _p(w), _p(bias), pg, ldg, _p(dp), dp.shape[1], _p(dgate),
-                                            (_mat(dgate)[1] if dgate is not None else 0), pdw, pdb, B, T, D, k, 1 if glu else 0,
-                                            pad_mode, chunk, wsp, _stream())
-    deferred = False
-    if ws is not None:
-        deferred = call(None, None, _p(ws)) == 0               # (SMX_EUNSUPPORTED: not the k = 31 vector path)
-    if not deferred:
-        own = _workspace(L.lib().smx_dwconv1d_glu_bwd_workspace(B, T, D, k), p.device, slot=4)
-        L.check(call(_p(dw), _p(dbias), _p(own)), "smx_dwconv1d_glu_bwd")
+    plan = _dwconv_plan(a, 1) if ws is not None else None
+    rows = plan.partial_rows if plan is not None and plan.deferrable else 0
+    if rows:
+        a.dw = a.dbias = None
+    else:
+        a.workspace = _p(_workspace(L.lib().smx_dwconv1d_glu_bwd_workspace(B, T, D, k), p.device, slot=4))
+    L.check(L.lib().smx_dwconv_bwd(ctypes.byref(a), _stream()), "smx_dwconv_bwd")
     _pe(tok)
-    return (dp, dgate, deferred) if ws is not None else (dp, dgate)
+    return (dp, dgate, rows) if ws is not None else (dp, dgate)
 
 
 def axpby(a, x, b=0.0, y0=None, out=None):

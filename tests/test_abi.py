@@ -65,6 +65,19 @@ def test_layernorm_descriptor_layouts_match_header():
     assert B.drop_seed2.offset == 176 and B.epoch.offset == 184 and B.Z.offset == 192 and B.zact.offset == 208 and B.D.offset == 216
 
 
+def test_dwconv_descriptor_layouts_match_header():
+    from summarymixing_amd import _lib
+    A, P = _lib.DwconvArgs, _lib.DwconvPlan
+    assert ctypes.sizeof(A) == 176 and ctypes.sizeof(P) == 40     # see include/smx.h smx_dwconv_args / smx_dwconv_plan
+    assert A.glu.offset == 4 and A.P.offset == 8 and A.w.offset == 24 and A.gate.offset == 40 and A.Y.offset == 56 and A.dP.offset == 72
+    assert A.dgate.offset == 88 and A.dw.offset == 104 and A.dbias.offset == 112 and A.workspace.offset == 120 and A.B.offset == 128
+    assert A.k.offset == 140 and A.pad_mode.offset == 144 and A.chunk.offset == 148 and A.drop_p.offset == 152
+    assert A.drop_seed.offset == 160 and A.epoch.offset == 168
+    assert P.route.offset == 0 and P.chunked.offset == 4 and P.deferrable.offset == 8 and P.partial_rows.offset == 12
+    assert P.grid.offset == 16 and P.seg.offset == 28 and P.nseg.offset == 32
+    assert (_lib.DW_TILED, _lib.DW_WINDOW, _lib.DW_ROLL, _lib.DW_ROLL_CSGU) == (0, 1, 2, 3)
+
+
 # Inputs the library refuses, with the code it returns.  The pointers are fake (never dereferenced: every case is refused on the
 # host before any launch); BASE is 4 KiB aligned, BASE + 4 / + 8 are the misaligned variants.
 _BASE = 1 << 40
