@@ -512,7 +512,7 @@ int smx_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_a
 /* ---- InputNormalization between the filterbank and the CNN front-end (recipe key `normalize`:
  * speechbrain.processing.features.InputNormalization, …transducer.yaml:167-169; upstream-only arithmetic). ----
  * smx_utt_meanstd: mean[b,f] and unbiased std[b,f] over the frames t < len[b] (std clamped below by eps; 0 / 1 when the
- * respective normalisation is off).  smx_stats_combine: glob = (1-w)*glob + w*mean_b(cur) (w = 1 replaces: the first
+ * respective normalisation is off; like torch, the std of fewer than two frames and the mean of none are NaN).  smx_stats_combine: glob = (1-w)*glob + w*mean_b(cur) (w = 1 replaces: the first
  * batch / norm_type "batch").  smx_colnorm: Y = (X - mean[b*stat_stride + f]) / std[...] over (B, T, F) rows b*T + t
  * (stat_stride 0 = shared statistics: "global" / "batch"; F = per-utterance: "sentence"). */
 int smx_utt_meanstd(int dtype, const void* X, int64_t ldx, const int32_t* len, float* mean, float* std, int B, int T, int F,

@@ -35,7 +35,7 @@ __global__ __launch_bounds__(256) void frame_window_kernel(const float* __restri
 // - 40x fewer MACs than the dense product (3.0 ms -> 0.2 ms for 128 000 frames).
 // spec layout: S (N, lds) with re at column f and im at column im_off + f.
 __global__ __launch_bounds__(256) void mel_db_kernel(const float* __restrict__ S, long lds, int im_off, const float* __restrict__ fb,
-                                                     int n_bins, int n_mels, float amin, float* __restrict__ db,
+                                                     int n_bins, int n_mels, float amin, float db_min, float* __restrict__ db,
                                                      float* __restrict__ bmax, int N_) {
   extern __shared__ float pw[];                        // 4 x n_bins power rows | n_mels x MELW filter bands
   constexpr int MELW = 48;                             // widest band kept in LDS (n_fft = 512, 80 mels: <= 27 bins); longer tails read global
@@ -106,7 +106,9 @@ __global__ __launch_bounds__(256) void mel_db_kernel(const float* __restrict__ S
         for (; j + 1 < wl; j += 2) { a0 += P[lo[k] + j] * bw[j]; a1 += P[lo[k] + j + 1] * bw[j + 1]; }
         if (j < wl) a0 += P[lo[k] + j] * bw[j];
         for (int f = lo[k] + MELW; f < hi[k]; ++f) a1 += P[f] * fr[f];
-        const float dbv = 10.f * log10f(fmaxf(a0 + a1, amin));
+        // db_min = 10 log10(amin) rounded on the host: the fast log10f puts 1e-10 at -99.99999 (one ulp), and nothing may lie below
+        const float sum = a0 + a1;
+        const float dbv = sum > amin ? fmaxf(10.f * log10f(sum), db_min) : db_min;
         db[(long)n * n_mels + m] = dbv;
         fmx = fmaxf(fmx, dbv);
       }
@@ -617,7 +619,10 @@ __global__ __launch_bounds__(256) void utt_meanstd_kernel(const T* __restrict__ 
   for (; t < n; t += TG) s0 += to_f32(x[(long)t * ldx]);
   red[tg][cl] = (s0 + s1) + (s2 + s3);
   __syncthreads();
-  const float m = n > 0 ? fold() / (float)n : 0.f;
+  // (the quotient in double: -ffast-math turns the float32 division into a reciprocal and a product, one ulp off - 63 frames of
+  //  1000.0 had the mean 1000.00006 and, from it, a std of 6e-5 where a constant feature has 0 -> eps.  torch.mean of no frame
+  //  - a length that rounds to 0 - is NaN)
+  const float m = n > 0 ? (float)((double)fold() / (double)n) : __builtin_nanf("");
   __syncthreads();
   float q0 = 0.f, q1 = 0.f, q2 = 0.f, q3 = 0.f;
   t = tg;
@@ -632,7 +637,8 @@ __global__ __launch_bounds__(256) void utt_meanstd_kernel(const T* __restrict__ 
   if (tg == 0 && c < F) {
     const float var = n > 1 ? fold() / (float)(n - 1) : __builtin_nanf("");
     mean[(long)b * F + c] = mean_norm ? m : 0.f;
-    sd[(long)b * F + c] = std_norm ? fmaxf(sqrtf(var), eps) : 1.f;    // torch.max(std, eps): NaN (one frame) propagates
+    const float sv = sqrtf(var);
+    sd[(long)b * F + c] = std_norm ? (sv < eps ? eps : sv) : 1.f;     // torch.max(std, eps): NaN (one frame) propagates (fmaxf drops it)
   }
 }
 
@@ -641,11 +647,14 @@ __global__ void stats_combine_kernel(const float* __restrict__ cur_mean, const f
                                      float* glob_mean, float* glob_std, float w) {
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c >= F) return;
-  float m = 0.f, s = 0.f;
-  for (int b = 0; b < B; ++b) { m += cur_mean[(long)b * F + c]; s += cur_std[(long)b * F + c]; }
-  m /= (float)B; s /= (float)B;
-  glob_mean[c] = w >= 1.f ? m : (1.f - w) * glob_mean[c] + w * m;
-  glob_std[c] = w >= 1.f ? s : (1.f - w) * glob_std[c] + w * s;
+  // in double, rounded once: B values per feature, and the running statistics are blended into themselves batch after batch
+  // (the float32 form under -ffast-math - reciprocal division, contracted blend - sat a few ulp off the expression each time)
+  double m = 0.0, s = 0.0;
+  for (int b = 0; b < B; ++b) { m += (double)cur_mean[(long)b * F + c]; s += (double)cur_std[(long)b * F + c]; }
+  m /= (double)B; s /= (double)B;
+  const double wd = (double)w;
+  glob_mean[c] = (float)(w >= 1.f ? m : (1.0 - wd) * (double)glob_mean[c] + wd * m);
+  glob_std[c] = (float)(w >= 1.f ? s : (1.0 - wd) * (double)glob_std[c] + wd * s);
 }
 
 // Y[b,t,c] = (X[b,t,c] - mean[b*stride + c]) / std[b*stride + c]   (stride 0: shared statistics)
@@ -696,7 +705,7 @@ extern "C" int smx_mel_db(int out_dtype, const float* spec, int64_t lds, int im_
   int mblocks = (N + 3) / 4;
   if (mblocks > 2048) mblocks = 2048;
   hipLaunchKernelGGL(mel_db_kernel, dim3(mblocks), dim3(256), (4 * n_bins + n_mels * 48) * sizeof(float), STREAM, spec, lds, im_off, fb, n_bins,
-                     n_mels, amin, db, bmax, N);
+                     n_mels, amin, (float)(10.0 * log10((double)amin)), db, bmax, N);
   hipLaunchKernelGGL(utt_max_kernel, dim3(B), dim3(256), 0, STREAM, bmax, T, 1, umax);
   const long total = (long)N * n_mels;
   if (out_dtype == SMX_BF16) hipLaunchKernelGGL((topdb_clamp_kernel<bf16_t>), dim3(fgrid(total)), dim3(256), 0, STREAM, db, umax, top_db, (bf16_t*)out, (long)T * n_mels, total);

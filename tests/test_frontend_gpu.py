@@ -1,5 +1,8 @@
 """Front-end kernels against this repo's CPU spec in oracle/smx_oracle.py (the reference pins
-nothing here: the arithmetic is un-vendored SpeechBrain code -> 'parity unpinned', self-consistency tests)."""
+nothing here: the arithmetic is un-vendored SpeechBrain code -> 'parity unpinned', self-consistency tests).  These are the
+end-to-end tests at the recipe's shapes; the stage-level tests of the log-mel filterbank (every Fbank.forward route, every branch of
+the mel / dB kernel, the clamp) are tests/test_fbank_kernels_gpu.py with its float64 restatement tests/_fbank_ref.py (pinned on the
+CPU by tests/test_fbank_ref_cpu.py), those of InputNormalization's three kernels tests/test_input_norm_kernels_gpu.py."""
 import pytest
 import torch
 
