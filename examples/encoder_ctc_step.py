@@ -3,7 +3,10 @@
 waveform -> Fbank -> InputNormalization -> ConvolutionFrontEnd -> TransformerASR.encode -> proj_enc -> proj_ctc ->
 log_softmax -> ctc_cost, optimised by the flat-buffer AdamW (needs an MI355X; synthetic data).
 
-    python examples/encoder_ctc_step.py [--steps 20] [--batch 16] [--seconds 8]
+    python examples/encoder_ctc_step.py [--steps 20] [--batch 16] [--seconds 8] [--augment]
+
+--augment inserts the recipe's fea_augment (time drops, frequency drops, time warp: yaml:195-245) between the filterbank and the
+normalisation, where upstream's transducer train.py applies it; off by default.
 
 The module names and constructor arguments are the ones the reference YAML passes (…/LibriSpeech/ASR/transducer/
 hparams/conformer_summarymixing_transducer.yaml); only the import root changes: speechbrain.* -> summarymixing_amd.*."""
@@ -15,6 +18,8 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from summarymixing_amd.augment.augmenter import Augmenter                                     # noqa: E402
+from summarymixing_amd.augment.freq_domain import SpectrogramDrop, Warping                  # noqa: E402
 from summarymixing_amd.lobes.features import Fbank, InputNormalization                     # noqa: E402
 from summarymixing_amd.lobes.models.convolution import ConvolutionFrontEnd                   # noqa: E402
 from summarymixing_amd.lobes.models.transformer.TransformerASR import EncoderWrapper, TransformerASR  # noqa: E402
@@ -25,8 +30,18 @@ from summarymixing_amd.trainer import FlatAdamW                                 
 
 
 class EncoderSide(torch.nn.Module):
-    def __init__(self, d_model=256, d_ffn=1024, layers=12, joint_dim=640, vocab=1000):
+    def __init__(self, d_model=256, d_ffn=1024, layers=12, joint_dim=640, vocab=1000, augment=False):
         super().__init__()
+        self.fea_augment = None
+        if augment:
+            time_drop = SpectrogramDrop(drop_length_low=15, drop_length_high=25, drop_count_low=5, drop_count_high=5,
+                                        replace="zeros", dim=1)
+            freq_drop = SpectrogramDrop(drop_length_low=25, drop_length_high=35, drop_count_low=2, drop_count_high=2,
+                                        replace="zeros", dim=2)
+            time_warp = Warping(warp_window=5, warp_mode="bicubic", dim=1)
+            self.fea_augment = Augmenter(parallel_augment=False, concat_original=False, repeat_augment=1, shuffle_augmentations=False,
+                                         min_augmentations=3, max_augmentations=3, augment_prob=1.0,
+                                         augmentations=[time_drop, freq_drop, time_warp])
         self.compute_features = Fbank(sample_rate=16000, n_fft=512, n_mels=80, win_length=32)
         self.normalize = InputNormalization(norm_type="global", update_until_epoch=4)
         self.CNN = ConvolutionFrontEnd((None, None, 80), num_blocks=2, num_layers_per_block=1, out_channels=(64, 32),
@@ -41,7 +56,10 @@ class EncoderSide(torch.nn.Module):
         self.log_softmax = Softmax(apply_log=True)
 
     def forward(self, wav, wav_lens, epoch=0):
-        feats = self.normalize(self.compute_features(wav, out_dtype=torch.bfloat16), wav_lens, epoch=epoch)
+        feats = self.compute_features(wav, out_dtype=torch.bfloat16)
+        if self.fea_augment is not None and self.training:
+            feats, _ = self.fea_augment(feats, wav_lens)
+        feats = self.normalize(feats, wav_lens, epoch=epoch)
         x = self.enc(self.CNN(feats), wav_lens)
         return self.log_softmax(self.proj_ctc(self.proj_enc(x)).float())
 
@@ -51,9 +69,10 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--seconds", type=float, default=8.0)
+    ap.add_argument("--augment", action="store_true", help="apply the recipe's fea_augment to the features")
     args = ap.parse_args()
     torch.manual_seed(0)
-    model = EncoderSide().cuda().train()
+    model = EncoderSide(augment=args.augment).cuda().train()
     opt = FlatAdamW(model, lr=8e-4, betas=(0.9, 0.98), weight_decay=0.01, max_grad_norm=5.0, compute_dtype=torch.bfloat16)
     B, L = args.batch, int(16000 * args.seconds)
     wav = torch.randn(B, L, device="cuda") * 0.1

@@ -781,6 +781,39 @@ int smx_slot_begin(int dtype, int64_t* counters, const uint8_t* start, const voi
                    int64_t ldpe, int B, int C, int D, void* stream);
 int smx_slot_advance(int64_t* counters, const int32_t* valid, int B, int C, void* stream);
 
+/* ---- Feature augmentation: the recipes' fea_augment (…/transducer/hparams/conformer_summarymixing_transducer.yaml:195-245) ------
+ * speechbrain.augment.freq_domain.SpectrogramDrop along time (dim 1), SpectrogramDrop along frequency (dim 2) and Warping (bicubic)
+ * on x (B, T, F), in that order, as one draw launch and one apply launch.  The draws live in an int32 PARAMETER BLOCK on the device:
+ *   [0] flags: SMX_SPECAUG_WARP | SMX_SPECAUG_TIME | SMX_SPECAUG_FREQ (a clear bit: that stage is the identity)
+ *   [1] c   [2] w     the warp: output rows [0, w) resample source rows [0, c), output rows [w, T) resample source rows [c, T)
+ *   [3] n_time   [4] n_freq     drops per row in force, one value for the whole batch (clamped to the caps)
+ *   [5..7] reserved (0)
+ *   then (pos, len)[B][n_time_cap]: row b drops the frames pos <= t < pos + len of its first n_time pairs (clipped at T)
+ *   then (pos, len)[B][n_freq_cap]: likewise along F
+ * A cap is a stage's drop_count_high (0 for an absent stage), at most 32.  smx_specaug_params_bytes: the block's size (0 for
+ * arguments out of range).
+ * smx_specaug_draw fills a block and writes nothing else: n uniform on [cnt_lo, cnt_hi], len on [len_lo, len_hi), pos on [0, T) or
+ *   [0, F); with T - window > window, c uniform on [window, T - window) and w on [c - window + 1, c + window], otherwise the warp
+ *   bit stays clear.  `stages`: the flag bits to draw for; the caps of the block are t_cnt_hi / f_cnt_hi of the stages present.
+ *   Every value is one 32-bit hash of (seed, *epoch, which value, index) - the counter-based generator of the dropout masks with a
+ *   salt of its own - scaled as (h * range) >> 32: no host synchronisation, no atomics, and a captured draw advances with the
+ *   device step counter `epoch` (NULL: by value, see smx_step_counter_add).
+ * smx_specaug_apply: Y = the three stages applied to X, a pure function of X and the block.  X, Y: (B * T) rows of F elements with
+ *   leading dimensions ldx, ldy.  Each output row gathers at most four source rows (torch's bicubic, align_corners = True: position
+ *   num / den with num = t * (n_in - 1), den = n_out - 1 in integer arithmetic, taps clamped into the segment, A = -0.75);
+ *   a tap dropped along time contributes nothing and is not loaded, so the warp interpolates across the zeroed frames exactly as
+ *   the sequential chain does; dropped columns are +0.  float32 accumulation, one rounding.  A row whose position falls on a
+ *   source row - every row when the warp bit is clear - is copied bit for bit.  16-byte accesses when F, ldx, ldy are multiples of
+ *   4 (F32) / 8 (BF16) and X, Y are 16-byte aligned, element accesses otherwise.  SMX_EUNSUPPORTED: F > 1024, a cap > 32, X == Y,
+ *   B > 65535. */
+enum { SMX_SPECAUG_WARP = 1, SMX_SPECAUG_TIME = 2, SMX_SPECAUG_FREQ = 4 };
+size_t smx_specaug_params_bytes(int B, int n_time_cap, int n_freq_cap);
+int smx_specaug_draw(int32_t* params, int B, int T, int F, int stages, int t_len_lo, int t_len_hi, int t_cnt_lo, int t_cnt_hi,
+                     int f_len_lo, int f_len_hi, int f_cnt_lo, int f_cnt_hi, int warp_window, uint64_t seed, const uint64_t* epoch,
+                     void* stream);
+int smx_specaug_apply(int dtype, const void* X, int64_t ldx, void* Y, int64_t ldy, const int32_t* params, int B, int T, int F,
+                      int n_time_cap, int n_freq_cap, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

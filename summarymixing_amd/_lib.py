@@ -22,6 +22,7 @@ EPI_LN_FWD = 8
 IO_RES_F32, IO_LNX_F32, IO_LNFY_F32 = 1, 2, 4
 PAD_ZERO, PAD_REFLECT = 0, 1
 DW_TILED, DW_WINDOW, DW_ROLL, DW_ROLL_CSGU = 0, 1, 2, 3
+SPECAUG_WARP, SPECAUG_TIME, SPECAUG_FREQ = 1, 2, 4
 ACTS = {"none": ACT_NONE, "identity": ACT_NONE, "gelu": ACT_GELU, "swish": ACT_SWISH,
         "leaky_relu": ACT_LEAKY_RELU, "relu": ACT_RELU}
 
@@ -242,6 +243,9 @@ SIGNATURES = {
     "smx_dwconv1d_glu_slots": (c_i, [c_i, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i, c_i, c_i, c_i, c_vp]),
     "smx_slot_begin": (c_i, [c_i, c_vp, c_vp, c_vp, c_i64, c_i, c_vp, c_i64, c_i, c_i, c_i, c_vp]),
     "smx_slot_advance": (c_i, [c_vp, c_vp, c_i, c_i, c_vp]),
+    "smx_specaug_params_bytes": (c_sz, [c_i, c_i, c_i]),
+    "smx_specaug_draw": (c_i, [c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, ctypes.c_uint64, c_vp, c_vp]),
+    "smx_specaug_apply": (c_i, [c_i, c_vp, c_i64, c_vp, c_i64, c_vp, c_i, c_i, c_i, c_i, c_i, c_vp]),
 }
 
 _lib = None

@@ -1491,3 +1491,30 @@ def input_proj_pe(src3, W, b, pe, T, p=0.0):
             return dx.view(xin.shape) if dx is not None else None
         return y.view(B, T, -1), bwd
     return block(src3, run, [W, b])
+
+
+# ---- feature augmentation (summarymixing_amd.augment) -------------------------------------------------------------------------
+class SpecAugBlock(collections.namedtuple("SpecAugBlock", "data n_time_cap n_freq_cap")):
+    """The draws of one fea_augment call: `data` is the int32 device block of include/smx.h (flags, c, w, n_time, n_freq, three
+    reserved words, then (pos, len)[B][n_time_cap] and (pos, len)[B][n_freq_cap]); the caps say how it is laid out."""
+    __slots__ = ()
+
+
+def spec_augment_draw(B, T, F, device, stages, time_drop=None, freq_drop=None, window=5, seed=None):
+    """A fresh SpecAugBlock drawn on the device for x (B, T, F): time_drop / freq_drop are (len_lo, len_hi, cnt_lo, cnt_hi) of the
+    stages in `stages` (L.SPECAUG_* bits).  No host synchronisation; the device step counter, when set, is mixed into the seed."""
+    if torch.device(device).type != "cuda":
+        raise RuntimeError(ops.NO_CPU)
+    ntc = time_drop[3] if stages & L.SPECAUG_TIME else 0
+    nfc = freq_drop[3] if stages & L.SPECAUG_FREQ else 0
+    data = torch.empty(ops.specaug_params_words(B, ntc, nfc), dtype=torch.int32, device=device)
+    ops.specaug_draw(data, B, T, F, stages, time_drop, freq_drop, window, ops.new_dropout_seed() if seed is None else seed)
+    return SpecAugBlock(data, ntc, nfc)
+
+
+def spec_augment(x, params):
+    """The recipes' fea_augment on x (B, T, F) with explicit draws: time drops, frequency drops, then the bicubic time warp, in one
+    pass (smx_specaug_apply).  params: a SpecAugBlock.  Returns a new tensor; there is no backward (features carry no gradient)."""
+    if x.dim() != 3:
+        raise ValueError(f"spec_augment takes (batch, time, features) input, got {tuple(x.shape)}")
+    return ops.specaug_apply(x.detach(), params.data, params.n_time_cap, params.n_freq_cap)

@@ -842,6 +842,48 @@ def colnorm(x2, mean, std, stat_stride, out, B, T):
             "smx_colnorm")
 
 
+SPECAUG_HDR = 8     # header words of the spec-augment parameter block (include/smx.h)
+
+
+def specaug_params_words(B, n_time_cap, n_freq_cap):
+    """int32 words of the parameter block of smx_specaug_draw / smx_specaug_apply."""
+    nbytes = L.lib().smx_specaug_params_bytes(B, n_time_cap, n_freq_cap)
+    if nbytes == 0:
+        raise ValueError(f"spec-augment block: B = {B} must be positive and the caps ({n_time_cap}, {n_freq_cap}) within 0 .. 32")
+    return nbytes // 4
+
+
+def specaug_draw(params, B, T, F, stages, time_drop, freq_drop, window, seed):
+    """Fill `params` on the device.  time_drop / freq_drop: (len_lo, len_hi, cnt_lo, cnt_hi) or None; the step counter is mixed in."""
+    assert params.is_cuda, NO_CPU
+    t, f = time_drop or (0, 1, 0, 0), freq_drop or (0, 1, 0, 0)
+    ntc, nfc = (t[3] if stages & L.SPECAUG_TIME else 0), (f[3] if stages & L.SPECAUG_FREQ else 0)
+    assert params.dtype == torch.int32 and params.is_contiguous() and params.numel() >= specaug_params_words(B, ntc, nfc)
+    L.check(L.lib().smx_specaug_draw(_p(params), B, T, F, stages, t[0], t[1], t[2], t[3], f[0], f[1], f[2], f[3], window,
+                                     seed & 0xFFFFFFFFFFFFFFFF, _epoch(), _stream()), "smx_specaug_draw")
+    return params
+
+
+def specaug_apply(x, params, n_time_cap, n_freq_cap, out=None):
+    """x (B, T, F) -> the augmented copy: one pass over x with the draws of `params` (smx_specaug_apply)."""
+    if not x.is_cuda or not params.is_cuda:
+        raise RuntimeError(NO_CPU)
+    B, T, F = x.shape
+    assert params.dtype == torch.int32 and params.is_contiguous() and params.numel() >= specaug_params_words(B, n_time_cap, n_freq_cap)
+    x2 = rows2d(x)
+    if out is None:
+        out = torch.empty((B, T, F), dtype=x.dtype, device=x.device)
+    o2 = rows2d(out)
+    assert o2.data_ptr() == out.data_ptr() and o2.dtype == x.dtype
+    px, ldx = _mat(x2)
+    po, ldo = _mat(o2)
+    tok = _pb(f"specaug ({B}x{T}x{F})", 2 * B * T * F * _es(x))
+    L.check(L.lib().smx_specaug_apply(dt(x), px, ldx, po, ldo, _p(params), B, T, F, n_time_cap, n_freq_cap, _stream()),
+            "smx_specaug_apply")
+    _pe(tok)
+    return out
+
+
 def log_softmax_fwd(x):
     """log_softmax over the last dim of a (N, V) view."""
     N, V = x.shape
