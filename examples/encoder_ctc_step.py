@@ -3,10 +3,12 @@
 waveform -> Fbank -> InputNormalization -> ConvolutionFrontEnd -> TransformerASR.encode -> proj_enc -> proj_ctc ->
 log_softmax -> ctc_cost, optimised by the flat-buffer AdamW (needs an MI355X; synthetic data).
 
-    python examples/encoder_ctc_step.py [--steps 20] [--batch 16] [--seconds 8] [--augment]
+    python examples/encoder_ctc_step.py [--steps 20] [--batch 16] [--seconds 8] [--augment] [--wav-augment]
 
 --augment inserts the recipe's fea_augment (time drops, frequency drops, time warp: yaml:195-245) between the filterbank and the
 normalisation, where upstream's transducer train.py applies it; off by default.
+--wav-augment applies the recipe's wav_augment (SpeedPerturb at speeds 95 / 100 / 105: yaml:177-192) to the waveform batch before
+the filterbank, where upstream's train.py applies it; off by default.
 
 The module names and constructor arguments are the ones the reference YAML passes (…/LibriSpeech/ASR/transducer/
 hparams/conformer_summarymixing_transducer.yaml); only the import root changes: speechbrain.* -> summarymixing_amd.*."""
@@ -20,6 +22,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from summarymixing_amd.augment.augmenter import Augmenter                                     # noqa: E402
 from summarymixing_amd.augment.freq_domain import SpectrogramDrop, Warping                  # noqa: E402
+from summarymixing_amd.augment.time_domain import SpeedPerturb                               # noqa: E402
 from summarymixing_amd.lobes.features import Fbank, InputNormalization                     # noqa: E402
 from summarymixing_amd.lobes.models.convolution import ConvolutionFrontEnd                   # noqa: E402
 from summarymixing_amd.lobes.models.transformer.TransformerASR import EncoderWrapper, TransformerASR  # noqa: E402
@@ -30,8 +33,13 @@ from summarymixing_amd.trainer import FlatAdamW                                 
 
 
 class EncoderSide(torch.nn.Module):
-    def __init__(self, d_model=256, d_ffn=1024, layers=12, joint_dim=640, vocab=1000, augment=False):
+    def __init__(self, d_model=256, d_ffn=1024, layers=12, joint_dim=640, vocab=1000, augment=False, wav_augment=False):
         super().__init__()
+        self.wav_augment = None
+        if wav_augment:
+            speed_perturb = SpeedPerturb(orig_freq=16000, speeds=[95, 100, 105])
+            self.wav_augment = Augmenter(parallel_augment=False, concat_original=False, repeat_augment=1, shuffle_augmentations=False,
+                                         min_augmentations=1, max_augmentations=1, augment_prob=1.0, augmentations=[speed_perturb])
         self.fea_augment = None
         if augment:
             time_drop = SpectrogramDrop(drop_length_low=15, drop_length_high=25, drop_count_low=5, drop_count_high=5,
@@ -56,6 +64,8 @@ class EncoderSide(torch.nn.Module):
         self.log_softmax = Softmax(apply_log=True)
 
     def forward(self, wav, wav_lens, epoch=0):
+        if self.wav_augment is not None and self.training:
+            wav, wav_lens = self.wav_augment(wav, wav_lens)
         feats = self.compute_features(wav, out_dtype=torch.bfloat16)
         if self.fea_augment is not None and self.training:
             feats, _ = self.fea_augment(feats, wav_lens)
@@ -70,9 +80,10 @@ def main():
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--seconds", type=float, default=8.0)
     ap.add_argument("--augment", action="store_true", help="apply the recipe's fea_augment to the features")
+    ap.add_argument("--wav-augment", action="store_true", help="apply the recipe's wav_augment (speed perturbation) to the waveforms")
     args = ap.parse_args()
     torch.manual_seed(0)
-    model = EncoderSide(augment=args.augment).cuda().train()
+    model = EncoderSide(augment=args.augment, wav_augment=args.wav_augment).cuda().train()
     opt = FlatAdamW(model, lr=8e-4, betas=(0.9, 0.98), weight_decay=0.01, max_grad_norm=5.0, compute_dtype=torch.bfloat16)
     B, L = args.batch, int(16000 * args.seconds)
     wav = torch.randn(B, L, device="cuda") * 0.1

@@ -814,6 +814,32 @@ int smx_specaug_draw(int32_t* params, int B, int T, int F, int stages, int t_len
 int smx_specaug_apply(int dtype, const void* X, int64_t ldx, void* Y, int64_t ldy, const int32_t* params, int B, int T, int F,
                       int n_time_cap, int n_freq_cap, void* stream);
 
+/* ---- Waveform augmentation: the recipes' wav_augment (…/transducer/hparams/conformer_summarymixing_transducer.yaml:177-192) -----
+ * speechbrain.augment.time_domain.SpeedPerturb (speed_perturb, yaml:177-179: orig_freq 16000, speeds [95, 100, 105]) resamples the
+ * batch with speechbrain's Resample = torchaudio's polyphase windowed-sinc filter at its defaults (sinc_interp_hann,
+ * lowpass_filter_width 6, rolloff 0.99); the Augmenter around it (wav_augment, yaml:181-192) applies that one stage to every batch.
+ * With g = gcd(orig_freq, new_freq), o = orig_freq / g, n = new_freq / g, base = min(o, n) * 0.99, width = ceil(6 * o / base) and
+ * K = 2 * width + o, phase p in [0, n) has the taps
+ *   h[p][k] = sinc(pi t) cos^2(pi t / 12) base / o,  t = clamp(((k - width) / o - p / n) base, -6, 6),  k in [0, K),
+ * evaluated in float64 and rounded to float32, and row x[0, L) (zero outside) gives L_out = ceil(n L / o) outputs
+ *   y[q n + p] = sum_k h[p][k] x[q o + k - width].
+ * The nonzero float32 taps of a phase are one contiguous run; `taps` is the longest run of the plan.
+ * smx_resample_plan (host only, touches no GPU; yaml:177-179 fixes the three ratios a recipe needs) fills info[8] =
+ *   {o, n, width, K, taps, Q, 0, 0} (Q: whole n-sample output blocks per workgroup tile), *image_bytes (may be NULL) and, when `image`
+ *   is not NULL, the PLAN IMAGE of image_bytes bytes (SMX_EINVAL if image_capacity is smaller): int32 info[8], int32 first[n] (index
+ *   k of the first nonzero tap of phase p), float32 w[n][taps] (w[p][j] = h[p][first[p] + j], zero behind the run).
+ *   SMX_EUNSUPPORTED: a rate <= 0; n * taps > 8192 floats (the table lives in LDS; more than 1024 phases are refused before any tap
+ *   is evaluated); K + taps + o + 3 > 4096 samples (one block's input does not fit a workgroup's span).
+ * smx_resample (yaml:181-192, the pass wav_augment makes): Y[b][0, L_out) = the resampled X[b][0, L) for b < B, float32, `plan` the
+ *   image on the device; writes exactly those elements (ldy >= L_out is the caller's to guarantee: o and n live on the device).
+ *   One launch, no allocation, no host synchronisation.  Each output is summed in ascending k with one float32 fused multiply-add
+ *   per tap of the run, so two runs agree bit for bit and a unit impulse returns the taps themselves.  16-byte loads when X is
+ *   16-byte aligned and ldx % 4 == 0, 16-byte stores when Y is and ldy % 4 == 0, element accesses otherwise (same bits).  No
+ *   length masking: the padded tail of a row is resampled like any other sample.  SMX_EINVAL: L < 1, ldx < L;
+ *   SMX_EUNSUPPORTED: X == Y, B > 65535.  A block that is not a plan image writes nothing. */
+int smx_resample_plan(int orig_freq, int new_freq, int32_t* info, size_t* image_bytes, void* image, size_t image_capacity);
+int smx_resample(const float* X, int64_t ldx, float* Y, int64_t ldy, const int32_t* plan, int B, int64_t L, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -246,6 +246,8 @@ SIGNATURES = {
     "smx_specaug_params_bytes": (c_sz, [c_i, c_i, c_i]),
     "smx_specaug_draw": (c_i, [c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, ctypes.c_uint64, c_vp, c_vp]),
     "smx_specaug_apply": (c_i, [c_i, c_vp, c_i64, c_vp, c_i64, c_vp, c_i, c_i, c_i, c_i, c_i, c_vp]),
+    "smx_resample_plan": (c_i, [c_i, c_i, c_vp, c_vp, c_vp, c_sz]),
+    "smx_resample": (c_i, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i, c_i64, c_vp]),
 }
 
 _lib = None

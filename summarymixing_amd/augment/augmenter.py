@@ -6,6 +6,7 @@ import torch.nn as nn
 from .. import _lib as L
 from .. import functional as SF
 from .freq_domain import SpectrogramDrop, Warping, _features
+from .time_domain import Resample, SpeedPerturb
 
 # what the constructor accepts for the options that are not built: name -> the values that mean "off"
 _FIXED = {"parallel_augment": (False,), "concat_original": (False,), "shuffle_augmentations": (False,), "repeat_augment": (1,),
@@ -21,8 +22,9 @@ def _slot(m):
 
 
 class Augmenter(nn.Module):
-    """forward(x, lengths) -> (augmented x, lengths).  A list that is a subsequence of [SpectrogramDrop(dim=1),
-    SpectrogramDrop(dim=2), Warping] runs as ONE draw launch and ONE pass over x (drops first, then the warp, which interpolates
+    """forward(x, lengths) -> (augmented x, lengths).  A list of one waveform stage (the recipes' wav_augment: [SpeedPerturb] with
+    min_augmentations = max_augmentations = 1) resamples the batch (B, T) -> (B, T') in one launch.  A list that is a subsequence
+    of [SpectrogramDrop(dim=1), SpectrogramDrop(dim=2), Warping] runs as ONE draw launch and ONE pass over x (drops first, then the warp, which interpolates
     across the zeroed stripes exactly as the module-by-module chain does); any other list runs module by module through the
     same kernel.  `seed` / `last_params`: as on the stages (freq_domain._Stage)."""
 
@@ -42,16 +44,27 @@ class Augmenter(nn.Module):
             if value is not None and value != len(augmentations):
                 raise NotImplementedError(f"Augmenter({name}={value!r}) is not built: every augmentation runs on every call "
                                           f"({name}=None or {len(augmentations)})")
+        # the recipes' wav_augment (…transducer.yaml:181-192): one waveform stage, applied to every batch
+        wave = [isinstance(m, (SpeedPerturb, Resample)) for m in augmentations]
+        self.waveform = any(wave)
+        if self.waveform and not all(wave):
+            raise NotImplementedError("augmentations: a list that mixes waveform stages (SpeedPerturb, Resample) with spectrogram "
+                                      "stages (SpectrogramDrop, Warping) is not built: wav_augment and fea_augment are two Augmenters")
+        if self.waveform and len(augmentations) > 1:
+            raise NotImplementedError(f"augmentations: {len(augmentations)} waveform stages are not built (one is: the recipes' "
+                                      "[speed_perturb])")
         for m in augmentations:
-            if _slot(m) is None:
+            if _slot(m) is None and not self.waveform:
                 raise NotImplementedError(f"augmentations: {type(m).__name__} is not built (SpectrogramDrop and Warping are)")
         self.augmentations = nn.ModuleList(augmentations)
         slots = [_slot(m) for m in augmentations]
-        self.fused = len(slots) > 0 and all(a < b for a, b in zip(slots, slots[1:]))
+        self.fused = not self.waveform and len(slots) > 0 and all(a < b for a, b in zip(slots, slots[1:]))
         self.seed = None
         self.last_params = None
 
     def forward(self, x, lengths):
+        if self.waveform:                                    # (B, T) samples; relative lengths stay what they were
+            return self.augmentations[0](x), lengths
         x = _features(x)
         if self.fused:
             B, T, F = x.shape

@@ -1518,3 +1518,56 @@ def spec_augment(x, params):
     if x.dim() != 3:
         raise ValueError(f"spec_augment takes (batch, time, features) input, got {tuple(x.shape)}")
     return ops.specaug_apply(x.detach(), params.data, params.n_time_cap, params.n_freq_cap)
+
+
+# ---- waveform augmentation (summarymixing_amd.augment.time_domain) --------------------------------------------------------------
+_RESAMPLE_PLANS = {}     # (orig_freq, new_freq) -> ops.ResamplePlan (host)
+_RESAMPLE_IMAGES = {}    # (orig_freq, new_freq, device) -> the plan image on that device
+
+
+def resample_plan(orig_freq, new_freq, device=None):
+    """(ops.ResamplePlan, its image on `device` or None), each built once per ratio / per device and kept."""
+    key = (int(orig_freq), int(new_freq))
+    plan = _RESAMPLE_PLANS.get(key)
+    if plan is None:
+        plan = _RESAMPLE_PLANS[key] = ops.resample_plan(*key)
+    if device is None:
+        return plan, None
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(ops.NO_CPU)
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    image = _RESAMPLE_IMAGES.get(key + (device,))
+    if image is None:
+        image = _RESAMPLE_IMAGES[key + (device,)] = plan.image.to(device)
+    return plan, image
+
+
+def resample(x, orig_freq, new_freq, out=None):
+    """x (B, L) float32 resampled from orig_freq to new_freq -> (B, ceil(n L / o)): torchaudio's polyphase windowed-sinc filter at its
+    defaults (what speechbrain's Resample computes), one launch (smx_resample).  The padded tail of a row is resampled like any
+    other sample.  Equal rates return x itself, with no launch.  out: a (B, L_out) float32 view to write into (unit inner stride).
+    The first call for a ratio on a device builds and uploads its plan; later calls allocate only the output, and with `out`
+    nothing, so they can be captured.  There is no backward (waveforms carry no gradient)."""
+    if x.dim() != 2:
+        raise ValueError(f"resample takes (batch, time) input, got {tuple(x.shape)}")
+    if int(orig_freq) == int(new_freq):
+        return x
+    if not x.is_cuda:
+        raise RuntimeError(ops.NO_CPU)
+    if x.dtype != torch.float32:
+        raise NotImplementedError(f"resample: float32 waveforms only, got {x.dtype}")
+    plan, image = resample_plan(orig_freq, new_freq, x.device)
+    B, Lin = x.shape
+    if B < 1 or Lin < 1:
+        raise ValueError(f"resample needs a non-empty batch, got {tuple(x.shape)}")
+    x = x.detach()
+    if x.stride(1) != 1:
+        x = x.contiguous()
+    Lout = plan.out_len(Lin)
+    if out is None:
+        out = torch.empty((B, Lout), dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (B, Lout) or out.dtype != torch.float32 or out.device != x.device or (Lout > 1 and out.stride(1) != 1):
+        raise ValueError(f"resample: out must be a float32 (B, L_out) = ({B}, {Lout}) view with unit inner stride on {x.device}")
+    return ops.resample(x, image, out, Lin)

@@ -4,6 +4,7 @@ torch is plumbing here: tensors own device memory, ``data_ptr()`` / strides / th
 handed to the kernels.  All arithmetic happens in the hand-written gfx950 kernels.  Matrices are 2-D
 views ``(rows, cols)`` with unit stride along cols; the row stride is the leading dimension.
 """
+import collections
 import ctypes
 
 
@@ -882,6 +883,53 @@ def specaug_apply(x, params, n_time_cap, n_freq_cap, out=None):
             "smx_specaug_apply")
     _pe(tok)
     return out
+
+
+class ResamplePlan(collections.namedtuple("ResamplePlan", "o n width K taps tile_blocks image")):
+    """smx_resample_plan's result: the reduced rates, the filter's half width and length, the longest run of nonzero taps, the
+    n-sample output blocks per workgroup tile, and the plan image (int32 words, on the CPU) of include/smx.h."""
+    __slots__ = ()
+
+    def out_len(self, L):
+        """ceil(n L / o) in exact integers."""
+        return (self.n * int(L) + self.o - 1) // self.o
+
+    def first(self):
+        return self.image[8:8 + self.n]
+
+    def weights(self):
+        return self.image[8 + self.n:].view(torch.float32).view(self.n, self.taps)
+
+
+def resample_plan(orig_freq, new_freq):
+    """The polyphase plan of orig_freq -> new_freq (host arithmetic, no GPU).  NotImplementedError for a ratio the kernel cannot
+    hold (SMX_EUNSUPPORTED: the table or one block's input does not fit LDS, a rate <= 0)."""
+    info = (ctypes.c_int32 * 8)()
+    nbytes = ctypes.c_size_t(0)
+    code = L.lib().smx_resample_plan(int(orig_freq), int(new_freq), info, ctypes.byref(nbytes), None, 0)
+    if code == -2:
+        raise NotImplementedError(L.lib().smx_last_error().decode())
+    L.check(code, "smx_resample_plan")
+    image = torch.zeros(nbytes.value // 4, dtype=torch.int32)
+    L.check(L.lib().smx_resample_plan(int(orig_freq), int(new_freq), info, None, ctypes.c_void_p(image.data_ptr()), nbytes.value),
+            "smx_resample_plan")
+    return ResamplePlan(*list(info)[:6], image)
+
+
+def resample(x2, image, out2, L_in):
+    """out2[b][0, L_out) = the resampled x2[b][0, L_in): x2 (B, >= L_in), out2 (B, L_out) float32 views with unit inner stride, image
+    the plan image on their device (smx_resample).  L_out is out2's width and the caller's to get right (ResamplePlan.out_len)."""
+    if not (x2.is_cuda and out2.is_cuda and image.is_cuda):
+        raise RuntimeError(NO_CPU)
+    assert x2.dtype == torch.float32 and out2.dtype == torch.float32 and image.dtype == torch.int32 and image.is_contiguous()
+    B = x2.shape[0]
+    assert out2.shape[0] == B and x2.shape[1] >= L_in
+    px, ldx = _mat(x2)
+    po, ldo = _mat(out2)
+    tok = _pb(f"resample ({B}x{L_in})", 4 * B * (L_in + out2.shape[1]))
+    L.check(L.lib().smx_resample(px, ldx, po, ldo, _p(image), B, L_in, _stream()), "smx_resample")
+    _pe(tok)
+    return out2
 
 
 def log_softmax_fwd(x):
