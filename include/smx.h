@@ -840,6 +840,41 @@ int smx_specaug_apply(int dtype, const void* X, int64_t ldx, void* Y, int64_t ld
 int smx_resample_plan(int orig_freq, int new_freq, int32_t* info, size_t* image_bytes, void* image, size_t image_capacity);
 int smx_resample(const float* X, int64_t ldx, float* Y, int64_t ldy, const int32_t* plan, int B, int64_t L, void* stream);
 
+/* ---- Label-smoothed sequence losses and accuracy: the recipes' second loss head ------------------------------------------------
+ * speechbrain.nnet.losses.kldiv_loss (`seq_cost` with `label_smoothing`, reduction batchmean:
+ * …/LibriSpeech/ASR/transformer/hparams/branchformer_summarymixing.yaml:278-280, and the AISHELL-1 / CommonVoice Branchformer recipes;
+ * V = 5000 / 5000 / 1000), speechbrain.nnet.losses.nll_loss (`ce_cost`, label_smoothing 0.1, the cross-entropy multitask head over
+ * the prediction network: …/LibriSpeech/ASR/transducer/hparams/conformer_summarymixing_transducer.yaml:319-320) and
+ * speechbrain.utils.Accuracy.AccuracyStats (`acc_computer`, the Branchformer recipes' validation).
+ * X: (B, U) rows of V elements (F32 or BF16), row (b, u) at X + b * bsx + u * ldx (a truncated view keeps its strides); targets int32,
+ * token (b, u) at targets[b * ldt + u].  One target distribution serves both losses: q[v] = off (v != y), q[y] = conf, and
+ *   row loss = cst - conf * lp[y] - off * (sum_v lp[v] - lp[y])
+ *   nll_loss, smoothing e:  conf = (1 - e) + e / V, off = e / V,       cst = 0
+ *   kldiv_loss, 0 < e < 1:  conf = 1 - e,           off = e / (V - 1), cst = conf log conf + (V - 1) off log off
+ * With off == 0 the row sum does not enter (a -inf away from y leaves the loss finite).
+ * keep[b, u] = (len == NULL || u < len[b]) && (pad_idx < 0 || y != pad_idx); len int32 (B) on the device.  A dropped row is not read.
+ * smx_seqloss_fwd, from_logits = 0: X holds log-probabilities.  from_logits = 1: X holds raw logits; the one read of the row carries
+ *   an online (max, sum exp), lse = max + log sum, lp[v] = X[v] - lse, sum lp = sum X - V lse, and lse (B * U, 2) receives the fp32
+ *   value and the fp32 residual of the fp64 one (the backward's exp(z - lse) needs both once the logits are large).
+ *   Outputs: row_loss (B * U) fp32 (0 for a dropped row), row_flags (B * U) int32 (bit 0 kept, bit 1 the row's argmax - first index
+ *   among equal entries - is the target), and, from a second launch that folds each utterance in a fixed order (no atomics: two runs
+ *   agree bit for bit), utt_loss (B) fp32 = the sum over kept rows, utt_kept (B), utt_hits (B, may be NULL) int32.
+ *   A target outside [0, V) on a kept row indexes nothing: its row loss is NaN and it counts as kept and not hit.
+ *   fp32 / fp64 arithmetic, the final combination in fp64 rounded once.
+ * smx_seqloss_bwd: g (B * U) fp32 = reduction weight * upstream gradient per row.  dX row r at dX + r * lddx, in the input dtype:
+ *   from_logits = 0: -g keep q (X, lse unused);  from_logits = 1: g keep (exp(X - lse) - q), lse as the forward wrote it.
+ *   Every element of every row is written: exact zeros for dropped rows, NaN for a kept row with a target outside [0, V).
+ * A row is cut into 16-byte groups anchored at its first column plus an element tail; a row whose address is 16-byte aligned moves
+ * a group per access (every row at V = 1000 or 5000, dense), any other row moves the same groups element by element: same bits either
+ * way.  No host synchronisation, no allocation: capturable.
+ * SMX_EINVAL: a NULL pointer, V < 1, ldx < V, ldt < U, NaN or negative off; SMX_EUNSUPPORTED: B * U >= 2^31, pad_idx >= V, X == dX. */
+int smx_seqloss_fwd(int dtype, int from_logits, const void* X, int64_t ldx, int64_t bsx, const int32_t* targets, int64_t ldt,
+                    const int32_t* len, int B, int U, int V, int pad_idx, float conf, float off, float cst, float* row_loss,
+                    float* lse, int32_t* row_flags, float* utt_loss, int32_t* utt_kept, int32_t* utt_hits, void* stream);
+int smx_seqloss_bwd(int dtype, int from_logits, const void* X, int64_t ldx, int64_t bsx, const int32_t* targets, int64_t ldt,
+                    const int32_t* len, int B, int U, int V, int pad_idx, float conf, float off, const float* lse, const float* g,
+                    void* dX, int64_t lddx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -248,6 +248,10 @@ SIGNATURES = {
     "smx_specaug_apply": (c_i, [c_i, c_vp, c_i64, c_vp, c_i64, c_vp, c_i, c_i, c_i, c_i, c_i, c_vp]),
     "smx_resample_plan": (c_i, [c_i, c_i, c_vp, c_vp, c_vp, c_sz]),
     "smx_resample": (c_i, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i, c_i64, c_vp]),
+    "smx_seqloss_fwd": (c_i, [c_i, c_i, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_vp, c_vp, c_vp,
+                              c_vp, c_vp, c_vp, c_vp]),
+    "smx_seqloss_bwd": (c_i, [c_i, c_i, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i, c_i, c_i, c_i, c_f, c_f, c_vp, c_vp, c_vp, c_i64,
+                              c_vp]),
 }
 
 _lib = None

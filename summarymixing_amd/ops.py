@@ -972,6 +972,60 @@ def ctc_bwd(lp2, targets, in_len, tgt_len, B, T, blank, nll, gscale, ws):
     return g
 
 
+# ---- label-smoothed sequence losses + accuracy (csrc/seqloss.hip).  x (B, U, V) with unit stride along V and any row / batch strides
+# (a truncated view is not copied); targets int32 (B, >= U) with unit stride along U; keep_len int32 (B) on the device or None.
+def _seq3(x, targets, keep_len):
+    if not (x.is_cuda and targets.is_cuda and (keep_len is None or keep_len.is_cuda)):
+        raise RuntimeError(NO_CPU)
+    assert x.dim() == 3 and targets.dim() == 2 and targets.dtype == torch.int32
+    B, U, V = x.shape
+    assert targets.shape[0] == B and targets.shape[1] >= U and (targets.shape[1] <= 1 or targets.stride(1) == 1)
+    assert V == 1 or x.stride(2) == 1, f"need unit stride along the vocabulary, got {x.stride()}"
+    assert keep_len is None or (keep_len.dtype == torch.int32 and keep_len.shape == (B,) and keep_len.is_contiguous())
+    ldx = x.stride(1) if U > 1 else max(x.stride(1), V)
+    bsx = x.stride(0) if B > 1 else 0
+    ldt = targets.stride(0) if B > 1 else max(targets.stride(0), U)
+    return B, U, V, ldx, bsx, ldt
+
+
+def seqloss_fwd(x, targets, keep_len, pad_idx, conf, off, cst, from_logits, want_hits=True):
+    """-> (row_loss (B, U) fp32, lse (B, U, 2) fp32 or None, row_flags (B, U) int32, utt_loss (B) fp32, utt_kept (B) int32,
+    utt_hits (B) int32 or None): smx_seqloss_fwd.  No host synchronisation."""
+    B, U, V, ldx, bsx, ldt = _seq3(x, targets, keep_len)
+    dev = x.device
+    row_loss = torch.empty((B, U), dtype=torch.float32, device=dev)
+    flags = torch.empty((B, U), dtype=torch.int32, device=dev)
+    lse = torch.empty((B, U, 2), dtype=torch.float32, device=dev) if from_logits else None
+    utt_loss = torch.empty((B,), dtype=torch.float32, device=dev)
+    utt_kept = torch.empty((B,), dtype=torch.int32, device=dev)
+    utt_hits = torch.empty((B,), dtype=torch.int32, device=dev) if want_hits else None
+    tok = _pb(f"seqloss_fwd {'logits' if from_logits else 'logprobs'} {'bf16' if _es(x) == 2 else 'f32'} ({B},{U},{V})",
+              B * U * V * _es(x) + B * U * (8 + 4 + (8 if from_logits else 0)))
+    L.check(L.lib().smx_seqloss_fwd(dt(x), int(bool(from_logits)), _p(x), ldx, bsx, _p(targets), ldt, _p(keep_len), B, U, V, int(pad_idx),
+                                    float(conf), float(off), float(cst), _p(row_loss), _p(lse), _p(flags), _p(utt_loss), _p(utt_kept),
+                                    _p(utt_hits), _stream()), "smx_seqloss_fwd")
+    _pe(tok)
+    return row_loss, lse, flags, utt_loss, utt_kept, utt_hits
+
+
+def seqloss_bwd(x, targets, keep_len, pad_idx, conf, off, lse, g, from_logits, out=None):
+    """g (B, U) fp32 contiguous -> dX (B, U, V) in x's dtype (torch.empty: the kernel writes every element, zeros for dropped rows):
+    smx_seqloss_bwd."""
+    B, U, V, ldx, bsx, ldt = _seq3(x, targets, keep_len)
+    assert g.is_cuda and g.dtype == torch.float32 and g.shape == (B, U) and g.is_contiguous()
+    assert not from_logits or (lse is not None and lse.shape == (B, U, 2) and lse.is_contiguous())
+    if out is None:
+        out = torch.empty((B, U, V), dtype=x.dtype, device=x.device)
+    assert out.shape == (B, U, V) and out.dtype == x.dtype and out.is_contiguous()
+    tok = _pb(f"seqloss_bwd {'logits' if from_logits else 'logprobs'} {'bf16' if _es(x) == 2 else 'f32'} ({B},{U},{V})",
+              (2 if from_logits else 1) * B * U * V * _es(x) + B * U * (8 + (8 if from_logits else 0)))
+    L.check(L.lib().smx_seqloss_bwd(dt(x), int(bool(from_logits)), _p(x) if from_logits else None, ldx, bsx, _p(targets), ldt,
+                                    _p(keep_len), B, U, V, int(pad_idx), float(conf), float(off), _p(lse), _p(g), _p(out), V, _stream()),
+            "smx_seqloss_bwd")
+    _pe(tok)
+    return out
+
+
 # ---- transducer head (csrc/transducer.hip).  Lattice rows (b, t, u), u fastest; every size below comes from tensor shapes and the
 # lengths stay on the device: no call here synchronises with the host.
 def transducer_joint_fwd(enc, dec, act):
