@@ -3,12 +3,14 @@
 waveform -> Fbank -> InputNormalization -> ConvolutionFrontEnd -> TransformerASR.encode -> proj_enc -> proj_ctc ->
 log_softmax -> ctc_cost, optimised by the flat-buffer AdamW (needs an MI355X; synthetic data).
 
-    python examples/encoder_ctc_step.py [--steps 20] [--batch 16] [--seconds 8] [--augment] [--wav-augment]
+    python examples/encoder_ctc_step.py [--steps 20] [--batch 16] [--seconds 8] [--augment] [--wav-augment] [--decode]
 
 --augment inserts the recipe's fea_augment (time drops, frequency drops, time warp: yaml:195-245) between the filterbank and the
 normalisation, where upstream's transducer train.py applies it; off by default.
 --wav-augment applies the recipe's wav_augment (SpeedPerturb at speeds 95 / 100 / 105: yaml:177-192) to the waveform batch before
 the filterbank, where upstream's train.py applies it; off by default.
+--decode prints, after the last step, the batch's hypotheses under CTC greedy decoding (speechbrain.decoders.ctc.ctc_greedy_decode:
+row arg-max, merge repeats, drop the blank - on the device, one copy to the host at the end).
 
 The module names and constructor arguments are the ones the reference YAML passes (…/LibriSpeech/ASR/transducer/
 hparams/conformer_summarymixing_transducer.yaml); only the import root changes: speechbrain.* -> summarymixing_amd.*."""
@@ -23,6 +25,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from summarymixing_amd.augment.augmenter import Augmenter                                     # noqa: E402
 from summarymixing_amd.augment.freq_domain import SpectrogramDrop, Warping                  # noqa: E402
 from summarymixing_amd.augment.time_domain import SpeedPerturb                               # noqa: E402
+from summarymixing_amd.decoders import ctc_greedy_decode                                     # noqa: E402
 from summarymixing_amd.lobes.features import Fbank, InputNormalization                     # noqa: E402
 from summarymixing_amd.lobes.models.convolution import ConvolutionFrontEnd                   # noqa: E402
 from summarymixing_amd.lobes.models.transformer.TransformerASR import EncoderWrapper, TransformerASR  # noqa: E402
@@ -81,6 +84,7 @@ def main():
     ap.add_argument("--seconds", type=float, default=8.0)
     ap.add_argument("--augment", action="store_true", help="apply the recipe's fea_augment to the features")
     ap.add_argument("--wav-augment", action="store_true", help="apply the recipe's wav_augment (speed perturbation) to the waveforms")
+    ap.add_argument("--decode", action="store_true", help="print the batch's CTC greedy hypotheses after the last step")
     args = ap.parse_args()
     torch.manual_seed(0)
     model = EncoderSide(augment=args.augment, wav_augment=args.wav_augment).cuda().train()
@@ -108,6 +112,12 @@ def main():
         dt = (time.perf_counter() - t0) / (args.steps - 3)
         frames = B * (1 + L // 160 + 3) // 4
         print(f"{dt*1e3:.1f} ms/step, {frames/dt:,.0f} encoder frames/s including front-end and CTC head")
+    if args.decode:
+        model.eval()
+        with torch.no_grad():
+            hyps = ctc_greedy_decode(model(wav, wav_lens), wav_lens, blank_id=0)
+        for b, h in enumerate(hyps):
+            print(f"hyp {b:2d} ({len(h):3d} tokens): {' '.join(str(k) for k in h[:24])}{' ...' if len(h) > 24 else ''}")
 
 
 if __name__ == "__main__":

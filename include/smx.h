@@ -875,6 +875,56 @@ int smx_seqloss_bwd(int dtype, int from_logits, const void* X, int64_t ldx, int6
                     const int32_t* len, int B, int U, int V, int pad_idx, float conf, float off, const float* lse, const float* g,
                     void* dX, int64_t lddx, void* stream);
 
+/* ---- CTC greedy (best-path) decoding of the encoder's CTC head --------------------------------------------------------------------
+ * speechbrain.decoders.ctc.ctc_greedy_decode / filter_ctc_output over the head every recipe trains (`ctc_lin` 512 -> 5000 with
+ * `ctc_weight: 0.3` in the Branchformer recipes, `proj_ctc` 640 -> 1000 in the transducer recipes): row arg-max, collapse repeats,
+ * drop blanks.  The decoder's source is not part of the reference tree; the semantics below are complete in themselves.
+ * No call synchronises with the host or allocates (capturable); nothing is atomic and every sum has a fixed order, so two runs agree
+ * bit for bit.  A NaN never wins a comparison, and a token is only ever compared, never used as an index.
+ * smx_ctc_best_path: X (N, V) logits or log-probabilities (F32 or BF16), row n at X + n * ldx.  tok[n] int32 = the lowest index of the
+ *   row maximum (-1 when no entry of the row is a number), lp[n] fp32 = max - logsumexp(row) = -log sum exp(X - max), the maximum's
+ *   log-probability (for log-softmax input the maximum itself, up to rounding); NaN when any entry of the row is a NaN.  One wave per
+ *   row, 16-byte loads for a 16-byte aligned row and element loads otherwise (same bits), an element tail of V % (4 | 8) columns.
+ *   SMX_EINVAL: a NULL pointer, V < 1, ldx < V.
+ * smx_ctc_head_best_path: the same two outputs for z = X W^T + bias, X (N, K) with leading dimension ldx and W (V, K) dense, both in
+ *   `dtype`; bias (V) fp32 or NULL.  z is never stored: a 128 x 128 MFMA tile per workgroup (fp32 accumulation; F32 operands sum each
+ *   32-element stage on its own) leaves per (row, column tile) the tile's max, first arg-max and sum exp(z - max) in the workspace
+ *   (smx_ctc_head_workspace(N, V) bytes, 16-byte aligned), and a second launch folds a row's tiles in ascending order (a tie keeps the
+ *   lower column).  Columns at and beyond V count as -inf; rows beyond N re-read row N - 1 and are never stored.
+ *   Supported (smx_ctc_head_ok; SMX_EUNSUPPORTED otherwise): K a multiple of 64, V >= 2, X / ldx / W 16-byte aligned.
+ * smx_ctc_collapse: one wave per utterance over tok / lp (B, T) (frame (b, t) at [b * ld + t]).  in_len (B) int32: the frames of THIS
+ *   call that count per row, clamped to [0, T]; NULL: all T.  start (B) uint8 or NULL: non-zero resets the row's state before the call.
+ *   State per row, read and written: prev int32 (the last counted frame's token; INT32_MIN before the first frame, which equals no
+ *   token), seen int32 (frames counted so far), n_tok int32 (tokens emitted so far), score fp32.
+ *   Frame t < in_len[b] emits iff tok[t] != blank && tok[t] >= 0 && tok[t] != (t == 0 ? prev : tok[t - 1]): `a a` gives `a`,
+ *   `a blank a` gives `a a`, a -1 emits nothing and a real token after it does.  Emissions go to tokens / frames (B, cap) int32 at
+ *   n_tok[b], n_tok[b] + 1, ... in frame order (frames: seen + t, the index from the start of the stream); one at or beyond cap is
+ *   not stored while n_tok keeps counting (n_tok > cap tells the caller).  Entries [n_tok, cap) are set to -1 by every call; entries
+ *   below the call's first emission are left alone.  score[b] += lp[b, t] for t < in_len[b] as ONE fp32 chain strictly in frame order -
+ *   a fixed tree (the left comb), and the only one for which a stream cut into calls gives the bits of the whole.  in_len[b] == 0
+ *   without `start` leaves the row's state as it was.
+ *   SMX_EINVAL: a NULL pointer, negative sizes, ld < T, blank < 0. */
+typedef struct smx_ctc_collapse_args {
+  const int32_t* tok;     /* (B, T) */
+  const float* lp;        /* (B, T) */
+  int64_t ld;             /* row stride of tok and lp (elements) */
+  const int32_t* in_len;  /* (B) or NULL */
+  const uint8_t* start;   /* (B) or NULL */
+  int32_t* prev;          /* (B) state */
+  int32_t* seen;          /* (B) state */
+  int32_t* n_tok;         /* (B) state */
+  float* score;           /* (B) state */
+  int32_t* tokens;        /* (B, cap) */
+  int32_t* frames;        /* (B, cap) */
+  int32_t B, T, blank, cap;
+} smx_ctc_collapse_args;  /* 104 bytes */
+int smx_ctc_best_path(int dtype, const void* X, int64_t ldx, int N, int V, int32_t* tok, float* lp, void* stream);
+int smx_ctc_head_ok(int dtype, int K, int V);
+size_t smx_ctc_head_workspace(int N, int V);
+int smx_ctc_head_best_path(int dtype, const void* X, int64_t ldx, const void* W, const float* bias, int N, int K, int V, int32_t* tok,
+                           float* lp, void* workspace, void* stream);
+int smx_ctc_collapse(const smx_ctc_collapse_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -111,6 +111,13 @@ class DwconvPlan(ctypes.Structure):
                 for n in ("route", "chunked", "deferrable", "partial_rows", "grid", "seg", "nseg", "pad_")]
 
 
+class CtcCollapse(ctypes.Structure):
+    """smx_ctc_collapse_args of include/smx.h."""
+    _fields_ = [("tok", c_vp), ("lp", c_vp), ("ld", c_i64), ("in_len", c_vp), ("start", c_vp), ("prev", c_vp), ("seen", c_vp),
+                ("n_tok", c_vp), ("score", c_vp), ("tokens", c_vp), ("frames", c_vp)] + [
+                (n, ctypes.c_int32) for n in ("B", "T", "blank", "cap")]
+
+
 # name -> (restype, argtypes); mirrors include/smx.h one to one (tests/test_abi.py checks the export list)
 SIGNATURES = {
     "smx_version": (c_i, []),
@@ -252,6 +259,11 @@ SIGNATURES = {
                               c_vp, c_vp, c_vp, c_vp]),
     "smx_seqloss_bwd": (c_i, [c_i, c_i, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i, c_i, c_i, c_i, c_f, c_f, c_vp, c_vp, c_vp, c_i64,
                               c_vp]),
+    "smx_ctc_best_path": (c_i, [c_i, c_vp, c_i64, c_i, c_i, c_vp, c_vp, c_vp]),
+    "smx_ctc_head_ok": (c_i, [c_i, c_i, c_i]),
+    "smx_ctc_head_workspace": (c_sz, [c_i, c_i]),
+    "smx_ctc_head_best_path": (c_i, [c_i, c_vp, c_i64, c_vp, c_vp, c_i, c_i, c_i, c_vp, c_vp, c_vp, c_vp]),
+    "smx_ctc_collapse": (c_i, [ctypes.POINTER(CtcCollapse), c_vp]),
 }
 
 _lib = None

@@ -1297,6 +1297,66 @@ def greedy_decode(enc, in_len, WihT, bias, Whh, Wproj, Wlin, blin, state, logp, 
     return tokens, frames, n_tok
 
 
+# ---- CTC greedy decoding (csrc/ctcdec.hip).  Everything stays on the device: no call here synchronises with the host.
+def _row_outputs(N, device):
+    return torch.empty((N,), dtype=torch.int32, device=device), torch.empty((N,), dtype=torch.float32, device=device)
+
+
+def ctc_best_path(x2):
+    """x2 (N, V) logits or log-probabilities with unit stride along V -> (tok (N) int32: lowest index of the row maximum, -1 for a
+    row without a number; lp (N) fp32 = max - logsumexp): smx_ctc_best_path."""
+    px, ldx = _mat(x2)
+    N, V = x2.shape
+    tok, lp = _row_outputs(N, x2.device)
+    t = _pb(f"ctc_best_path {'bf16' if _es(x2) == 2 else 'f32'} ({N},{V})", N * V * _es(x2) + 8 * N)
+    L.check(L.lib().smx_ctc_best_path(dt(x2), px, ldx, N, V, _p(tok), _p(lp), _stream()), "smx_ctc_best_path")
+    _pe(t)
+    return tok, lp
+
+
+def ctc_head_ok(dtype, K, V):
+    return dtype in _DT and bool(L.lib().smx_ctc_head_ok(_DT[dtype], K, V))
+
+
+def ctc_head_best_path(x2, W, bias):
+    """The same pair for z = x2 W^T + bias without storing z: x2 (N, K) and W (V, K) in one dtype, bias (V) fp32 or None
+    (smx_ctc_head_best_path; the shapes of smx_ctc_head_ok)."""
+    px, ldx = _mat(x2)
+    N, K = x2.shape
+    V = W.shape[0]
+    assert W.is_cuda and W.dtype == x2.dtype and W.is_contiguous() and W.shape[1] == K
+    assert bias is None or (bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == V)
+    tok, lp = _row_outputs(N, x2.device)
+    ws = _workspace(L.lib().smx_ctc_head_workspace(N, V), x2.device, "ctc_head")
+    t = _pb(f"ctc_head_best_path {'bf16' if _es(x2) == 2 else 'f32'} ({N},{K},{V})", (N * K + V * K) * _es(x2) + 8 * N, 2.0 * N * K * V)
+    L.check(L.lib().smx_ctc_head_best_path(dt(x2), px, ldx, _p(W), _p(bias), N, K, V, _p(tok), _p(lp), _p(ws), _stream()),
+            "smx_ctc_head_best_path")
+    _pe(t)
+    return tok, lp
+
+
+def ctc_collapse(tok, lp, in_len, blank, start, state, tokens, frames):
+    """tok int32 / lp fp32 (B, T) with one row stride; in_len (B) int32 or None; start (B) uint8 or None; state = (prev, seen, n_tok,
+    score), updated IN PLACE; tokens / frames (B, cap) int32, appended to at n_tok (smx_ctc_collapse)."""
+    B, T = tok.shape
+    prev, seen, n_tok, score = state
+    assert tok.is_cuda, NO_CPU
+    assert tok.dtype == torch.int32 and lp.dtype == torch.float32 and lp.shape == tok.shape
+    assert T == 0 or (tok.stride(1) == 1 and lp.stride(1) == 1 and (B == 1 or tok.stride(0) == lp.stride(0)))
+    assert all(t.dtype == torch.int32 and t.is_contiguous() and t.shape == (B,) for t in (prev, seen, n_tok))
+    assert score.dtype == torch.float32 and score.is_contiguous() and score.shape == (B,)
+    assert in_len is None or (in_len.dtype == torch.int32 and in_len.is_contiguous() and in_len.shape == (B,))
+    assert start is None or (start.dtype == torch.uint8 and start.is_contiguous() and start.shape == (B,))
+    assert tokens.dtype == torch.int32 and frames.dtype == torch.int32 and tokens.is_contiguous() and frames.is_contiguous()
+    assert tokens.dim() == 2 and tokens.shape[0] == B and frames.shape == tokens.shape
+    a = L.CtcCollapse(tok=_p(tok), lp=_p(lp), ld=max(tok.stride(0), T) if B > 1 else T, in_len=_p(in_len), start=_p(start), prev=_p(prev),
+                      seen=_p(seen), n_tok=_p(n_tok), score=_p(score), tokens=_p(tokens), frames=_p(frames), B=B, T=T, blank=int(blank),
+                      cap=tokens.shape[1])
+    t = _pb(f"ctc_collapse (B {B}, T {T})", 8 * B * T)
+    L.check(L.lib().smx_ctc_collapse(ctypes.byref(a), _stream()), "smx_ctc_collapse")
+    _pe(t)
+
+
 _CSGU_DROP_FUSE = True   # (round 4: A/B knob SMX_CSGU_DROP_FUSE removed)     # (read once, like the library's own knobs)
 _STEP_COUNTER = None          # the training loop's device step counter (held HERE, in the Python host; libsmx has no such state)
 
