@@ -925,6 +925,71 @@ int smx_ctc_head_best_path(int dtype, const void* X, int64_t ldx, const void* W,
                            float* lp, void* workspace, void* stream);
 int smx_ctc_collapse(const smx_ctc_collapse_args* a, void* stream);
 
+/* ---- scaled-dot-product attention (speechbrain.nnet.attention.MultiheadAttention, `attention_type: regularMHA`) -------------------
+ * The arithmetic between the in- and out-projections of the module the reference's TransformerDecoderLayer holds twice
+ * (speechbrain/lobes/models/transformer/Transformer.py:745-751 builds `self_attn` and `mutihead_attn`, :811-840 runs them: causal
+ * self-attention over the tokens, cross-attention over the encoder output) and TransformerLM is made of.
+ * Q (B, L, H, D), K / V (B, S, H, D), O / dO / dQ (B, L, H, D), dK / dV (B, S, H, D): each an smx_attn_operand, element
+ * (b, row, h, d) at p[b sb + row sr + h sh + d sd].  sd must be 1 and the base and every stride 16-byte aligned (SMX_EUNSUPPORTED
+ * otherwise), so q / k / v may be views into one packed (B, L, 3, H, D) or (B, S, 2, H, D) projection output and dq / dk / dv views
+ * into the packed gradient buffer; nothing is copied.  dtype F32 or BF16, D in {64, 128, 256, 512}, B, L, S, H >= 1 with no
+ * multiple-of-tile requirement (other dtype / D: SMX_EUNSUPPORTED).
+ *   s[b,h,i,j] = scale <q_i, k_j> + attn_bias[i ldbias + j]      attn_bias fp32 (L, S) or NULL, shared by batch and heads, -inf = masked
+ *   masked also where causal != 0 and j > i + (S - L), and where key_pad[b ldpad + j] != 0 (uint8 (B, S) or NULL)
+ *   p = softmax_j(s), fp32, row maximum subtracted;  p~ = keep ? p / (1 - drop_p) : 0 with the library's counter-based mask at index
+ *   ((b H + h) L + i) S + j of (drop_seed, epoch): the mask smx_dropout draws on a (B H L, S) matrix with that seed; off at drop_p == 0
+ *   O = p~ V,  lse[(b H + h) L + i] = log sum_j exp(s) (fp32).
+ * A row whose keys are all masked: O = 0, lse = -inf, zero gradients, never NaN (a stated deviation: torch yields NaN there).
+ * Arithmetic: F32 operands use exact fp32 products (v_mfma_f32_16x16x4_f32), BF16 operands the bf16 MFMA; accumulators, softmax, lse
+ * and delta are fp32; for BF16, p~ and dS are rounded to bf16 once, as the operand of the product that follows them.
+ * smx_attn_fwd: one launch, online softmax over 64-key tiles, writes o and lse; no (B, H, L, S) tensor exists anywhere.
+ * smx_attn_bwd: reads dO, q, k, v, lse, writes dq, dk, dv (every element of every row) and delta (B H L fp32 of workspace).  Two
+ *   launches: dQ by query tile, which first sums delta_i = sum_j p~_ij dP_ij - rowsum(dO o) taken from the dP bits the gradients use,
+ *   so p (dP - delta) cancels exactly for a row with one visible key; o may be passed and is neither read nor checked - then dK / dV
+ *   by key tile.
+ *   Probabilities are recomputed from lse, the keep mask from the seed; no atomics, one fixed summation order: two runs agree bit for
+ *   bit.  dk / dv rows of padded keys are exact zeros.
+ * smx_attn_weights: weights[b w_sb + i ldw + j] = (1 / H) sum_h p~[b,h,i,j] (fp32, heads summed in index order; dropped as the
+ *   forward when drop_p > 0, which is what torch returns); reads q, k, lse and the masks; masked entries are exact zeros.
+ * smx_attn_plan_query: the geometry of the launch `pass` (SMX_ATTN_PASS_*) for the descriptor's
+ *   sizes and dtype; needs no GPU and no pointers (those present are checked).
+ * No call synchronises with the host or allocates: capturable.  SMX_EINVAL: a NULL operand the pass needs, sizes < 1, drop_p
+ * outside [0, 1), ldbias / ldpad / ldw < S. */
+enum { SMX_ATTN_PASS_FWD = 0, SMX_ATTN_PASS_BWD_DQ = 1, SMX_ATTN_PASS_BWD_DKV = 2, SMX_ATTN_PASS_WEIGHTS = 3 };
+typedef struct smx_attn_operand {
+  void* p;
+  int64_t sb, sr, sh, sd; /* element strides: batch, row, head, D (sd must be 1) */
+} smx_attn_operand;       /* 40 bytes */
+typedef struct smx_attn_args {
+  int32_t dtype, causal;
+  smx_attn_operand q, k, v, o, dO, dq, dk, dv;
+  float* lse;              /* (B, H, L) */
+  float* delta;            /* (B, H, L) backward workspace */
+  const float* attn_bias;  /* (L, S) or NULL */
+  int64_t ldbias;
+  const uint8_t* key_pad;  /* (B, S) or NULL */
+  int64_t ldpad;
+  float* weights;          /* (B, L, S), smx_attn_weights only */
+  int64_t w_sb, ldw;
+  int32_t B, L, S, H, D;
+  float scale, drop_p;
+  int32_t pad_;
+  uint64_t drop_seed;
+  const uint64_t* epoch;   /* device step counter mixed into the seed, or NULL */
+} smx_attn_args;           /* 448 bytes */
+typedef struct smx_attn_plan {
+  int32_t rows;            /* rows of the tile a workgroup owns: queries (pass 0, 1, 3) or keys (pass 2) */
+  int32_t key_tile;        /* width of the tile it walks: keys (pass 0, 1, 3) or queries (pass 2) */
+  int32_t d_chunk;         /* columns of D staged through LDS at a time */
+  int32_t lds_bytes, threads, launches;
+  int32_t grid[3];
+  int32_t pad_;
+} smx_attn_plan;           /* 40 bytes */
+int smx_attn_fwd(const smx_attn_args* a, void* stream);
+int smx_attn_bwd(const smx_attn_args* a, void* stream);
+int smx_attn_weights(const smx_attn_args* a, void* stream);
+int smx_attn_plan_query(const smx_attn_args* a, int pass, smx_attn_plan* plan);
+
 #ifdef __cplusplus
 }
 #endif

@@ -118,6 +118,28 @@ class CtcCollapse(ctypes.Structure):
                 (n, ctypes.c_int32) for n in ("B", "T", "blank", "cap")]
 
 
+class AttnOperand(ctypes.Structure):
+    """smx_attn_operand of include/smx.h: base pointer + element strides (batch, row, head, D)."""
+    _fields_ = [("p", c_vp), ("sb", c_i64), ("sr", c_i64), ("sh", c_i64), ("sd", c_i64)]
+
+
+class AttnArgs(ctypes.Structure):
+    """smx_attn_args of include/smx.h."""
+    _fields_ = [("dtype", ctypes.c_int32), ("causal", ctypes.c_int32)] + [
+                (n, AttnOperand) for n in ("q", "k", "v", "o", "dO", "dq", "dk", "dv")] + [
+                ("lse", c_vp), ("delta", c_vp), ("attn_bias", c_vp), ("ldbias", c_i64), ("key_pad", c_vp), ("ldpad", c_i64),
+                ("weights", c_vp), ("w_sb", c_i64), ("ldw", c_i64)] + [(n, ctypes.c_int32) for n in ("B", "L", "S", "H", "D")] + [
+                ("scale", c_f), ("drop_p", c_f), ("pad_", ctypes.c_int32), ("drop_seed", ctypes.c_uint64), ("epoch", c_vp)]
+
+
+class AttnPlan(ctypes.Structure):
+    """smx_attn_plan of include/smx.h (smx_attn_plan_query)."""
+    _fields_ = [(n, ctypes.c_int32 * 3 if n == "grid" else ctypes.c_int32)
+                for n in ("rows", "key_tile", "d_chunk", "lds_bytes", "threads", "launches", "grid", "pad_")]
+
+
+ATTN_FWD, ATTN_BWD_DQ, ATTN_BWD_DKV, ATTN_WEIGHTS = 0, 1, 2, 3      # `pass` of smx_attn_plan_query
+
 # name -> (restype, argtypes); mirrors include/smx.h one to one (tests/test_abi.py checks the export list)
 SIGNATURES = {
     "smx_version": (c_i, []),
@@ -264,6 +286,10 @@ SIGNATURES = {
     "smx_ctc_head_workspace": (c_sz, [c_i, c_i]),
     "smx_ctc_head_best_path": (c_i, [c_i, c_vp, c_i64, c_vp, c_vp, c_i, c_i, c_i, c_vp, c_vp, c_vp, c_vp]),
     "smx_ctc_collapse": (c_i, [ctypes.POINTER(CtcCollapse), c_vp]),
+    "smx_attn_fwd": (c_i, [ctypes.POINTER(AttnArgs), c_vp]),
+    "smx_attn_bwd": (c_i, [ctypes.POINTER(AttnArgs), c_vp]),
+    "smx_attn_weights": (c_i, [ctypes.POINTER(AttnArgs), c_vp]),
+    "smx_attn_plan_query": (c_i, [ctypes.POINTER(AttnArgs), c_i, ctypes.POINTER(AttnPlan)]),
 }
 
 _lib = None

@@ -1571,3 +1571,62 @@ def resample(x, orig_freq, new_freq, out=None):
     elif tuple(out.shape) != (B, Lout) or out.dtype != torch.float32 or out.device != x.device or (Lout > 1 and out.stride(1) != 1):
         raise ValueError(f"resample: out must be a float32 (B, L_out) = ({B}, {Lout}) view with unit inner stride on {x.device}")
     return ops.resample(x, image, out, Lin)
+
+
+# ----------------------------------------------------------------------------------------------------
+# scaled-dot-product attention (csrc/attention.hip): the arithmetic of nnet.attention.MultiheadAttention between its projections
+# ----------------------------------------------------------------------------------------------------
+def attn_bias_of(attn_mask, device):
+    """A 2-D (L, S) attention mask - bool (True = masked) or float (additive) - as the fp32 additive bias the kernels read."""
+    if attn_mask.dim() != 2:
+        raise NotImplementedError(f"attn_mask must be 2-D (L, S); a {attn_mask.dim()}-D (per batch / per head) mask is not supported")
+    if attn_mask.dtype == torch.bool:
+        return torch.zeros(attn_mask.shape, dtype=torch.float32, device=device).masked_fill_(attn_mask.to(device), float("-inf"))
+    if not attn_mask.is_floating_point():
+        raise TypeError(f"attn_mask must be bool or floating point, got {attn_mask.dtype}")
+    return attn_mask.to(device=device, dtype=torch.float32).contiguous()
+
+
+def key_pad_u8(key_padding_mask, B, S, device):
+    """bool (B, S) key padding mask (True = padded key) -> the uint8 view the kernels read."""
+    if key_padding_mask is None:
+        return None
+    if key_padding_mask.dtype != torch.bool or tuple(key_padding_mask.shape) != (B, S):
+        raise ValueError(f"key_padding_mask must be bool ({B}, {S}), got {key_padding_mask.dtype} {tuple(key_padding_mask.shape)}")
+    return key_padding_mask.to(device).contiguous().view(torch.uint8)
+
+
+class _SdpaFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, bias, pad, causal, drop_p, seed, scale):
+        o, lse = ops.attention_fwd(q, k, v, bias, pad, causal, scale, drop_p, seed)
+        ctx.save_for_backward(q, k, v, o, lse)
+        ctx.cfg = (bias, pad, causal, drop_p, seed, scale)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        q, k, v, o, lse = ctx.saved_tensors
+        bias, pad, causal, drop_p, seed, scale = ctx.cfg
+        if do.stride(-1) != 1 or any((s * do.element_size()) % 16 for s in do.stride()[:-1]):
+            do = do.contiguous()
+        dq, dk, dv = ops.attention_bwd(do, q, k, v, o, lse, bias, pad, causal, scale, drop_p, seed)
+        return dq, dk, dv, None, None, None, None, None, None
+
+
+def scaled_dot_product_attention(q, k, v, *, attn_bias=None, key_padding_mask=None, causal=False, dropout_p=0.0, seed=None, scale=None):
+    """softmax(scale q k^T + attn_bias, masked) v on the fused kernels: q (B, L, H, D), k / v (B, S, H, D) views with unit stride
+    along D (views of a packed projection output are read in place) -> (B, L, H, D).  attn_bias: fp32 (L, S) additive, -inf = masked;
+    key_padding_mask: bool (B, S), True = padded; causal: key j visible to query i iff j <= i + (S - L).  Saves O and the fp32
+    log-sum-exp for the backward; the probabilities are recomputed and the dropout mask regenerated from `seed` (a fresh site seed by
+    default; the device step counter is mixed in, so a captured step draws a new mask at every replay).  No host synchronisation.
+    A fully masked row yields zeros and zero gradients, not torch's NaN."""
+    if not (q.is_cuda and k.is_cuda and v.is_cuda):
+        raise RuntimeError(ops.NO_CPU)
+    B, S = k.shape[0], k.shape[1]
+    if attn_bias is not None and (attn_bias.dtype != torch.float32 or not attn_bias.is_cuda):
+        attn_bias = attn_bias_of(attn_bias, q.device)
+    pad = key_pad_u8(key_padding_mask, B, S, q.device)
+    if dropout_p > 0.0 and seed is None:
+        seed = ops.new_dropout_seed()
+    return _SdpaFn.apply(q, k, v, attn_bias, pad, bool(causal), float(dropout_p), seed or 0, scale)

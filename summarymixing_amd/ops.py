@@ -1530,3 +1530,98 @@ def col2im_s2(dcol, B, T, F_, C):
     dx = torch.empty((B, T, F_, C), dtype=dcol.dtype, device=dcol.device)
     L.check(L.lib().smx_col2im_s2(dt(dcol), _p(dcol), _p(dx), B, T, F_, C, dcol.shape[1], _stream()), "smx_col2im_s2")
     return dx
+
+
+# ---- scaled-dot-product attention (csrc/attention.hip).  q (B, L, H, D), k / v (B, S, H, D): 4-D views with unit stride along D and
+# any batch / row / head strides (views of a packed (B, L, 3, H, D) or (B, S, 2, H, D) projection output are not copied).
+def _attn_operand(t, B, R, H, D, what):
+    if t is None:
+        return L.AttnOperand()
+    if not t.is_cuda:
+        raise RuntimeError(NO_CPU)
+    assert t.dim() == 4 and tuple(t.shape) == (B, R, H, D), f"attention: {what} must be ({B}, {R}, {H}, {D}), got {tuple(t.shape)}"
+    sb, sr, sh, sd = t.stride()
+    # (the stride of a size-1 dimension is arbitrary in torch and never multiplied by anything but 0: hand the kernels 0)
+    return L.AttnOperand(t.data_ptr(), sb if B > 1 else 0, sr if R > 1 else 0, sh if H > 1 else 0, sd)
+
+
+def _attn_args(q, k, v, attn_bias, key_pad, causal, scale, drop_p, seed):
+    B, Lq, H, D = q.shape
+    S = k.shape[1]
+    a = L.AttnArgs(dtype=dt(q), causal=int(bool(causal)), B=B, L=Lq, S=S, H=H, D=D, scale=float(scale), drop_p=float(drop_p),
+                   drop_seed=int(seed or 0) & 0xFFFFFFFFFFFFFFFF)
+    assert k.dtype == q.dtype and (v is None or v.dtype == q.dtype), "attention: q, k, v must share a dtype"
+    a.q, a.k, a.v = _attn_operand(q, B, Lq, H, D, "q"), _attn_operand(k, B, S, H, D, "k"), _attn_operand(v, B, S, H, D, "v")
+    if attn_bias is not None:
+        assert attn_bias.is_cuda and attn_bias.dtype == torch.float32 and tuple(attn_bias.shape) == (Lq, S) and (S == 1 or attn_bias.stride(1) == 1)
+        a.attn_bias, a.ldbias = attn_bias.data_ptr(), attn_bias.stride(0) if Lq > 1 else max(attn_bias.stride(0), S)
+    if key_pad is not None:
+        assert key_pad.is_cuda and key_pad.dtype == torch.uint8 and tuple(key_pad.shape) == (B, S) and (S == 1 or key_pad.stride(1) == 1)
+        a.key_pad, a.ldpad = key_pad.data_ptr(), key_pad.stride(0) if B > 1 else max(key_pad.stride(0), S)
+    a.epoch = _epoch() if drop_p > 0.0 else None
+    return a, (B, Lq, S, H, D)
+
+
+def _attn_name(what, q, dims, causal, drop_p):
+    return f"{what} {'bf16' if _es(q) == 2 else 'f32'} (B {dims[0]}, L {dims[1]}, S {dims[2]}, H {dims[3]}, D {dims[4]})" + (
+        " causal" if causal else "") + (f" p={drop_p}" if drop_p > 0.0 else "")
+
+
+def attention_fwd(q, k, v, attn_bias=None, key_pad=None, causal=False, scale=None, drop_p=0.0, seed=0, out=None):
+    """-> (o (B, L, H, D) in q's dtype, lse (B, H, L) fp32): smx_attn_fwd, one launch.  attn_bias fp32 (L, S) additive (-inf = masked),
+    key_pad uint8 (B, S) (non-zero = masked), seed: the dropout site's seed (the device step counter is mixed in when one is set)."""
+    scale = q.shape[-1] ** -0.5 if scale is None else scale
+    a, (B, Lq, S, H, D) = _attn_args(q, k, v, attn_bias, key_pad, causal, scale, drop_p, seed)
+    if out is None:
+        out = torch.empty((B, Lq, H, D), dtype=q.dtype, device=q.device)
+    lse = torch.empty((B, H, Lq), dtype=torch.float32, device=q.device)
+    a.o, a.lse = _attn_operand(out, B, Lq, H, D, "out"), lse.data_ptr()
+    tok = _pb(_attn_name("attn_fwd", q, (B, Lq, S, H, D), causal, drop_p), (2 * B * Lq + 2 * B * S) * H * D * _es(q), 4.0 * B * H * Lq * S * D)
+    L.check(L.lib().smx_attn_fwd(ctypes.byref(a), _stream()), "smx_attn_fwd")
+    _pe(tok)
+    return out, lse
+
+
+def attention_bwd(do, q, k, v, o, lse, attn_bias=None, key_pad=None, causal=False, scale=None, drop_p=0.0, seed=0,
+                  dq=None, dk=None, dv=None):
+    """-> (dq, dk, dv): smx_attn_bwd (two launches, no atomics; `o` is accepted for symmetry with the saved tensors and not read).  dq / dk / dv may be views into a packed gradient buffer; every
+    element of them is written."""
+    scale = q.shape[-1] ** -0.5 if scale is None else scale
+    a, (B, Lq, S, H, D) = _attn_args(q, k, v, attn_bias, key_pad, causal, scale, drop_p, seed)
+    dq = torch.empty((B, Lq, H, D), dtype=q.dtype, device=q.device) if dq is None else dq
+    dk = torch.empty((B, S, H, D), dtype=q.dtype, device=q.device) if dk is None else dk
+    dv = torch.empty((B, S, H, D), dtype=q.dtype, device=q.device) if dv is None else dv
+    assert do.dtype == q.dtype and o.dtype == q.dtype and dq.dtype == q.dtype and dk.dtype == q.dtype and dv.dtype == q.dtype
+    assert lse.dtype == torch.float32 and tuple(lse.shape) == (B, H, Lq) and lse.is_contiguous()
+    delta = torch.empty((B, H, Lq), dtype=torch.float32, device=q.device)
+    a.o, a.dO = _attn_operand(o, B, Lq, H, D, "o"), _attn_operand(do, B, Lq, H, D, "do")
+    a.dq, a.dk, a.dv = _attn_operand(dq, B, Lq, H, D, "dq"), _attn_operand(dk, B, S, H, D, "dk"), _attn_operand(dv, B, S, H, D, "dv")
+    a.lse, a.delta = lse.data_ptr(), delta.data_ptr()
+    tok = _pb(_attn_name("attn_bwd", q, (B, Lq, S, H, D), causal, drop_p), (4 * B * Lq + 4 * B * S) * H * D * _es(q), 16.0 * B * H * Lq * S * D)
+    L.check(L.lib().smx_attn_bwd(ctypes.byref(a), _stream()), "smx_attn_bwd")
+    _pe(tok)
+    return dq, dk, dv
+
+
+def attention_weights(q, k, lse, attn_bias=None, key_pad=None, causal=False, scale=None, drop_p=0.0, seed=0):
+    """-> W (B, L, S) fp32, the head-averaged (dropped, when drop_p > 0) probabilities: smx_attn_weights, a launch of its own."""
+    scale = q.shape[-1] ** -0.5 if scale is None else scale
+    a, (B, Lq, S, H, D) = _attn_args(q, k, None, attn_bias, key_pad, causal, scale, drop_p, seed)
+    assert lse.dtype == torch.float32 and tuple(lse.shape) == (B, H, Lq) and lse.is_contiguous()
+    W = torch.empty((B, Lq, S), dtype=torch.float32, device=q.device)
+    a.lse, a.weights, a.w_sb, a.ldw = lse.data_ptr(), W.data_ptr(), Lq * S, S
+    tok = _pb(_attn_name("attn_weights", q, (B, Lq, S, H, D), causal, drop_p), (B * Lq + B * S) * H * D * _es(q) + 4 * B * Lq * S,
+              2.0 * B * H * Lq * S * D)
+    L.check(L.lib().smx_attn_weights(ctypes.byref(a), _stream()), "smx_attn_weights")
+    _pe(tok)
+    return W
+
+
+def attention_plan(B, Lq, S, H, D, dtype=torch.float32, which=L.ATTN_FWD):
+    """smx_attn_plan_query for a problem size (needs no GPU): a dict of the pass's tile rows, key-tile width, D chunk, LDS bytes,
+    threads, launches and grid.  Raises where the library refuses the problem (head dimension, dtype)."""
+    a = L.AttnArgs(dtype=_DT.get(dtype, -1), B=B, L=Lq, S=S, H=H, D=D, scale=D ** -0.5)
+    plan = L.AttnPlan()
+    L.check(L.lib().smx_attn_plan_query(ctypes.byref(a), int(which), ctypes.byref(plan)), "smx_attn_plan_query")
+    return dict(rows=plan.rows, key_tile=plan.key_tile, d_chunk=plan.d_chunk, lds_bytes=plan.lds_bytes, threads=plan.threads,
+                launches=plan.launches, grid=tuple(plan.grid))
