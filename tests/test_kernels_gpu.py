@@ -423,15 +423,22 @@ def test_gemm_large_ragged_shapes_and_epilogues():
             return (a.float() - r).abs().max().item() / r.abs().max().item()
         y = torch.empty(N, M, device="cuda", dtype=torch.bfloat16)
         z = torch.empty_like(y)
-        ops.gemm(L.GEMM_NT, x, w, y, N, M, K, ops.epilogue(bias=b, act=L.ACT_SWISH, z=z, row_mask=mask))
+        e = ops.epilogue(bias=b, act=L.ACT_SWISH, z=z, row_mask=mask)
+        assert ops.gemm_symbol(L.GEMM_NT, x, w, y, N, M, K, e) == "gemm_kernel<bf16_t, true, true, 128, 128, true, 0, 0>"
+        ops.gemm(L.GEMM_NT, x, w, y, N, M, K, e)
         assert rel(z, zr) < 1e-2 and rel(y, torch.nn.functional.silu(zr) * mask[:, None]) < 1e-2, (N, K, M, "NT")
         wt = w.t().contiguous()
         y32 = torch.empty(N, M, device="cuda", dtype=torch.float32)
-        ops.gemm(L.GEMM_NN, x, wt, y32, N, M, K, ops.epilogue(bias=b, res=res, out_mode=L.OUT_F32))
+        e = ops.epilogue(bias=b, res=res, out_mode=L.OUT_F32)
+        assert ops.gemm_symbol(L.GEMM_NN, x, wt, y32, N, M, K, e) == "gemm_kernel<bf16_t, true, false, 128, 128, true, 0, 0>"
+        ops.gemm(L.GEMM_NN, x, wt, y32, N, M, K, e)
         assert rel(y32, zr + res.float()) < 1e-2, (N, K, M, "NN")
         zz = torch.randn(N, M, device="cuda").bfloat16()
         cs = torch.zeros(M, device="cuda")
-        ops.gemm(L.GEMM_NN, x, wt, y, N, M, K, ops.epilogue(act=L.ACT_SWISH, act_grad_z=zz, colsum=cs))
+        e = ops.epilogue(act=L.ACT_SWISH, act_grad_z=zz, colsum=cs)
+        e.workspace = cs.data_ptr()                        # (the plan query wants one; ops.gemm attaches the real workspace)
+        assert ops.gemm_symbol(L.GEMM_NN, x, wt, y, N, M, K, e) == "gemm_kernel<bf16_t, true, false, 128, 128, true, 0, 0>"
+        ops.gemm(L.GEMM_NN, x, wt, y, N, M, K, e)
         zf = zz.float()
         sg = torch.sigmoid(zf)
         ref = (x.float() @ wt.float()) * (sg * (1 + zf * (1 - sg)))
@@ -463,13 +470,19 @@ def test_gemm_256x256_tile_long_reduction(N):
         return (a.float() - r).abs().max().item() / r.abs().max().item()
     y = torch.empty(N, M, device="cuda", dtype=torch.bfloat16)
     z = torch.empty_like(y)
-    ops.gemm(L.GEMM_NT, x, w, y, N, M, K, ops.epilogue(bias=b, act=L.ACT_SWISH, z=z, row_mask=mask, res=res, alpha=0.5))
+    t256, wide = "gemm_kernel<bf16_t, true, %s, 256, 256, true, 0, 0>", "gemm_kernel<bf16_t, true, %s, 128, 256, true, 0, 0>"
+    e = ops.epilogue(bias=b, act=L.ACT_SWISH, z=z, row_mask=mask, res=res, alpha=0.5)
+    assert ops.gemm_symbol(L.GEMM_NT, x, w, y, N, M, K, e) == wide % "true"
+    ops.gemm(L.GEMM_NT, x, w, y, N, M, K, e)
     assert rel(z, zr) < 1e-2
     assert rel(y, res.float() + 0.5 * torch.nn.functional.silu(zr) * mask[:, None]) < 1e-2
     y32 = torch.empty(N, M, device="cuda", dtype=torch.float32)
+    assert ops.gemm_symbol(L.GEMM_NT, x, w, y32, N, M, K, ops.epilogue(bias=b, out_mode=L.OUT_F32)) == wide % "true"
     ops.gemm(L.GEMM_NT, x, w, y32, N, M, K, ops.epilogue(bias=b, out_mode=L.OUT_F32))
     assert rel(y32, zr) < 1e-2
     # the 256 x 256 tile's NT variant: bias (+ row mask, + dropout), bf16 output, no element-wise side input
+    assert ops.gemm_symbol(L.GEMM_NT, x, w, y, N, M, K, ops.epilogue(bias=b, row_mask=mask)) == t256 % "true"
+    assert ops.gemm_symbol(L.GEMM_NT, x, w, y, N, M, K, ops.epilogue(bias=b, row_mask=mask, drop=(0.25, 4242))) == t256 % "true"
     ops.gemm(L.GEMM_NT, x, w, y, N, M, K, ops.epilogue(bias=b, row_mask=mask))
     assert rel(y, zr * mask[:, None]) < 1e-2
     yd = torch.empty_like(y)
@@ -483,11 +496,15 @@ def test_gemm_256x256_tile_long_reduction(N):
     ops.gemm(L.GEMM_NT, x, w, yd2, N, M, K, ops.epilogue(bias=b, row_mask=mask, drop=(0.25, 4242)))
     assert torch.equal(yd, yd2)                            # ... and a pure function of (seed, element)
     wt = w.t().contiguous()                                # NN: (N, K) x (K, M)
+    assert ops.gemm_symbol(L.GEMM_NN, x, wt, y, N, M, K) == t256 % "false"
     ops.gemm(L.GEMM_NN, x, wt, y, N, M, K)
     assert rel(y, x.float() @ wt.float()) < 1e-2
     zz = torch.randn(N, M, device="cuda").bfloat16()
     cs = torch.zeros(M, device="cuda")
-    ops.gemm(L.GEMM_NN, x, wt, y, N, M, K, ops.epilogue(act=L.ACT_SWISH, act_grad_z=zz, colsum=cs))
+    e = ops.epilogue(act=L.ACT_SWISH, act_grad_z=zz, colsum=cs)
+    e.workspace = cs.data_ptr()                            # (the plan query wants one; ops.gemm attaches the real workspace)
+    assert ops.gemm_symbol(L.GEMM_NN, x, wt, y, N, M, K, e) == wide % "false"
+    ops.gemm(L.GEMM_NN, x, wt, y, N, M, K, e)
     zf = zz.float()
     sg = torch.sigmoid(zf)
     assert rel(y, (x.float() @ wt.float()) * (sg * (1 + zf * (1 - sg)))) < 1e-2
@@ -535,15 +552,20 @@ def test_gemm_register_domain_epilogue(N, K, M):
     zr = x.float() @ w.float().t() + b
     yr = torch.nn.functional.gelu(zr) * mask[:, None] * 0.5
     y1 = torch.empty(N, M, device="cuda", dtype=torch.bfloat16)
+    t128 = "gemm_kernel<bf16_t, true, %s, 128, 128, true, 0, 0>"
+    assert ops.gemm_symbol(L.GEMM_NT, x, w, y1, N, M, K, ops.epilogue(bias=b, act=L.ACT_GELU, row_mask=mask, alpha=0.5)) == t128 % "true"
     ops.gemm(L.GEMM_NT, x, w, y1, N, M, K, ops.epilogue(bias=b, act=L.ACT_GELU, row_mask=mask, alpha=0.5))
     assert rel_err(y1.float(), yr) < 1e-2
     # NN layout (dgrad shaped), bias only, strided output (a column slice of a wider buffer)
     wide = torch.zeros(N, M + 64, device="cuda", dtype=torch.bfloat16)
+    assert ops.gemm_symbol(L.GEMM_NN, x, w.t().contiguous(), wide[:, 64:], N, M, K, ops.epilogue(bias=b)) == t128 % "false"
     ops.gemm(L.GEMM_NN, x, w.t().contiguous(), wide[:, 64:], N, M, K, ops.epilogue(bias=b))
     assert rel_err(wide[:, 64:].float(), zr) < 1e-2 and float(wide[:, :64].abs().max()) == 0.0
     # dropout: register-domain path (no Z) vs fp32-staged path (Z requested) with the same seed
     ya, yb = torch.empty_like(y1), torch.empty_like(y1)
     z = torch.empty_like(y1)
+    assert ops.gemm_symbol(L.GEMM_NT, x, w, ya, N, M, K, ops.epilogue(bias=b, act=L.ACT_SWISH, row_mask=mask, drop=(0.15, 4242))) == t128 % "true"
+    assert ops.gemm_symbol(L.GEMM_NT, x, w, yb, N, M, K, ops.epilogue(bias=b, act=L.ACT_SWISH, row_mask=mask, drop=(0.15, 4242), z=z)) == t128 % "true"
     ops.gemm(L.GEMM_NT, x, w, ya, N, M, K, ops.epilogue(bias=b, act=L.ACT_SWISH, row_mask=mask, drop=(0.15, 4242)))
     ops.gemm(L.GEMM_NT, x, w, yb, N, M, K, ops.epilogue(bias=b, act=L.ACT_SWISH, row_mask=mask, drop=(0.15, 4242), z=z))
     assert torch.equal(ya == 0, yb == 0)
