@@ -990,6 +990,26 @@ int smx_attn_bwd(const smx_attn_args* a, void* stream);
 int smx_attn_weights(const smx_attn_args* a, void* stream);
 int smx_attn_plan_query(const smx_attn_args* a, int pass, smx_attn_plan* plan);
 
+/* ---- target embedding of the seq2seq decoder ----------------------------------------------------------------------------------------
+ * What TransformerASR.forward / decode do to the tokens before the decoder (speechbrain/lobes/models/transformer/): `custom_tgt_module`
+ * = NormalizedEmbedding, emb(tokens) * sqrt(d_model) (Transformer.py:991-1021); `tgt + positional_encoding(tgt)` (TransformerASR.py:430,
+ * :486) and get_key_padding_mask(tgt, pad_idx) = tgt.eq(pad_idx) (Transformer.py:1024-1060, called at TransformerASR.py:172): five
+ * ATen launches forward and an atomic scatter-add backward.
+ * smx_tgt_embed_fwd: for every row r < rows (= B U):  Y[r ldy + c] = table[tok[r] ldt + c] * sqrt(D) + pe[(r %% U) ldpe + c]  in out_dtype
+ *   (F32 or BF16; table (V, D) and pe (rows [0, U) of the positional table, D columns) are fp32) and key_pad[r] = (tok[r] == pad_idx)
+ *   as uint8, the (B, U) layout smx_attn_* read as `key_pad`.  A token outside [0, V) reads as a zero row (smx_gather_rows'
+ *   convention): Y = pe, key_pad = 0; the token is compared before the table is indexed.  One launch, 16-byte loads and stores.
+ * smx_tgt_embed_bwd: gTable[v ldg + c] += sqrt(D) * sum_{r : tok[r] == v} dY[r lddy + c]  (dY in dy_dtype, gTable fp32 (V, D), sums
+ *   fp32), the rows of each v added in ascending r by the one workgroup that owns v: no atomics, two runs agree bit for bit.  Row
+ *   pad_idx receives nothing (upstream's table is nn.Embedding(padding_idx = blank_id = 0)), nor does any token outside [0, V); a row
+ *   no token names is not written.  One launch.
+ * Both: D and the leading dimensions multiples of 8 elements and 16-byte aligned bases (SMX_EUNSUPPORTED otherwise); SMX_EINVAL for a
+ * NULL pointer, rows < 0, U / V / D < 1 or a leading dimension < D.  Nothing synchronises with the host or allocates: capturable. */
+int smx_tgt_embed_fwd(int out_dtype, const int32_t* tok, const float* table, int64_t ldt, const float* pe, int64_t ldpe, void* Y,
+                      int64_t ldy, uint8_t* key_pad, int rows, int U, int V, int D, int pad_idx, void* stream);
+int smx_tgt_embed_bwd(int dy_dtype, const int32_t* tok, const void* dY, int64_t lddy, float* gTable, int64_t ldg, int rows, int V, int D,
+                      int pad_idx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

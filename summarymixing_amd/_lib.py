@@ -290,6 +290,8 @@ SIGNATURES = {
     "smx_attn_bwd": (c_i, [ctypes.POINTER(AttnArgs), c_vp]),
     "smx_attn_weights": (c_i, [ctypes.POINTER(AttnArgs), c_vp]),
     "smx_attn_plan_query": (c_i, [ctypes.POINTER(AttnArgs), c_i, ctypes.POINTER(AttnPlan)]),
+    "smx_tgt_embed_fwd": (c_i, [c_i, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i, c_i, c_i, c_i, c_i, c_vp]),
+    "smx_tgt_embed_bwd": (c_i, [c_i, c_vp, c_vp, c_i64, c_vp, c_i64, c_i, c_i, c_i, c_i, c_vp]),
 }
 
 _lib = None

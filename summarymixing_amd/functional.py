@@ -1260,14 +1260,15 @@ def dwconv_bwd_deferred(dy, p_, wd, bd, gwd, gbd, B, T, D, k, glu, pad_mode, chu
     return dp, dg
 
 
-def ffn_module_fwd(x, P, act, need_bwd, dtype, alpha=0.5, p=0.0, pre_ln=None, ln_next=None, ln_pair=None):
+def ffn_module_fwd(x, P, act, need_bwd, dtype, alpha=0.5, p=0.0, pre_ln=None, ln_next=None, ln_pair=None, eps=1e-5):
     """y = x + alpha * D2(W2 D1(act(W1 LN(x) + b1)) + b2)   (Conformer.py:458-472,507,536; D = dropout, p = 0 in eval).
     With p == 0 the second Linear's epilogue carries the residual and alpha (no extra pass).
     pre_ln = (LN(x), stats) when the producer of x already ran this module's LayerNorm in its epilogue; ln_next = (gamma,
     beta, eps) of the LayerNorm that follows the module: it runs in the second Linear's epilogue where possible, and a
     third value (LN(y), stats) | None is returned.  ln_pair = (gamma2, beta2, eps2): the LayerNorm that follows THAT one (the next
-    layer's first); where the epilogue can run both, a fourth value (LN2(LN(y)), stats2) | None is returned."""
-    h, ln_b = ln_fwd(x, P["ln_w"], P["ln_b"], 1e-5, need_bwd, pre=pre_ln, out_dtype=dtype)
+    layer's first); where the epilogue can run both, a fourth value (LN2(LN(y)), stats2) | None is returned.  eps: of the module's own
+    LayerNorm (the encoders' 1e-5; the Transformer decoder layer's norm3 has 1e-6, Transformer.py:775)."""
+    h, ln_b = ln_fwd(x, P["ln_w"], P["ln_b"], eps, need_bwd, pre=pre_ln, out_dtype=dtype)
     W1, W2 = wcast(P["W1"], dtype), wcast(P["W2"], dtype)
     d1 = (p, ops.new_dropout_seed()) if p > 0.0 else None       # both dropouts are fused into the GEMM epilogues
     d2 = (p, ops.new_dropout_seed()) if p > 0.0 else None

@@ -2,8 +2,15 @@
 
 Mirrors speechbrain/lobes/models/transformer/TransformerASR.py (:50-180 masks, :281-360 ctor, :501-560 encode,
 :687-741 EncoderWrapper) and Transformer.py:284-335 (PositionalEncoding), :201-259 (encoder dispatch) for
-attention_type="SummaryMixing" with encoder_module in {"conformer", "branchformer"}.  The MHA decoder and the
-vanilla-Transformer encoder (broken for SummaryMixing in the reference) are out of scope.
+attention_type="SummaryMixing" with encoder_module in {"conformer", "branchformer"}.  The vanilla-Transformer encoder (broken for
+SummaryMixing in the reference) is out of scope.
+
+Seq2seq side (:362-499, Transformer.py:262-277): with num_decoder_layers > 0 the constructor also builds `decoder` (always regularMHA,
+causal) and `custom_tgt_module` (NormalizedEmbedding); forward(src, tgt, wav_len, pad_idx) -> (encoder_out, decoder_out) and
+decode(tgt, encoder_out, enc_len) -> (prediction, last cross-attention weights).  The tokens become the decoder input in ONE launch
+(smx_tgt_embed_fwd: embedding * sqrt(d) + positional rows + the key-padding mask); the look-ahead mask is the attention kernels'
+causal flag.  Deviation: forward with wav_len=None runs the decoder without a memory padding mask (upstream crashes on
+logical_not(None) there).
 
 Streaming (:562-685,731-741): make_streaming_context / encode_streaming run a Dynamic-Chunk-trained Conformer encoder one chunk at a
 time, from the encoder input on (the front-end is not streamed).  Chunk c gets rows [c C, c C + C_cur) of the positional table, as
@@ -30,6 +37,9 @@ from ....utils.dynamic_chunk_training import DynChunkTrainConfig  # noqa: F401
 from ...models.VanillaNN import Linear
 from .Branchformer import BranchformerEncoder
 from .Conformer import ConformerEncoder, _slot_commit
+from .Transformer import (LOOKAHEAD, NormalizedEmbedding, TransformerDecoder, get_key_padding_mask,  # noqa: F401
+                          get_lookahead_mask)
+from ....nnet.attention import HEAD_DIMS
 
 
 @dataclass
@@ -62,9 +72,9 @@ def make_transformer_src_mask(src, causal=False, masked_false_or_true=True, dync
 
 def make_transformer_src_tgt_masks(src, tgt=None, wav_len=None, pad_idx=0, causal=False, masked_false_or_true=True,
                                    dynchunktrain_config=None):
-    """TransformerASR.py:113-180 (encoder side)."""
-    if tgt is not None:
-        raise NotImplementedError("the MHA decoder is outside the SummaryMixing hot path")
+    """TransformerASR.py:113-180.  With `tgt` (B, U) tokens the two target masks are upstream's tensors: tgt.eq(pad_idx) and the dense
+    (U, U) look-ahead mask (TransformerASR.forward itself builds neither: the embedding launch writes the first, the attention
+    kernels' causal flag stands for the second)."""
     src_key_padding_mask = None
     if wav_len is not None:
         abs_len = torch.round(wav_len * src.shape[1])
@@ -73,6 +83,8 @@ def make_transformer_src_tgt_masks(src, tgt=None, wav_len=None, pad_idx=0, causa
         valid = length_to_mask(abs_len, src.shape[1])
         src_key_padding_mask = ~valid if masked_false_or_true else valid
     src_mask = make_transformer_src_mask(src, causal, masked_false_or_true, dynchunktrain_config)
+    if tgt is not None:
+        return src_key_padding_mask, get_key_padding_mask(tgt, pad_idx=pad_idx), src_mask, get_lookahead_mask(tgt)
     return src_key_padding_mask, None, src_mask, None
 
 
@@ -101,6 +113,14 @@ class _SrcModule(nn.Module):
     def __init__(self, input_size, d_model, dropout):
         super().__init__()
         self.layers = nn.ModuleList([Linear(d_model, input_size), nn.Dropout(dropout)])
+
+
+class _TgtModule(nn.Module):
+    """Key layout of the reference's custom_tgt_module: layers.0 = NormalizedEmbedding (emb.Embedding.weight)."""
+
+    def __init__(self, d_model, vocab):
+        super().__init__()
+        self.layers = nn.ModuleList([NormalizedEmbedding(d_model, vocab)])
 
 
 class TransformerASR(nn.Module):
@@ -148,13 +168,81 @@ class TransformerASR(nn.Module):
         else:
             raise NotImplementedError("encoder_module='transformer' + SummaryMixing is broken in the reference "
                                       "(SURVEY §2 row 8); use 'conformer' or 'branchformer'")
+        if num_decoder_layers > 0:                                            # Transformer.py:262-277: always regularMHA, causal
+            if d_model % nhead != 0 or d_model // nhead not in HEAD_DIMS:
+                raise NotImplementedError(f"TransformerASR: the decoder's head dimension d_model / nhead = {d_model}/{nhead} is not "
+                                          f"supported; the attention kernels take {HEAD_DIMS}")
+            self.decoder = TransformerDecoder(num_layers=num_decoder_layers, nhead=nhead, d_ffn=d_ffn, d_model=d_model,
+                                              dropout=dropout, activation=activation, normalize_before=normalize_before,
+                                              causal=True, attention_type="regularMHA")
         self.custom_src_module = _SrcModule(input_size, d_model, dropout)
+        if num_decoder_layers > 0:
+            self.custom_tgt_module = _TgtModule(d_model, tgt_vocab)           # TransformerASR.py:356-358
         for p in self.parameters():                                           # _init_params, :681-684
             if p.dim() > 1:
                 torch.nn.init.xavier_normal_(p)
 
     def forward(self, src, tgt=None, wav_len=None, pad_idx=0):
-        raise NotImplementedError("the seq2seq decoder is outside the SummaryMixing hot path; call .encode()")
+        """TransformerASR.py:362-451: -> (encoder_out, decoder_out (B, U, d)), or (encoder_out, None) without `tgt`.  src as in
+        encode; tgt (B, U) integer tokens.  The encoder reads its padding mask as True = valid (masked_false_or_true is False for
+        SummaryMixing, :344-347); the decoder gets it inverted as the memory key-padding mask (:437-438), or none with wav_len=None
+        (upstream crashes there).  The attention weights are not computed on this path."""
+        if tgt is not None:
+            self._check_tgt(tgt)
+        encoder_out = self.encode(src, wav_len, pad_idx, masked_false_or_true=self.masked_false_or_true)
+        if tgt is None:
+            return encoder_out, None
+        mem_pad = None
+        if wav_len is not None:
+            S = encoder_out.shape[1]
+            mem_pad = ~length_to_mask(torch.round(wav_len * S), S)
+        return encoder_out, self._decoder_side(tgt, encoder_out, mem_pad, pad_idx)
+
+    def _decoder_side(self, tgt, encoder_out, mem_pad, pad_idx=0):
+        """forward() from the tokens and the encoder output on (:425-450); what tools/decoder_bench.py times."""
+        x, tgt_pad = self._embed_tgt(tgt, pad_idx, F.stream_dtype(encoder_out.dtype) if self.decoder.layers[0].normalize_before
+                                     else encoder_out.dtype)
+        decoder_out, _, _ = self.decoder(tgt=x, memory=encoder_out, memory_mask=None, tgt_mask=LOOKAHEAD,
+                                         tgt_key_padding_mask=tgt_pad, memory_key_padding_mask=mem_pad, _weights="none")
+        return decoder_out
+
+    def _check_tgt(self, tgt):
+        """Host-side refusals, before any launch."""
+        if self.num_decoder_layers <= 0:
+            raise RuntimeError("TransformerASR was built with num_decoder_layers=0: there is no decoder to run `tgt` through")
+        if tgt.dim() != 2 or tgt.is_floating_point():
+            raise ValueError(f"tgt must be (B, U) integer tokens, got {tgt.dtype} {tuple(tgt.shape)}")
+        if self.positional_encoding_type == "fixed_abs_sine" and tgt.shape[1] > self.positional_encoding.max_len:
+            raise ValueError(f"target length {tgt.shape[1]} exceeds max_length {self.positional_encoding.max_len}")
+        if not tgt.is_cuda:
+            raise RuntimeError(ops.NO_CPU)
+
+    def _embed_tgt(self, tgt, pad_idx, out_dtype):
+        """custom_tgt_module + positional_encoding + get_key_padding_mask (:425-430, :172) in one launch."""
+        emb = self.custom_tgt_module.layers[0]
+        U = tgt.shape[1]
+        if self.positional_encoding_type == "fixed_abs_sine":
+            pe = self.positional_encoding.pe[0, :U]
+        else:
+            pe = torch.zeros((U, emb.d_model), device=tgt.device)
+        return emb.embed(tgt, pe, pad_idx, out_dtype)
+
+    @torch.no_grad()
+    def decode(self, tgt, encoder_out, enc_len=None):
+        """TransformerASR.py:453-499: one decoding step over the whole prefix tgt (B, U) -> (prediction (B, U, d), the last layer's
+        cross-attention weights (B, U, S)).  enc_len: the absolute encoder lengths (B).  No key-padding mask on the targets, as
+        upstream; no KV cache."""
+        self._check_tgt(tgt)
+        if not encoder_out.is_cuda:
+            raise RuntimeError(ops.NO_CPU)
+        mem_pad = None
+        if enc_len is not None:
+            mem_pad = ~length_to_mask(enc_len.to(encoder_out.device), encoder_out.shape[1])
+        x, _ = self._embed_tgt(tgt, 0, F.stream_dtype(encoder_out.dtype) if self.decoder.layers[0].normalize_before
+                               else encoder_out.dtype)
+        prediction, _, multihead_attns = self.decoder(x, encoder_out, tgt_mask=LOOKAHEAD, memory_key_padding_mask=mem_pad,
+                                                      _weights="last_cross")
+        return prediction, multihead_attns[-1]
 
     def encode(self, src, wav_len=None, pad_idx=0, dynchunktrain_config=None, masked_false_or_true: Optional[bool] = True):
         """TransformerASR.py:501-560.  masked_false_or_true is honoured exactly like the reference: the SummaryMixing cell

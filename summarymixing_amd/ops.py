@@ -1625,3 +1625,46 @@ def attention_plan(B, Lq, S, H, D, dtype=torch.float32, which=L.ATTN_FWD):
     L.check(L.lib().smx_attn_plan_query(ctypes.byref(a), int(which), ctypes.byref(plan)), "smx_attn_plan_query")
     return dict(rows=plan.rows, key_tile=plan.key_tile, d_chunk=plan.d_chunk, lds_bytes=plan.lds_bytes, threads=plan.threads,
                 launches=plan.launches, grid=tuple(plan.grid))
+
+
+# ---- target embedding of the seq2seq decoder (csrc/tgt_embed.hip).  One launch per direction; neither synchronises with the host.
+def tgt_embed_fwd(tokens, table, pe, pad_idx=0, out_dtype=torch.float32, out=None, key_pad=None):
+    """tokens (B, U) integer, table (V, d) fp32, pe (>= U, d) fp32 (rows [0, U) are read) -> (y (B, U, d) in out_dtype =
+    table[tokens] * sqrt(d) + pe[u], key_pad (B, U) bool = tokens == pad_idx).  A token outside [0, V): y = pe[u], flag False.
+    out / key_pad: destinations to write instead of fresh ones ((B U, d) rows view in out_dtype, (B U) uint8)."""
+    if not (tokens.is_cuda and table.is_cuda and pe.is_cuda):
+        raise RuntimeError(NO_CPU)
+    assert tokens.dim() == 2 and table.dim() == 2 and table.dtype == torch.float32 and pe.dtype == torch.float32
+    B, U = tokens.shape
+    V, D = table.shape
+    assert pe.dim() == 2 and pe.shape[0] >= U and pe.shape[1] == D, f"tgt_embed: pe must hold {U} rows of {D}, got {tuple(pe.shape)}"
+    tk = _tokens_i32(tokens)
+    y = torch.empty((B * U, D), dtype=out_dtype, device=table.device) if out is None else out
+    flags = torch.empty((B * U,), dtype=torch.uint8, device=table.device) if key_pad is None else key_pad
+    assert y.dtype == out_dtype and tuple(y.shape) == (B * U, D) and flags.dtype == torch.uint8 and flags.numel() == B * U and flags.is_contiguous()
+    pt, ldt = _mat(table)
+    pp, ldp = _mat(pe)
+    py, ldy = _mat(y)
+    tok = _pb(f"tgt_embed_fwd {'bf16' if out_dtype == torch.bfloat16 else 'f32'} ({B * U}x{D}, V {V})", B * U * (D * (8 + _es(y)) + 5))
+    L.check(L.lib().smx_tgt_embed_fwd(_DT[out_dtype], _p(tk), pt, ldt, pp, ldp, py, ldy, _p(flags), B * U, U, V, D, int(pad_idx), _stream()),
+            "smx_tgt_embed_fwd")
+    _pe(tok)
+    return y.view(B, U, D), flags.view(B, U).view(torch.bool)
+
+
+def tgt_embed_bwd(tokens, dy, gtable, pad_idx=0):
+    """gtable (V, d) fp32 += sqrt(d) * sum over the rows r with tokens[r] == v of dy[r] (dy (B U, d) or (B, U, d), float32 or
+    bfloat16), rows added in ascending r, no atomics.  Row pad_idx and tokens outside [0, V) receive nothing."""
+    if not (tokens.is_cuda and dy.is_cuda and gtable.is_cuda):
+        raise RuntimeError(NO_CPU)
+    V, D = gtable.shape
+    assert gtable.dtype == torch.float32
+    dy2 = rows2d(dy)
+    tk = _tokens_i32(tokens)
+    assert dy2.shape == (tk.numel(), D), f"tgt_embed_bwd: dy must be ({tk.numel()}, {D}), got {tuple(dy2.shape)}"
+    pd, ldd = _mat(dy2)
+    pg, ldg = _mat(gtable)
+    tok = _pb(f"tgt_embed_bwd {'bf16' if _es(dy2) == 2 else 'f32'} ({tk.numel()}x{D}, V {V})", tk.numel() * (D * (_es(dy2) + 8) + 4))
+    L.check(L.lib().smx_tgt_embed_bwd(dt(dy2), _p(tk), pd, ldd, pg, ldg, tk.numel(), V, D, int(pad_idx), _stream()), "smx_tgt_embed_bwd")
+    _pe(tok)
+    return gtable
