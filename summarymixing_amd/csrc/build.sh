@@ -22,7 +22,11 @@ mkdir -p "$OBJ"
 pids=()
 for f in capi gemm gemm_ln256 gemm_ln256r64 gemm_ln512 gemm_panel gemm_panel_bwd rowwise layernorm slab_epilogue dwconv frontend ctc transducer lstm lstm_step greedy reduce wgrad_group stream augment resample seqloss ctcdec attention tgt_embed; do
   src="${HERE}/${f}.hip"; obj="${OBJ}/${f}.o"
-  if [[ ! -f "$obj" || "$src" -nt "$obj" || "${HERE}/smx_common.h" -nt "$obj" || "${HERE}/gemm_common.h" -nt "$obj" || "${HERE}/gemm_kernel.h" -nt "$obj" || "${HERE}/gemm_panel.h" -nt "$obj" || "${HERE}/dwconv_roll.h" -nt "$obj" || "${HERE}/lstm_tile.h" -nt "$obj" || "${HERE}/build.sh" -nt "$obj" || "${HERE}/../../include/smx.h" -nt "$obj" ]]; then
+  stale=0
+  for dep in "$src" "${HERE}"/*.h "${HERE}/build.sh" "${HERE}/../../include/smx.h"; do
+    if [[ ! -f "$obj" || "$dep" -nt "$obj" ]]; then stale=1; break; fi
+  done
+  if [[ "$stale" == "1" ]]; then
     extra=()
     "$HIPCC" "${FLAGS[@]}" "${extra[@]}" -c "$src" -o "$obj" &
     pids+=($!)

@@ -9,8 +9,6 @@
 
 namespace smx {
 
-static constexpr float NEG_INF = -__builtin_inff();
-
 __device__ __forceinline__ float lse3(float a, float b, float c) {
   const float m = fmaxf(a, fmaxf(b, c));
   if (m == NEG_INF) return NEG_INF;
@@ -25,13 +23,8 @@ __global__ __launch_bounds__(256) void log_softmax_fwd_kernel(const T* __restric
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= N_) return;
   const T* x = X + (long)row * ldx;
-  float m = NEG_INF;
-  for (int c = lane; c < V; c += 64) m = fmaxf(m, to_f32(x[c]));
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
-  float s = 0.f;
-  for (int c = lane; c < V; c += 64) s += expf(to_f32(x[c]) - m);
-  s = wave_sum(s);
+  float m, s;
+  row_max_sumexp(x, V, lane, m, s);
   // x - (m + log s) with the sum and the difference in fp64, rounded once.  In fp32 the sum m + log s rounds at eps |m|, which is
   // all that is left of an entry near the maximum (|y| << |m|) once the logits are large.  Writing (x - m) - log s in fp32 does
   // not help: the library is built with -ffast-math and the compiler reassociates it back to x - (m + log s), hoisting the sum
@@ -243,8 +236,7 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const T* __restrict__ LP,
   for (int v = threadIdx.x; v < V; v += 256) acc[v] = 0.f;
   float m = NEG_INF;
   for (int s = threadIdx.x; s < L; s += 256) m = fmaxf(m, oc[s]);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+  m = wave_max(m);
   if ((threadIdx.x & 63) == 0) redm[threadIdx.x >> 6] = m;
   __syncthreads();
   m = fmaxf(fmaxf(redm[0], redm[1]), fmaxf(redm[2], redm[3]));

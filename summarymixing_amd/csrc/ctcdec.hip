@@ -3,9 +3,9 @@
 // filter_ctc_output), gfx950 only: row arg-max, collapse repeats, drop blanks.  Three pieces, all on the caller's stream, none of
 // which talks to the host:
 //   a. ctc_best_path_kernel   stored scores -> per row (lowest index of the maximum, max - logsumexp).  One wave per row, 16-byte
-//                             groups anchored at column 0 plus an element tail, an online (max, sum exp) pair per lane: the row
-//                             geometry of seqloss.hip.
-//   b. ctc_head_kernel        z = X W^T + bias on the 128 x 128 MFMA tile of transducer.hip's tj_stats_kernel; the epilogue keeps,
+//                             groups anchored at column 0 plus an element tail (row_scan.h), an online (max, sum exp) pair per
+//                             lane.
+//   b. ctc_head_kernel        z = X W^T + bias on the 128 x 128 MFMA tile of head_tile.h; the epilogue keeps,
 //                             per (row, column tile), the tile's max, its first arg-max and sum exp(z - max) - the partial layout of
 //                             greedy.hip.  z is never stored.  ctc_head_reduce_kernel folds a row's tiles in ascending order.
 //   c. ctc_collapse_kernel    one wave per utterance: frame t emits iff its token is neither the blank, nor negative, nor the
@@ -13,39 +13,14 @@
 //                             (previous token, frames seen, tokens emitted, score) is carried between calls.
 // A NaN never wins a comparison; a token is only ever a value, never an index.  Every sum has a fixed order and nothing is atomic:
 // two runs agree bit for bit.
-#include "gemm_common.h"
+#include "head_tile.h"
+#include "row_scan.h"
 
 #include <limits.h>
 
 namespace smx {
 
-static constexpr float CD_NEG_INF = -__builtin_inff();
-static constexpr int CD_TILE = 128;                     // rows and columns of a fused-head tile
 static constexpr int CD_NO_TOKEN = INT_MIN;             // `prev` before the first frame: equals no token (not even the -1 of a NaN row)
-static constexpr int CD_DEPTH = 4;                      // 16-byte groups a lane has in flight (row pass)
-
-// (value, column) meets (value, column): the higher value, the lower column among equals; a NaN on either side never wins
-__device__ __forceinline__ void cd_take(float& m, int& k, float om, int ok) {
-  if (om > m || (om == m && ok < k)) { m = om; k = ok; }
-}
-// sum exp(. - a) and sum exp(. - b) -> sum exp(. - max(a, b)); an empty side (max -inf) contributes nothing
-__device__ __forceinline__ float cd_rescale(float s, float m, float M) { return m == CD_NEG_INF ? 0.f : s * expf(m - M); }
-
-template <typename T> struct CdGrp;                     // 16 bytes of a row as floats
-template <> struct CdGrp<float> {
-  static constexpr int N = 4;
-  static __device__ __forceinline__ void load(const float* p, float (&f)[4]) { load4<float>(p, f); }
-};
-template <> struct CdGrp<bf16_t> {
-  static constexpr int N = 8;
-  static __device__ __forceinline__ void load(const bf16_t* p, float (&f)[8]) {
-    const uint4 r = *reinterpret_cast<const uint4*>(p);
-    f[0] = bf16_bits_to_f32(r.x & 0xffffu); f[1] = bf16_bits_to_f32(r.x >> 16);
-    f[2] = bf16_bits_to_f32(r.y & 0xffffu); f[3] = bf16_bits_to_f32(r.y >> 16);
-    f[4] = bf16_bits_to_f32(r.z & 0xffffu); f[5] = bf16_bits_to_f32(r.z >> 16);
-    f[6] = bf16_bits_to_f32(r.w & 0xffffu); f[7] = bf16_bits_to_f32(r.w >> 16);
-  }
-};
 
 // what one lane has seen of its row: the running arg-max (bv, bi), the online softmax pair (m, s) over the entries that are
 // numbers, and whether any entry was a NaN
@@ -57,25 +32,28 @@ struct CdRow {
 
 template <int N>
 __device__ __forceinline__ void cd_row_take(CdRow& a, const float (&x)[N], int c0) {
-  float gm = CD_NEG_INF;
+  float gm = NEG_INF;
 #pragma unroll
   for (int j = 0; j < N; ++j) {
-    cd_take(a.bv, a.bi, x[j], c0 + j);
+    argmax_take(a.bv, a.bi, x[j], c0 + j);
     if (x[j] > gm) gm = x[j];
     a.nan |= __builtin_isnan(x[j]) ? 1 : 0;
   }
   if (gm > a.m) {                                       // one rescale per group; a.s is 0 while a.m is -inf
-    a.s = cd_rescale(a.s, a.m, gm);
+    a.s = lse_rescale(a.s, a.m, gm);
     a.m = gm;
   }
-  if (a.m != CD_NEG_INF) {
+  if (a.m != NEG_INF) {
+    // -ffast-math lets the compiler pick the tree of this sum.  The order below (a.s first, then the columns in turn) is the one the
+    // kernel had before it moved onto row_scan; it was pinned against those bits (tests/test_head_bits_gpu.py), and the pragma holds
+    // the compiler to it.  seqloss.hip's row_take has no pragma on purpose: its pinned bits are those of the compiler's own tree.
+#pragma clang fp reassociate(off)
 #pragma unroll
     for (int j = 0; j < N; ++j) a.s += __builtin_isnan(x[j]) ? 0.f : expf(x[j] - a.m);
   }
 }
 
-// grid = ceil(N / 4), block = 256: wave w of a block owns row 4 blockIdx.x + w.  A row whose address is 16-byte aligned loads a group
-// at once, any other row loads the same group element by element: the lanes see the same values in the same order (same bits).
+// grid = ceil(N / 4), block = 256: wave w of a block owns row 4 blockIdx.x + w and reads it once (row_scan).
 template <typename T>
 __global__ __launch_bounds__(256) void ctc_best_path_kernel(const T* __restrict__ X, long ldx, int N, int V, int32_t* __restrict__ tok,
                                                             float* __restrict__ lp) {
@@ -83,220 +61,67 @@ __global__ __launch_bounds__(256) void ctc_best_path_kernel(const T* __restrict_
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= N) return;
   const T* x = X + row * ldx;
-  constexpr int G = CdGrp<T>::N;
-  CdRow a = {CD_NEG_INF, INT_MAX, CD_NEG_INF, 0.f, 0};
-  const int Vv = V - V % G;
-  const bool vec = (reinterpret_cast<uintptr_t>(x) & 15u) == 0;
-  for (int c0 = lane * G; c0 < Vv; c0 += 64 * G * CD_DEPTH) {
-    float f[CD_DEPTH][G];
-#pragma unroll
-    for (int d = 0; d < CD_DEPTH; ++d) {
-      const int c = c0 + d * 64 * G;
-      if (c < Vv) {
-        if (vec) CdGrp<T>::load(x + c, f[d]);
-        else {
-#pragma unroll
-          for (int j = 0; j < G; ++j) f[d][j] = to_f32(x[c + j]);
-        }
-      }
-    }
-#pragma unroll
-    for (int d = 0; d < CD_DEPTH; ++d) {
-      const int c = c0 + d * 64 * G;
-      if (c < Vv) cd_row_take<G>(a, f[d], c);
-    }
-  }
-  for (int c = Vv + lane; c < V; c += 64) {             // the tail: fewer than G columns
-    const float f[1] = {to_f32(x[c])};
-    cd_row_take<1>(a, f, c);
-  }
+  CdRow a = {NEG_INF, INT_MAX, NEG_INF, 0.f, 0};
+  row_scan(x, V, lane, [&](const auto& g, int c0) { cd_row_take(a, g, c0); });
   // across the wave (butterflies: every lane ends with the same bits)
-  float bv = a.bv, m = a.m;
+  float bv = a.bv;
   int bi = a.bi, nan = a.nan;
+  argmax_meet<64>(bv, bi);
+  const float m = wave_max(a.m);
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    cd_take(bv, bi, __shfl_xor(bv, o, 64), __shfl_xor(bi, o, 64));
-    m = fmaxf(m, __shfl_xor(m, o, 64));
-    nan |= __shfl_xor(nan, o, 64);
-  }
-  const float s = wave_sum(cd_rescale(a.s, a.m, m));
+  for (int o = 32; o > 0; o >>= 1) nan |= __shfl_xor(nan, o, 64);
+  const float s = wave_sum(lse_rescale(a.s, a.m, m));
   if (lane != 0) return;
   tok[row] = bi == INT_MAX ? -1 : bi;                   // (no entry is a number: every comparison failed)
   lp[row] = nan ? __builtin_nanf("") : -logf(s);        // max - logsumexp = -log sum exp(z - max)
 }
 
-// ---- fused head: the tile and the K loop of transducer.hip's tj_mainloop (4 waves, 2 x 2 of 64 x 64, 32 x 32 MFMA fragments, MFMA
-// operand a = W (columns v), b = X (rows n): lane l holds row n = l % 32 of each fragment, accumulator register r column
-// v = 8 (r / 4) + 4 (l / 32) + r % 4) with a leading dimension for X and CLAMPED instead of zero-filled edges: rows >= N re-read row
-// N - 1 and columns >= V re-read column V - 1; neither is ever stored (the epilogue sets the columns to -inf).
-typedef __attribute__((ext_vector_type(4))) uint32_t cd_u32x4;
-template <typename T> struct CdTraits;
-template <> struct CdTraits<bf16_t> { static constexpr int BK = 64, PAD = 8; };
-template <> struct CdTraits<float> { static constexpr int BK = 32, PAD = 4; };
-template <typename T>
-struct CdTile {
-  static constexpr int BK = CdTraits<T>::BK, LDK = BK + CdTraits<T>::PAD;      // LDS row stride (elements; 16-byte multiple)
-  static constexpr int CPR = BK * (int)sizeof(T) / 16;                          // 16-byte chunks per operand row and stage
-  static constexpr int NLD = CD_TILE * CPR / 256;                               // chunks per thread and operand
-  static constexpr int OP_BYTES = CD_TILE * LDK * (int)sizeof(T);
-};
-
-template <typename T>
-__device__ __forceinline__ void cd_mainloop(const T* __restrict__ X, long ldx, const T* __restrict__ W, int N, int V, int K, int n0,
-                                            int v0, char* smem, f32x16 (&acc)[2][2]) {
-  using TT = CdTile<T>;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wv = wave & 1, wn = wave >> 1, l31 = lane & 31, hi = lane >> 5;
-  char* Xs = smem;
-  char* Ws = smem + TT::OP_BYTES;
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-  cd_u32x4 rx[TT::NLD], rw[TT::NLD];               // (a first-class vector: the loads below are values, not struct copies)
-  auto load = [&](int k0) __attribute__((always_inline)) {
-#pragma unroll
-    for (int p = 0; p < TT::NLD; ++p) {
-      const int idx = t + 256 * p, r = idx / TT::CPR, c = idx % TT::CPR;
-      const int n = min(n0 + r, N - 1), v = min(v0 + r, V - 1);
-      rx[p] = *reinterpret_cast<const cd_u32x4*>(reinterpret_cast<const char*>(X + (long)n * ldx + k0) + c * 16);
-      rw[p] = *reinterpret_cast<const cd_u32x4*>(reinterpret_cast<const char*>(W + (long)v * K + k0) + c * 16);
-    }
-  };
-  const int nk = K / TT::BK;
-  load(0);
-  for (int kt = 0; kt < nk; ++kt) {
-    __syncthreads();                                     // the previous stage has been read
-#pragma unroll
-    for (int p = 0; p < TT::NLD; ++p) {
-      const int idx = t + 256 * p, r = idx / TT::CPR, c = idx % TT::CPR;
-      *reinterpret_cast<cd_u32x4*>(Xs + r * TT::LDK * (int)sizeof(T) + c * 16) = rx[p];
-      *reinterpret_cast<cd_u32x4*>(Ws + r * TT::LDK * (int)sizeof(T) + c * 16) = rw[p];
-    }
-    __syncthreads();
-    if (kt + 1 < nk) load((kt + 1) * TT::BK);
-    if constexpr (sizeof(T) == 2) {
-#pragma unroll
-      for (int kk = 0; kk < TT::BK / 16; ++kk) {
-        bf16x8 fa[2], fb[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-          fa[i] = *reinterpret_cast<const bf16x8*>(Ws + ((wv * 64 + i * 32 + l31) * TT::LDK + kk * 16 + hi * 8) * 2);
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          fb[j] = *reinterpret_cast<const bf16x8*>(Xs + ((wn * 64 + j * 32 + l31) * TT::LDK + kk * 16 + hi * 8) * 2);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
-      }
-    } else {
-      // fp32 operands: each stage is summed on its own and then added to the running sum (two levels of rounding, as tj_mainloop)
-      const float* Wf = reinterpret_cast<const float*>(Ws);
-      const float* Xf = reinterpret_cast<const float*>(Xs);
-      f32x16 st[2][2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int e = 0; e < 16; ++e) st[i][j][e] = 0.f;
-#pragma unroll
-      for (int kk = 0; kk < TT::BK / 2; ++kk) {
-        float fa[2], fb[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) fa[i] = Wf[(wv * 64 + i * 32 + l31) * TT::LDK + kk * 2 + hi];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) fb[j] = Xf[(wn * 64 + j * 32 + l31) * TT::LDK + kk * 2 + hi];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) st[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i], fb[j], st[i][j], 0, 0, 0);
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] += st[i][j];
-    }
-  }
-}
-
+// ---- fused head (head_tile.h).  Columns beyond V re-read column V - 1 in the main loop; the epilogue sets them to -inf. ----
 // part[n][ct] = (max, first arg-max, sum exp(z - max)) of row n over the valid columns of column tile ct.  A thread walks its 32
 // columns of a row in ascending order, then the two lane halves and the two waves that share the row meet in a fixed order.
 template <typename T>
 __global__ __launch_bounds__(256, 2) void ctc_head_kernel(const T* __restrict__ X, long ldx, const T* __restrict__ W,
                                                           const float* __restrict__ bias, int N, int K, int V, int nct,
                                                           float* __restrict__ pmax, int* __restrict__ parg, float* __restrict__ psum) {
-  __shared__ __attribute__((aligned(16))) char smem[2 * CdTile<T>::OP_BYTES];
-  __shared__ float sbias[CD_TILE];
-  __shared__ float red_m[CD_TILE], red_s[CD_TILE];
-  __shared__ int red_k[CD_TILE];
+  __shared__ __attribute__((aligned(16))) char smem[2 * HeadTile<T>::OP_BYTES];
+  __shared__ float sbias[HEAD_TILE];
+  __shared__ ArgLseStat red[HEAD_TILE];
   const int ct = blockIdx.x % nct, rt = blockIdx.x / nct;
-  const int n0 = rt * CD_TILE, v0 = ct * CD_TILE;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wv = wave & 1, wn = wave >> 1, l31 = lane & 31, hi = lane >> 5;
-  if (t < CD_TILE) sbias[t] = (bias && v0 + t < V) ? bias[v0 + t] : 0.f;
+  const int n0 = rt * HEAD_TILE, v0 = ct * HEAD_TILE;
+  const int t = threadIdx.x, wv = (t >> 6) & 1, hi = (t >> 5) & 1;
+  if (t < HEAD_TILE) sbias[t] = (bias && v0 + t < V) ? bias[v0 + t] : 0.f;
   f32x16 acc[2][2];
-  cd_mainloop<T>(X, ldx, W, N, V, K, n0, v0, smem, acc);      // (its barriers publish sbias)
-  float m[2], s[2];
-  int k[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    float mx = CD_NEG_INF;
+  head_mainloop<T>(X, ldx, W, N, V, K, n0, v0, smem, acc);    // (its barriers publish sbias)
+  auto thread_stat = [&](int j) __attribute__((always_inline)) -> ArgLseStat {
+    float mx = NEG_INF;
     int kx = INT_MAX;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int vl = wv * 64 + i * 32 + 8 * (r >> 2) + 4 * hi + (r & 3), v = v0 + vl;
-        const float z = v < V ? acc[i][j][r] + sbias[vl] : CD_NEG_INF;          // columns beyond V: -inf, not the clamped column's value
+        const int vl = head_col(wv, i, r, hi), v = v0 + vl;
+        const float z = v < V ? acc[i][j][r] + sbias[vl] : NEG_INF;             // columns beyond V: -inf, not the clamped column's value
         acc[i][j][r] = z;
-        if (v < V) cd_take(mx, kx, z, v);
+        if (v < V) argmax_take(mx, kx, z, v);
       }
     float sm = 0.f;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int v = v0 + wv * 64 + i * 32 + 8 * (r >> 2) + 4 * hi + (r & 3);
         const float z = acc[i][j][r];
-        if (v < V) sm += __builtin_isnan(z) ? z : (mx == CD_NEG_INF ? 0.f : expf(z - mx));   // a NaN logit makes the row's lp a NaN
+        if (v0 + head_col(wv, i, r, hi) < V) sm += __builtin_isnan(z) ? z : (mx == NEG_INF ? 0.f : expf(z - mx));   // a NaN logit makes the row's lp a NaN
       }
-    // the other lane half (same row, the other 4-column groups): fixed pairing, both halves end with the same bits
-    const float mo = __shfl_xor(mx, 32, 64), so = __shfl_xor(sm, 32, 64);
-    const int ko = __shfl_xor(kx, 32, 64);
-    float M = mx;
-    int Kk = kx;
-    cd_take(M, Kk, mo, ko);
-    const float a = hi ? mo : mx, sa = hi ? so : sm, bq = hi ? mx : mo, sb = hi ? sm : so;   // (lower half first)
-    m[j] = M; k[j] = Kk;
-    s[j] = (__builtin_isnan(sa) || __builtin_isnan(sb)) ? __builtin_nanf("") : cd_rescale(sa, a, M) + cd_rescale(sb, bq, M);
-  }
-  // the two waves of a row pair: wave wv = 1 parks its result, wave wv = 0 folds it in (column order) and writes
-  if (wv == 1 && hi == 0) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int nl = wn * 64 + j * 32 + l31;
-      red_m[nl] = m[j]; red_k[nl] = k[j]; red_s[nl] = s[j];
-    }
-  }
-  __syncthreads();
-  if (wv == 0 && hi == 0) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int nl = wn * 64 + j * 32 + l31, n = n0 + nl;
-      if (n < N) {
-        const float om = red_m[nl], os = red_s[nl];
-        float M = m[j];
-        int Kk = k[j];
-        cd_take(M, Kk, om, red_k[nl]);
-        const long o = (long)n * nct + ct;
-        pmax[o] = M;
-        parg[o] = Kk;
-        psum[o] = (__builtin_isnan(s[j]) || __builtin_isnan(os)) ? __builtin_nanf("") : cd_rescale(s[j], m[j], M) + cd_rescale(os, om, M);
-      }
-    }
-  }
+    return {mx, kx, sm};
+  };
+  head_row_meet(red, thread_stat, [&](int nl, const ArgLseStat& r) {
+    const int n = n0 + nl;
+    if (n >= N) return;
+    const long o = (long)n * nct + ct;
+    pmax[o] = r.m;
+    parg[o] = r.k;
+    psum[o] = r.s;
+  });
 }
 
 // one thread per row: the tiles in ascending order (a tie keeps the lower column)
@@ -306,15 +131,15 @@ __global__ __launch_bounds__(256) void ctc_head_reduce_kernel(const float* __res
   const int n = blockIdx.x * 256 + threadIdx.x;
   if (n >= N) return;
   const long o = (long)n * nct;
-  float M = CD_NEG_INF;
+  float M = NEG_INF;
   int k = INT_MAX;
-  for (int c = 0; c < nct; ++c) cd_take(M, k, pmax[o + c], parg[o + c]);
+  for (int c = 0; c < nct; ++c) argmax_take(M, k, pmax[o + c], parg[o + c]);
   float S = 0.f;
   int nan = 0;
   for (int c = 0; c < nct; ++c) {
     const float ps = psum[o + c];
     nan |= __builtin_isnan(ps) ? 1 : 0;
-    S += __builtin_isnan(ps) ? 0.f : cd_rescale(ps, pmax[o + c], M);
+    S += __builtin_isnan(ps) ? 0.f : lse_rescale(ps, pmax[o + c], M);
   }
   tok[n] = (k >= 0 && k < V) ? k : -1;
   lp[n] = nan ? __builtin_nanf("") : -logf(S);
@@ -367,7 +192,7 @@ __global__ __launch_bounds__(64) void ctc_collapse_kernel(smx_ctc_collapse_args 
   }
 }
 
-static int cd_tiles(int V) { return (V + CD_TILE - 1) / CD_TILE; }
+static int cd_tiles(int V) { return (V + HEAD_TILE - 1) / HEAD_TILE; }
 static bool cd_head_shape_ok(int K, int V) { return K >= 64 && K % 64 == 0 && V >= 2; }
 
 }  // namespace smx
@@ -408,7 +233,7 @@ extern "C" int smx_ctc_head_best_path(int dtype, const void* X, int64_t ldx, con
   if (!aligned16(X) || !aligned16(W) || !aligned16(workspace) || (ldx * es) % 16 != 0)
     return fail(SMX_EUNSUPPORTED, "smx_ctc_head_best_path: X (and its leading dimension), W and the workspace must be 16-byte aligned");
   const int nct = cd_tiles(V);
-  const long nrt = ((long)N + CD_TILE - 1) / CD_TILE;
+  const long nrt = ((long)N + HEAD_TILE - 1) / HEAD_TILE;
   if ((long)N * nct >= (1L << 31) || nrt * nct >= (1L << 31))
     return fail(SMX_EUNSUPPORTED, "smx_ctc_head_best_path: N = %d rows x %d column tiles is too many", N, nct);
   if (N == 0) return SMX_OK;

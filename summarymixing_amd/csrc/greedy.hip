@@ -32,16 +32,6 @@ template <typename T> struct GreedyPad;           // a's LDS rows are 16 bytes l
 template <> struct GreedyPad<float> { static constexpr int value = 4; };
 template <> struct GreedyPad<bf16_t> { static constexpr int value = 8; };
 
-// the (value, column) pairs of 16 neighbouring lanes meet: a higher value wins, the lower column on a tie; all 16 end with the winner
-__device__ __forceinline__ void argmax_meet16(float& m, int& k) {
-#pragma unroll
-  for (int off = 8; off > 0; off >>= 1) {
-    const float om = __shfl_xor(m, off, 16);
-    const int ok = __shfl_xor(k, off, 16);
-    if (om > m || (om == m && ok < k)) { m = om; k = ok; }
-  }
-}
-
 struct GreedyLogits {
   const void* enc; long ld_b, ld_t;     // enc[b,t,:] = enc + b ld_b + t ld_t
   const void* pdec;                     // (B, J)
@@ -82,7 +72,7 @@ __global__ __launch_bounds__(256) void greedy_logits_kernel(GreedyLogits s) {
     const lstm_f32x4 acc = tile_dot(a + r * lda, b_row, J, q);
     const float bias = (s.blin && v < s.V) ? s.blin[v] : 0.f;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) zt[q * 4 + i][c0 + r] = v < s.V ? acc[i] + bias : -INFINITY;
+    for (int i = 0; i < 4; ++i) zt[q * 4 + i][c0 + r] = v < s.V ? acc[i] + bias : NEG_INF;
   }
   __syncthreads();
   // 16 threads per row, 8 consecutive columns each, then the 16 meet
@@ -94,7 +84,7 @@ __global__ __launch_bounds__(256) void greedy_logits_kernel(GreedyLogits s) {
     const float z = zt[bb][jj * 8 + i];
     if (z > m) { m = z; k = jj * 8 + i; }
   }
-  argmax_meet16(m, k);
+  argmax_meet<16>(m, k);
   float sum = 0.f;
 #pragma unroll
   for (int i = 0; i < 8; ++i) sum += __expf(zt[bb][jj * 8 + i] - m);
@@ -134,13 +124,13 @@ __global__ __launch_bounds__(256) void greedy_step_kernel(GreedyStep s) {
   } else {
     // select: the NT partials of row b, 16 threads per row in ascending tiles, then the 16 meet
     const long o = (long)min(b, s.B - 1) * s.NT;
-    float m = -INFINITY;
+    float m = NEG_INF;
     int k = INT_MAX;
     for (int t = jj; t < s.NT; t += 16) {
       const float om = s.pmax[o + t];
       if (t == jj || om > m) { m = om; k = s.parg[o + t]; }                  // (tiles ascend: a tie keeps the lower column)
     }
-    argmax_meet16(m, k);
+    argmax_meet<16>(m, k);
     float sum = 0.f;
     for (int t = jj; t < s.NT; t += 16) sum += s.psum[o + t] * __expf(s.pmax[o + t] - m);
 #pragma unroll

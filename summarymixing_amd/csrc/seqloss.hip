@@ -8,39 +8,11 @@
 // the logits and the argmax: lse = m + log s, lp[v] = z[v] - lse, sum lp = sum z - V lse; no log-probability is stored.  A second,
 // tiny launch (one wave per utterance) folds the rows of an utterance in a fixed order: no float atomics, two runs agree bit for
 // bit.  Backward: one wave per row, one read (logits form) and one write; dropped rows are written as zeros and never read.
-#include "smx_common.h"
+#include "row_scan.h"
 
 namespace smx {
 
-static constexpr float SL_NEG_INF = -__builtin_inff();
 enum { SL_KEEP = 1, SL_HIT = 2 };
-static constexpr int SL_DEPTH = 4;                      // 16-byte groups a lane has in flight
-
-// 16 bytes of a row <-> floats: 4 fp32 or 8 bf16
-template <typename T>
-struct Grp16;
-template <>
-struct Grp16<float> {
-  static constexpr int N = 4;
-  static __device__ __forceinline__ void load(const float* p, float (&f)[4]) { load4<float>(p, f); }
-  static __device__ __forceinline__ void store(float* p, const float (&f)[4]) { store4<float>(p, f); }
-};
-template <>
-struct Grp16<bf16_t> {
-  static constexpr int N = 8;
-  static __device__ __forceinline__ void load(const bf16_t* p, float (&f)[8]) {
-    const uint4 r = *reinterpret_cast<const uint4*>(p);
-    f[0] = bf16_bits_to_f32(r.x & 0xffffu); f[1] = bf16_bits_to_f32(r.x >> 16);
-    f[2] = bf16_bits_to_f32(r.y & 0xffffu); f[3] = bf16_bits_to_f32(r.y >> 16);
-    f[4] = bf16_bits_to_f32(r.z & 0xffffu); f[5] = bf16_bits_to_f32(r.z >> 16);
-    f[6] = bf16_bits_to_f32(r.w & 0xffffu); f[7] = bf16_bits_to_f32(r.w >> 16);
-  }
-  static __device__ __forceinline__ void store(bf16_t* p, const float (&f)[8]) {
-    uint4 r;
-    r.x = pack_bf16x2(f[0], f[1]); r.y = pack_bf16x2(f[2], f[3]); r.z = pack_bf16x2(f[4], f[5]); r.w = pack_bf16x2(f[6], f[7]);
-    *reinterpret_cast<uint4*>(p) = r;
-  }
-};
 
 // what one lane has seen of its row: the online softmax pair, the plain sum (fp64: at V = 5000 and logits near 80 an fp32 sum
 // resolves 0.03, and sum z - V lse cancels to a few units) and the running argmax (first index among equals)
@@ -58,13 +30,13 @@ __device__ __forceinline__ void row_take(RowAcc& a, const float (&x)[N], int c0)
 #pragma unroll
   for (int j = 1; j < N; ++j)
     if (x[j] > gm) { gm = x[j]; gi = j; }                // strict: the first of equal entries stays
-  if (gm > a.bv || (gm == a.bv && c0 + gi < a.bi)) { a.bv = gm; a.bi = c0 + gi; }
+  argmax_take(a.bv, a.bi, gm, c0 + gi);
   if constexpr (LOGITS) {
     if (gm > a.m) {                                      // one rescale per group; a.s is 0 while a.m is -inf
-      a.s = a.m == SL_NEG_INF ? 0.f : a.s * expf(a.m - gm);
+      a.s = lse_rescale(a.s, a.m, gm);
       a.m = gm;
     }
-    if (a.m != SL_NEG_INF) {
+    if (a.m != NEG_INF) {
 #pragma unroll
       for (int j = 0; j < N; ++j) a.s += expf(x[j] - a.m);
     }
@@ -75,25 +47,11 @@ __device__ __forceinline__ void row_take(RowAcc& a, const float (&x)[N], int c0)
   }
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ int wave_sum_i32(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 __device__ __forceinline__ bool sl_keep(const int* __restrict__ len, int b, int u, int y, int pad_idx) {
   return (len == nullptr || u < len[b]) && (pad_idx < 0 || y != pad_idx);
 }
 
-// grid = ceil(B U / 4), block = 256: wave w of a block owns row 4 blockIdx.x + w.  The row is cut into 16-byte groups anchored at
-// column 0, group k to lane k % 64, and a tail of V % N columns; a row whose address is 16-byte aligned loads a group at once, any
-// other row loads the same group element by element: the lanes see the same values in the same order, so the two paths give the
-// same bits.
+// grid = ceil(B U / 4), block = 256: wave w of a block owns row 4 blockIdx.x + w and reads it once (row_scan).
 template <typename T, bool LOGITS, bool SUM>
 __global__ __launch_bounds__(256) void seqloss_fwd_kernel(const T* __restrict__ X, long ldx, long bsx, const int* __restrict__ tgt,
                                                           long ldt, const int* __restrict__ len, int B, int U, int V, int pad_idx,
@@ -113,50 +71,16 @@ __global__ __launch_bounds__(256) void seqloss_fwd_kernel(const T* __restrict__ 
     return;
   }
   const T* x = X + (long)b * bsx + (long)u * ldx;
-  constexpr int N = Grp16<T>::N;
-  RowAcc a = {SL_NEG_INF, 0.f, 0.0, SL_NEG_INF, 0x7fffffff};
-  const int Vv = V - V % N;
-  const bool vec = (reinterpret_cast<uintptr_t>(x) & 15u) == 0;
-  // SL_DEPTH groups of a lane are requested before the first is consumed (one wave per row: the loads in flight per lane are what
-  // hides the memory latency); the groups are still consumed in increasing column order
-  for (int c0 = lane * N; c0 < Vv; c0 += 64 * N * SL_DEPTH) {
-    float f[SL_DEPTH][N];
-#pragma unroll
-    for (int d = 0; d < SL_DEPTH; ++d) {
-      const int c = c0 + d * 64 * N;
-      if (c < Vv) {
-        if (vec) Grp16<T>::load(x + c, f[d]);
-        else {
-#pragma unroll
-          for (int j = 0; j < N; ++j) f[d][j] = to_f32(x[c + j]);
-        }
-      }
-    }
-#pragma unroll
-    for (int d = 0; d < SL_DEPTH; ++d) {
-      const int c = c0 + d * 64 * N;
-      if (c < Vv) row_take<LOGITS, SUM, N>(a, f[d], c);
-    }
-  }
-  for (int c = Vv + lane; c < V; c += 64) {              // the tail: fewer than N columns
-    const float f[1] = {to_f32(x[c])};
-    row_take<LOGITS, SUM, 1>(a, f, c);
-  }
+  RowAcc a = {NEG_INF, 0.f, 0.0, NEG_INF, 0x7fffffff};
+  row_scan(x, V, lane, [&](const auto& g, int c0) { row_take<LOGITS, SUM>(a, g, c0); });
   // across the wave (butterflies: every lane ends with the same bits)
   float bv = a.bv;
   int bi = a.bi;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(bv, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-  }
+  argmax_meet<64>(bv, bi);
   double L = 0.0;                                        // log sum exp of the row (logits form)
   if constexpr (LOGITS) {
-    float m = a.m;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    const float s = wave_sum(a.m == SL_NEG_INF ? 0.f : a.s * expf(a.m - m));
+    const float m = wave_max(a.m);
+    const float s = wave_sum(lse_rescale(a.s, a.m, m));
     L = (double)m + (double)logf(s);
   }
   double sum = 0.0;
@@ -238,10 +162,10 @@ __global__ __launch_bounds__(256) void seqloss_bwd_kernel(const T* __restrict__ 
     if constexpr (LOGITS) return gr * (expf((float)((double)z - L)) - q);    // fp64 difference: see the forward's note
     else return -(gr * q);
   };
-  for (int c0 = lane * N; c0 < Vv; c0 += 64 * N * SL_DEPTH) {
-    float f[SL_DEPTH][N];
+  for (int c0 = lane * N; c0 < Vv; c0 += 64 * N * ROW_DEPTH) {
+    float f[ROW_DEPTH][N];
 #pragma unroll
-    for (int d = 0; d < SL_DEPTH; ++d) {
+    for (int d = 0; d < ROW_DEPTH; ++d) {
       const int c = c0 + d * 64 * N;
       if (c < Vv) {
         if (read && vec_x) Grp16<T>::load(x + c, f[d]);
@@ -252,7 +176,7 @@ __global__ __launch_bounds__(256) void seqloss_bwd_kernel(const T* __restrict__ 
       }
     }
 #pragma unroll
-    for (int d = 0; d < SL_DEPTH; ++d) {
+    for (int d = 0; d < ROW_DEPTH; ++d) {
       const int c = c0 + d * 64 * N;
       if (c < Vv) {
 #pragma unroll

@@ -295,6 +295,47 @@ __device__ __forceinline__ float wave_sum(float v) {
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
 }
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+__device__ __forceinline__ int wave_sum_i32(int v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+  return v;
+}
+
+// ---- the pieces of a row's (max, arg-max, sum exp) that every vocabulary head shares
+static constexpr float NEG_INF = -__builtin_inff();
+// (value, column) meets (value, column): the higher value, the lower column among equals; a NaN on either side never wins
+__device__ __forceinline__ void argmax_take(float& m, int& k, float om, int ok) {
+  if (om > m || (om == m && ok < k)) { m = om; k = ok; }
+}
+// the pairs of W neighbouring lanes (W = 64: the wave, W = 16: a row of 16) meet; all W end with the winner
+template <int W>
+__device__ __forceinline__ void argmax_meet(float& m, int& k) {
+#pragma unroll
+  for (int off = W / 2; off > 0; off >>= 1) argmax_take(m, k, __shfl_xor(m, off, W), __shfl_xor(k, off, W));
+}
+// sum exp(. - m) -> sum exp(. - M), M >= m; an empty side (max -inf) contributes nothing
+__device__ __forceinline__ float lse_rescale(float s, float m, float M) { return m == NEG_INF ? 0.f : s * expf(m - M); }
+// the two-pass opening of a row kernel: lane-strided max, then sum exp(x - max) in increasing columns per lane; m and s end the
+// same in every lane
+template <typename T>
+__device__ __forceinline__ void row_max_sumexp(const T* x, int V, int lane, float& m, float& s) {
+  m = NEG_INF;
+  for (int c = lane; c < V; c += 64) m = fmaxf(m, to_f32(x[c]));
+  m = wave_max(m);
+  s = 0.f;
+  for (int c = lane; c < V; c += 64) s += expf(to_f32(x[c]) - m);
+  s = wave_sum(s);
+}
 
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }

@@ -9,11 +9,9 @@
 //   fused:   joint -> GEMM whose epilogue keeps only per-(row, column tile) (max, sum exp) partials and z_blank / z_y -> combine
 //            -> DP; backward: the same GEMM recomputed, its epilogue turns the tile into dz in registers and stores it once.
 // Every reduction has a fixed order (no atomics): losses and gradients are bit-reproducible.
-#include "gemm_common.h"
+#include "head_tile.h"
 
 namespace smx {
-
-static constexpr float TR_NEG_INF = -__builtin_inff();
 
 static constexpr double TR_NEG_INF64 = -__builtin_inf();
 __device__ __forceinline__ double lae2(double a, double b) {       // log(exp a + exp b), -inf safe
@@ -129,13 +127,8 @@ __global__ __launch_bounds__(256) void row_stats_kernel(const T* __restrict__ Z,
   const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (n >= rows) return;
   const T* z = Z + (long)n * ldz;
-  float m = TR_NEG_INF;
-  for (int c = lane; c < V; c += 64) m = fmaxf(m, to_f32(z[c]));
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
-  float s = 0.f;
-  for (int c = lane; c < V; c += 64) s += expf(to_f32(z[c]) - m);
-  s = wave_sum(s);
+  float m, s;
+  row_max_sumexp(z, V, lane, m, s);
   if (lane == 0) {
     const float l = m + logf(s);
     const int y = row_target(targets, n, Tm, U1);
@@ -295,108 +288,8 @@ __global__ __launch_bounds__(256) void logit_grad_kernel(const T* __restrict__ Z
   }
 }
 
-// ---- fused GEMM tiles: z = H W^T + bias on a 128-row x 128-column tile, 4 waves (2 x 2) of 64 x 64, 32 x 32 MFMA fragments ----
-// MFMA operand a = W (columns v), b = H (lattice rows n): lane l holds row n = l % 32 of each fragment, accumulator register r
-// column v = 8 (r / 4) + 4 (l / 32) + r % 4.  A row's reductions over v are in-thread, then across the two lane halves and
-// the two waves that share its rows.  BK: 64 (bf16, v_mfma_f32_32x32x16_bf16) / 32 (fp32, v_mfma_f32_32x32x2_f32) reduce
-// elements per LDS stage; the next stage is fetched into registers while this one is multiplied.
-static constexpr int TJ_TILE = 128;
-template <typename T> struct TjTraits;
-template <> struct TjTraits<bf16_t> { static constexpr int BK = 64, PAD = 8; };
-template <> struct TjTraits<float> { static constexpr int BK = 32, PAD = 4; };
-
-template <typename T>
-struct TjTile {
-  static constexpr int BK = TjTraits<T>::BK, LDK = BK + TjTraits<T>::PAD;      // LDS row stride (elements; 16-byte multiple)
-  static constexpr int CPR = BK * (int)sizeof(T) / 16;                          // 16-byte chunks per operand row and stage
-  static constexpr int NLD = TJ_TILE * CPR / 256;                               // chunks per thread and operand
-  static constexpr int OP_BYTES = TJ_TILE * LDK * (int)sizeof(T);
-};
-
-// acc[i][j]: fragment i of the wave's 64 columns, fragment j of its 64 rows.  smem: 2 * OP_BYTES.
-template <typename T>
-__device__ __forceinline__ void tj_mainloop(const T* __restrict__ H, const T* __restrict__ W, int N, int V, int J, int n0, int v0,
-                                            char* smem, f32x16 (&acc)[2][2]) {
-  using TT = TjTile<T>;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wv = wave & 1, wn = wave >> 1, l31 = lane & 31, hi = lane >> 5;
-  char* Hs = smem;
-  char* Ws = smem + TT::OP_BYTES;
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-  uint4 rh[TT::NLD], rw[TT::NLD];
-  auto load = [&](int k0) __attribute__((always_inline)) {
-#pragma unroll
-    for (int p = 0; p < TT::NLD; ++p) {
-      const int idx = t + 256 * p, r = idx / TT::CPR, c = idx % TT::CPR;
-      const int n = n0 + r, v = v0 + r;
-      rh[p] = n < N ? *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(H + (long)n * J + k0) + c * 16) : make_uint4(0, 0, 0, 0);
-      rw[p] = v < V ? *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(W + (long)v * J + k0) + c * 16) : make_uint4(0, 0, 0, 0);
-    }
-  };
-  const int nk = J / TT::BK;
-  load(0);
-  for (int kt = 0; kt < nk; ++kt) {
-    __syncthreads();                                     // the previous stage has been read
-#pragma unroll
-    for (int p = 0; p < TT::NLD; ++p) {
-      const int idx = t + 256 * p, r = idx / TT::CPR, c = idx % TT::CPR;
-      *reinterpret_cast<uint4*>(Hs + r * TT::LDK * (int)sizeof(T) + c * 16) = rh[p];
-      *reinterpret_cast<uint4*>(Ws + r * TT::LDK * (int)sizeof(T) + c * 16) = rw[p];
-    }
-    __syncthreads();
-    if (kt + 1 < nk) load((kt + 1) * TT::BK);
-    if constexpr (sizeof(T) == 2) {
-#pragma unroll
-      for (int kk = 0; kk < TT::BK / 16; ++kk) {
-        bf16x8 fa[2], fb[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-          fa[i] = *reinterpret_cast<const bf16x8*>(Ws + ((wv * 64 + i * 32 + l31) * TT::LDK + kk * 16 + hi * 8) * 2);
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          fb[j] = *reinterpret_cast<const bf16x8*>(Hs + ((wn * 64 + j * 32 + l31) * TT::LDK + kk * 16 + hi * 8) * 2);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
-      }
-    } else {
-      const float* Wf = reinterpret_cast<const float*>(Ws);
-      const float* Hf = reinterpret_cast<const float*>(Hs);
-      // fp32 operands: each stage is summed on its own and then added to the running sum.  One chain over the whole of J rounds
-      // J / 2 times in a row (x2 MFMAs); at J = 1088 that put lse / lp / dz 4 - 7 x further from fp64 than a blocked fp32 product
-      // (tests/test_transducer_kernels_gpu.py).  Two levels round BK / 2 + J / BK times.
-      f32x16 st[2][2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int e = 0; e < 16; ++e) st[i][j][e] = 0.f;
-#pragma unroll
-      for (int kk = 0; kk < TT::BK / 2; ++kk) {
-        float fa[2], fb[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) fa[i] = Wf[(wv * 64 + i * 32 + l31) * TT::LDK + kk * 2 + hi];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) fb[j] = Hf[(wn * 64 + j * 32 + l31) * TT::LDK + kk * 2 + hi];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) st[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i], fb[j], st[i][j], 0, 0, 0);
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] += st[i][j];
-    }
-  }
-}
-
+// ---- fused GEMM tiles (head_tile.h): z = H W^T + bias, H's rows being the lattice rows n.  Rows >= N and columns >= V are
+// clamped copies in the main loop: every use below is guarded by n < N / v < V, and blank and y are < V. ----
 // forward: part[n][ct] = (max, sum exp) of row n over the valid columns of column tile ct; zb[n] / zy[n] from the tile holding
 // them.  No logit leaves the registers.
 template <typename T>
@@ -404,26 +297,24 @@ __global__ __launch_bounds__(256, 2) void tj_stats_kernel(const T* __restrict__ 
                                                           const int32_t* __restrict__ targets, int N, int Tm, int U1, int J, int V,
                                                           int blank, int nct, float2* __restrict__ part, float* __restrict__ zb,
                                                           float* __restrict__ zy) {
-  __shared__ __attribute__((aligned(16))) char smem[2 * TjTile<T>::OP_BYTES];
-  __shared__ float sbias[TJ_TILE];
-  __shared__ float2 red[TJ_TILE];
+  __shared__ __attribute__((aligned(16))) char smem[2 * HeadTile<T>::OP_BYTES];
+  __shared__ float sbias[HEAD_TILE];
+  __shared__ LseStat red[HEAD_TILE];
   const int ct = blockIdx.x % nct, rt = blockIdx.x / nct;
-  const int n0 = rt * TJ_TILE, v0 = ct * TJ_TILE;
+  const int n0 = rt * HEAD_TILE, v0 = ct * HEAD_TILE;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wv = wave & 1, wn = wave >> 1, l31 = lane & 31, hi = lane >> 5;
-  if (t < TJ_TILE) sbias[t] = (bias && v0 + t < V) ? bias[v0 + t] : 0.f;
+  if (t < HEAD_TILE) sbias[t] = (bias && v0 + t < V) ? bias[v0 + t] : 0.f;
   f32x16 acc[2][2];
-  tj_mainloop<T>(H, W, N, V, J, n0, v0, smem, acc);      // (its barriers publish sbias)
-  float m[2], s[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
+  head_mainloop<T>(H, J, W, N, V, J, n0, v0, smem, acc);  // (its barriers publish sbias)
+  auto thread_stat = [&](int j) __attribute__((always_inline)) -> LseStat {
     const int n = n0 + wn * 64 + j * 32 + l31;
     const int y = n < N ? row_target(targets, n, Tm, U1) : -1;
-    float mx = TR_NEG_INF;
+    float mx = NEG_INF;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int vl = wv * 64 + i * 32 + 8 * (r >> 2) + 4 * hi + (r & 3), v = v0 + vl;
+        const int vl = head_col(wv, i, r, hi), v = v0 + vl;
         const float z = acc[i][j][r] + sbias[vl];
         acc[i][j][r] = z;
         if (v < V) mx = fmaxf(mx, z);
@@ -434,36 +325,13 @@ __global__ __launch_bounds__(256, 2) void tj_stats_kernel(const T* __restrict__ 
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int v = v0 + wv * 64 + i * 32 + 8 * (r >> 2) + 4 * hi + (r & 3);
-        if (v < V) sm += expf(acc[i][j][r] - mx);
-      }
-    // the other lane half (same row, the other 4-column groups): fixed pairing, both halves end with the same bits
-    const float mo = __shfl_xor(mx, 32, 64), so = __shfl_xor(sm, 32, 64);
-    const float M = fmaxf(mx, mo);
-    const float a = hi ? mo : mx, sa = hi ? so : sm, bq = hi ? mx : mo, sb = hi ? sm : so;   // (lower half first)
-    m[j] = M;
-    s[j] = M == TR_NEG_INF ? 0.f : (a == TR_NEG_INF ? 0.f : sa * expf(a - M)) + (bq == TR_NEG_INF ? 0.f : sb * expf(bq - M));
-  }
-  // the two waves of a row pair: wave wv = 1 parks its result, wave wv = 0 folds it in (column order) and writes
-  if (wv == 1 && hi == 0) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) red[wn * 64 + j * 32 + l31] = make_float2(m[j], s[j]);
-  }
-  __syncthreads();
-  if (wv == 0 && hi == 0) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int nl = wn * 64 + j * 32 + l31, n = n0 + nl;
-      if (n < N) {
-        const float2 o = red[nl];
-        const float M = fmaxf(m[j], o.x);
-        const float S = M == TR_NEG_INF ? 0.f
-                                         : (m[j] == TR_NEG_INF ? 0.f : s[j] * expf(m[j] - M)) + (o.x == TR_NEG_INF ? 0.f : o.y * expf(o.x - M));
-        part[(long)n * nct + ct] = make_float2(M, S);
-      }
-    }
-  }
+      for (int r = 0; r < 16; ++r)
+        if (v0 + head_col(wv, i, r, hi) < V) sm += expf(acc[i][j][r] - mx);
+    return {mx, sm};
+  };
+  head_row_meet(red, thread_stat, [&](int nl, const LseStat& r) {
+    if (n0 + nl < N) part[(long)(n0 + nl) * nct + ct] = make_float2(r.m, r.s);
+  });
 }
 
 // lse[n] from the partials in column-tile order; lpb = zb - lse, lpy = zy - lse (0 where the row has no label)
@@ -473,12 +341,12 @@ __global__ __launch_bounds__(256) void tj_combine_kernel(const float2* __restric
                                                          float* __restrict__ lpy) {
   const int n = blockIdx.x * 256 + threadIdx.x;
   if (n >= N) return;
-  float M = TR_NEG_INF;
+  float M = NEG_INF;
   for (int c = 0; c < nct; ++c) M = fmaxf(M, part[(long)n * nct + c].x);
   float S = 0.f;
   for (int c = 0; c < nct; ++c) {
     const float2 p = part[(long)n * nct + c];
-    if (p.x != TR_NEG_INF) S += p.y * expf(p.x - M);
+    if (p.x != NEG_INF) S += p.y * expf(p.x - M);        // (not lse_rescale: the guarded add contracts to one fma, and that is in the bits)
   }
   const float l = M + logf(S);
   const int y = row_target(targets, n, Tm, U1);
@@ -496,20 +364,20 @@ __global__ __launch_bounds__(256, 2) void tj_grad_kernel(const T* __restrict__ H
                                                          const float* __restrict__ gb, const float* __restrict__ gy, int row0, int N,
                                                          int Tm, int U1, int J, int V, int blank, int nct, T* __restrict__ dz,
                                                          long lddz) {
-  __shared__ __attribute__((aligned(16))) char smem[2 * TjTile<T>::OP_BYTES];
-  __shared__ float sbias[TJ_TILE];
+  __shared__ __attribute__((aligned(16))) char smem[2 * HeadTile<T>::OP_BYTES];
+  __shared__ float sbias[HEAD_TILE];
   const int ct = blockIdx.x % nct, rt = blockIdx.x / nct;
-  const int n0 = rt * TJ_TILE, v0 = ct * TJ_TILE;
+  const int n0 = rt * HEAD_TILE, v0 = ct * HEAD_TILE;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wv = wave & 1, wn = wave >> 1, l31 = lane & 31, hi = lane >> 5;
   int live = 0;
-  if (t < TJ_TILE) {
+  if (t < HEAD_TILE) {
     sbias[t] = (bias && v0 + t < V) ? bias[v0 + t] : 0.f;
     const int n = n0 + t;
     live = n < N && (gb[row0 + n] != 0.f || gy[row0 + n] != 0.f);
   }
   if (!__syncthreads_or(live)) {
-    for (int i = t; i < TJ_TILE * (TJ_TILE / 4); i += 256) {
-      const int r = i / (TJ_TILE / 4), v = v0 + (i % (TJ_TILE / 4)) * 4, n = n0 + r;
+    for (int i = t; i < HEAD_TILE * (HEAD_TILE / 4); i += 256) {
+      const int r = i / (HEAD_TILE / 4), v = v0 + (i % (HEAD_TILE / 4)) * 4, n = n0 + r;
       if (n < N && v < V) {
         const float zz[4] = {0.f, 0.f, 0.f, 0.f};
         store4(dz + (long)n * lddz + v, zz);
@@ -518,7 +386,7 @@ __global__ __launch_bounds__(256, 2) void tj_grad_kernel(const T* __restrict__ H
     return;
   }
   f32x16 acc[2][2];
-  tj_mainloop<T>(H + (long)row0 * J, W, N, V, J, n0, v0, smem, acc);
+  head_mainloop<T>(H + (long)row0 * J, J, W, N, V, J, n0, v0, smem, acc);
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int n = n0 + wn * 64 + j * 32 + l31;
@@ -529,7 +397,7 @@ __global__ __launch_bounds__(256, 2) void tj_grad_kernel(const T* __restrict__ H
     for (int i = 0; i < 2; ++i)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const int vl = wv * 64 + i * 32 + 8 * q + 4 * hi, v = v0 + vl;
+        const int vl = head_col(wv, i, 4 * q, hi), v = v0 + vl;
         if (v >= V) continue;
         float o[4];
 #pragma unroll
@@ -659,7 +527,7 @@ extern "C" int smx_transducer_fused_ok(int dtype, int J, int V) {
   return (dtype == SMX_BF16 || dtype == SMX_F32) && J > 0 && J % 64 == 0 && V > 0 && V % 4 == 0;
 }
 
-static int tj_nct(int V) { return (V + TJ_TILE - 1) / TJ_TILE; }
+static int tj_nct(int V) { return (V + HEAD_TILE - 1) / HEAD_TILE; }
 
 extern "C" size_t smx_transducer_stats_workspace(int rows, int V) {
   // [partials (rows, nct) float2][z_blank (rows)][z_y (rows)]
@@ -677,7 +545,7 @@ extern "C" int smx_transducer_gemm_stats(int dtype, const void* H, const void* W
   const long rows = (long)B * T * U1;
   SMX_REQUIRE(rows < (1L << 31) / 2, "smx_transducer_gemm_stats: too many lattice rows");
   if (rows == 0) return SMX_OK;
-  const int nct = tj_nct(V), nrt = (int)((rows + TJ_TILE - 1) / TJ_TILE);
+  const int nct = tj_nct(V), nrt = (int)((rows + HEAD_TILE - 1) / HEAD_TILE);
   float2* part = reinterpret_cast<float2*>(workspace);
   float* zb = reinterpret_cast<float*>(part + rows * nct);
   float* zy = zb + rows;
@@ -698,7 +566,7 @@ extern "C" int smx_transducer_gemm_grad(int dtype, const void* H, const void* W,
   const long rows = (long)B * T * U1;
   SMX_REQUIRE(row0 >= 0 && nrows >= 0 && row0 + (long)nrows <= rows, "smx_transducer_gemm_grad: row range [%d, %d + %d) outside the lattice", row0, row0, nrows);
   if (nrows == 0) return SMX_OK;
-  const int nct = tj_nct(V), nrt = (nrows + TJ_TILE - 1) / TJ_TILE;
+  const int nct = tj_nct(V), nrt = (nrows + HEAD_TILE - 1) / HEAD_TILE;
   const dim3 grid((unsigned)((long)nrt * nct));
   if (dtype == SMX_BF16) hipLaunchKernelGGL((tj_grad_kernel<bf16_t>), grid, dim3(256), 0, STREAM, (const bf16_t*)H, (const bf16_t*)W, bias, targets, lse, gb, gy, row0, nrows, T, U1, J, V, blank, nct, (bf16_t*)dz, lddz);
   else hipLaunchKernelGGL((tj_grad_kernel<float>), grid, dim3(256), 0, STREAM, (const float*)H, (const float*)W, bias, targets, lse, gb, gy, row0, nrows, T, U1, J, V, blank, nct, (float*)dz, lddz);

@@ -129,7 +129,7 @@ def greedy_decode(scores, lens: Optional[torch.Tensor] = None, blank=0, state: O
     return _collapse(tok, lp, _in_len(lens, B, T, scores.device), _blank(blank, V), state, start, out)
 
 
-# Route of greedy_decode_from_encoder: True = the fused head (csrc/ctcdec.hip: ctc_head_kernel), False = this package's Linear, then the
+# Route of greedy_decode_from_encoder: True = the fused head (csrc/ctcdec.hip: ctc_head_kernel on the tile of csrc/head_tile.h), False = this package's Linear, then the
 # row pass over the stored logits.  The rule: the fused route only where it beat the unfused pair by more than the run-to-run spread
 # of both (its slowest window faster than the other's fastest), measured in the same session: tools/ctcdec_bench.py on one MI355X,
 # profiles/ctcdec_bench.jsonl and ctcdec_bench_crossover.jsonl; fused / unfused, medians of 5 windows, N = B T rows:
