@@ -1,7 +1,7 @@
 """Host-side orchestration of the SummaryMixing encoder hot path on top of the libsmx.so kernels.
 
 Every block is a (forward, backward-closure) pair written against ``ops``; a single generic
-``torch.autograd.Function`` (``_BlockFn``) chains the blocks, so autograd only ever sees one activation in and
+``torch.autograd.Function`` (``node`` / ``block``) chains the blocks, so autograd only ever sees the activations in and
 one activation out per block: residual adds, gradient fan-in sums and parameter-gradient accumulation all
 happen inside the HIP kernels (GEMM epilogues, LayerNorm-backward residual input, split-K slabs / partial rows
 folded into ``param.grad`` by a fixed-order reduction - no atomics).  Parameter gradients are therefore written by
@@ -19,6 +19,7 @@ import weakref
 
 import collections
 import ctypes
+import math
 import os
 
 import torch
@@ -408,30 +409,39 @@ def _wgrad(dz, x, gW, N, M, K, dbias):
         defer(ws.data_ptr() + 4 * boff, dbias, M, nslabs, 1, M)
 
 
-class _BlockFn(torch.autograd.Function):
+class _NodeFn(torch.autograd.Function):
+    """A (forward, backward-closure) pair as ONE autograd node: the only thing autograd keeps is the closure."""
+
     @staticmethod
-    def forward(ctx, x, run, done, *params):
-        y, bwd = run(x, True)
-        ctx.bwd, ctx.done = bwd, done
-        ctx.n = len(params)
-        return y
+    def forward(ctx, run, done, n_in, *tensors):
+        out, ctx.bwd = run(True)
+        ctx.done, ctx.n_params = done, len(tensors) - n_in
+        return out
 
     @staticmethod
     def backward(ctx, dy):
-        dx = ctx.bwd(dy)
-        flush_deferred()        # the block's parameter gradients are final before its bucket is all-reduced
+        grads = ctx.bwd(dy)
+        flush_deferred()        # the node's parameter gradients are final before its bucket is all-reduced
         if ctx.done is not None:
             ctx.done()          # e.g. launch this block's gradient-bucket all-reduce (trainer.FlatAdamW)
-        return (dx, None, None) + (None,) * ctx.n
+        return (None, None, None) + (grads if isinstance(grads, tuple) else (grads,)) + (None,) * ctx.n_params
+
+
+def node(run, inputs, params, on_bwd_done=None):
+    """Run `run(need_bwd) -> (out, bwd)` over the activations `inputs` (run holds them itself); hook bwd into autograd when anything
+    upstream needs gradients.  bwd(dy) -> one gradient per input (a tuple; the bare gradient of a single input).  The parameters are
+    the node's inputs too, so that it is built when only they need gradients; their gradients are accumulated into ``param.grad`` by
+    the kernels inside the closure.  on_bwd_done runs behind the backward and the flush of its deferred reductions."""
+    params = [p for p in params if p is not None]
+    need = torch.is_grad_enabled() and (any(t.requires_grad for t in inputs) or any(p.requires_grad for p in params))
+    if not need:
+        return run(False)[0]
+    return _NodeFn.apply(run, on_bwd_done, len(inputs), *inputs, *params)
 
 
 def block(x, run, params, on_bwd_done=None):
-    """Run `run(x, need_bwd) -> (y, bwd)`; hook bwd into autograd when anything upstream needs gradients."""
-    params = [p for p in params if p is not None]
-    need = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
-    if not need:
-        return run(x, False)[0]
-    return _BlockFn.apply(x, run, on_bwd_done, *params)
+    """node() for `run(x, need_bwd) -> (y, bwd)` with one activation in."""
+    return node(lambda need: run(x, need), (x,), params, on_bwd_done)
 
 
 # ----------------------------------------------------------------------------------------------------
@@ -1631,3 +1641,65 @@ def scaled_dot_product_attention(q, k, v, *, attn_bias=None, key_padding_mask=No
     if dropout_p > 0.0 and seed is None:
         seed = ops.new_dropout_seed()
     return _SdpaFn.apply(q, k, v, attn_bias, pad, bool(causal), float(dropout_p), seed or 0, scale)
+
+
+def attention_sublayer(att, H, xq, xk, xv, B, Lq, S, bias, pad, causal, p_attn, *, seed=None, res=None, drop=None, need=True,
+                       need_dx=(True, True, True)):
+    """The attention sublayer of nnet.attention.MultiheadAttention and of a decoder layer, on 2-D row views:
+    out = res + D(out_proj(attention(in_proj(xq, xk, xv)))), D = `drop` (p, seed) | None in the out-projection's epilogue.  `att` holds
+    torch's parameters (in_proj_weight (3d, d), in_proj_bias, out_proj), H heads.  Which inputs there are selects the projections:
+    xk None - self-attention, ONE d -> 3d GEMM on xq; xv None or xv is xk - d -> d on xq plus d -> 2d on xk; else three GEMMs.  The
+    attention kernels read q / k / v through strides out of the packed projection outputs and write their gradients into buffers packed
+    the same way, so each projection has ONE dgrad / wgrad over the matching rows of in_proj_weight / in_proj_bias.  bias / pad / causal:
+    ops.attention_fwd's; p_attn: the attention dropout, its seed drawn here unless the caller drew it.
+    -> (out, bwd, kept).  bwd(dy, *res) -> one gradient per projection input (None-padded to three), res[i] added to the i-th in its
+    dgrad's epilogue; where need_dx[i] is false that dgrad is skipped and the slot returns res[i].  kept: for attention_sublayer_weights."""
+    Wi, bi, Wo, bo = att.in_proj_weight, att.in_proj_bias, att.out_proj.weight, att.out_proj.bias
+    d = Wi.shape[1]
+    D = d // H
+    dtype, dev = xq.dtype, xq.device
+    scale = 1.0 / math.sqrt(D)
+    Wc, Woc = wcast(Wi, dtype), wcast(Wo, dtype)
+    bd = bi.detach() if bi is not None else None
+    if seed is None:
+        seed = ops.new_dropout_seed() if p_attn > 0.0 else 0
+    # (input, first and one-past-last third of in_proj, rows per utterance) per projection GEMM
+    if xk is None:
+        segs = ((xq, 0, 3, Lq),)
+    elif xv is None or xv is xk:
+        segs = ((xq, 0, 1, Lq), (xk, 1, 3, S))
+    else:
+        segs = ((xq, 0, 1, Lq), (xk, 1, 2, S), (xv, 2, 3, S))
+
+    def thirds(t, lo, hi):
+        return t if (t is None or hi - lo == 3) else t[lo * d:hi * d]
+    q, k, v = (t for x, lo, hi, n in segs
+               for t in linear_fwd(x, thirds(Wc, lo, hi), thirds(bd, lo, hi))[0].view(B, n, hi - lo, H, D).unbind(2))
+    o, lse = ops.attention_fwd(q, k, v, bias, pad, causal, scale, p_attn, seed)
+    o2 = o.view(B * Lq, d)
+    out, _ = linear_fwd(o2, Woc, bo.detach() if bo is not None else None, res=res, drop=drop)
+    kept = (q, k, lse, bias, pad, causal, scale, p_attn, seed)
+    if not need:
+        return out, None, kept
+
+    def bwd(dy, *res):
+        do2, _ = linear_bwd(dy, o2, Woc, None, L.ACT_NONE, None, 1.0, gacc(Wo), gacc(bo), drop=drop)
+        gW, gb = gacc(Wi), gacc(bi)
+        packed = [torch.empty((B, n, hi - lo, H, D), dtype=dtype, device=dev) for _, lo, hi, n in segs]
+        dq, dk, dv = (t for g in packed for t in g.unbind(2))
+        ops.attention_bwd(do2.view(B, Lq, H, D), q, k, v, o, lse, bias, pad, causal, scale, p_attn, seed, dq=dq, dk=dk, dv=dv)
+        grads = [None, None, None]
+        for i, ((x, lo, hi, n), g) in enumerate(zip(segs, packed)):
+            r = res[i] if i < len(res) else None
+            dx, _ = linear_bwd(g.view(B * n, (hi - lo) * d), x, thirds(Wc, lo, hi), None, L.ACT_NONE, None, 1.0, thirds(gW, lo, hi),
+                               thirds(gb, lo, hi), need_dx=need_dx[i], res_grad=r if need_dx[i] else None)
+            grads[i] = dx if need_dx[i] else r
+        return tuple(grads)
+    return out, bwd, kept
+
+
+def attention_sublayer_weights(kept):
+    """The head-averaged attention weights (B, L, S) fp32 of an attention_sublayer call, detached: a launch of its own."""
+    q, k, lse, bias, pad, causal, scale, p_attn, seed = kept
+    with torch.no_grad():
+        return ops.attention_weights(q, k, lse, bias, pad, causal, scale, p_attn, seed)

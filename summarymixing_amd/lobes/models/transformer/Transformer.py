@@ -2,9 +2,11 @@
 TransformerDecoderLayer (:683-866), TransformerDecoder (:869-987), get_key_padding_mask (:1024-1060) and get_lookahead_mask
 (:1063-1090), with upstream's names, arguments and ``state_dict`` keys.  (PositionalEncoding, :284-335, lives in TransformerASR.py.)
 
-A decoder - its layers and the final LayerNorm - is ONE autograd node over (tgt, memory), built like functional.encoder_stack: every
-sublayer is a (forward, backward-closure) pair on the package's kernels and the gradient between two layers never visits autograd;
-parameter gradients are accumulated into ``param.grad`` by the kernels.  Per layer: norm1 -> ONE d -> 3d projection GEMM -> the
+A decoder - its layers and the final LayerNorm - is ONE autograd node over (tgt, memory) (functional.node), built like
+functional.encoder_stack: every sublayer is a (forward, backward-closure) pair on the package's kernels and the gradient between two
+layers never visits autograd; parameter gradients are accumulated into ``param.grad`` by the kernels.  Both attention sublayers of a
+layer are functional.attention_sublayer on the parameters of its two MultiheadAttention modules - the code their own ``forward``
+runs.  Per layer: norm1 -> ONE d -> 3d projection GEMM -> the
 fused causal self-attention (csrc/attention.hip; the look-ahead mask is the kernels' ``causal`` flag, no (U, U) tensor exists) ->
 the out-projection with dropout1 and the residual in its epilogue; norm2 -> d -> d on the targets and d -> 2d on the memory -> the
 fused cross-attention -> out-projection + dropout2 + residual; then functional.ffn_module_fwd with alpha = 1 and eps = 1e-6 (norm3,
@@ -18,8 +20,6 @@ once per forward.  GPU only (a CPU tensor raises ops.NO_CPU).
 Deviations, all stated: a query row whose keys are all masked yields zeros (torch: NaN); returned attention weights are detached;
 ``tgt_mask`` may be the module constant LOOKAHEAD instead of the dense matrix (what TransformerASR.forward / decode pass); the
 embedding maps a token outside [0, V) to a zero row where torch raises."""
-import math
-
 import torch
 from torch import nn
 
@@ -121,65 +121,6 @@ class NormalizedEmbedding(nn.Module):
         return self.embed(x, self._zero_pe[:U])[0]
 
 
-def _attn(att, xq, xkv, B, Lq, S, bias, pad, causal, p_attn, res, drop, need, need_dkv=True):
-    """One attention sublayer on row views: out = res + D(out_proj(attention(in_proj(xq [, xkv])))) with D = `drop` (p, seed) | None in
-    the out-projection's epilogue.  xkv None: self-attention (one d -> 3d GEMM).  -> (out, bwd, kept); bwd(dy, res_q, res_kv) ->
-    (dxq + res_q, dxkv + res_kv), the additions in the dgrad epilogues; kept = what ops.attention_weights needs."""
-    d, H = att.d_model, att.nhead
-    D = d // H
-    dtype, dev = xq.dtype, xq.device
-    scale = 1.0 / math.sqrt(D)
-    Wi, bi, Wo, bo = att.att.in_proj_weight, att.att.in_proj_bias, att.att.out_proj.weight, att.att.out_proj.bias
-    Wc, Woc = F.wcast(Wi, dtype), F.wcast(Wo, dtype)
-    bd = bi.detach() if bi is not None else None
-    seed = ops.new_dropout_seed() if p_attn > 0.0 else 0
-
-    def bsl(lo, hi):
-        return bd[lo * d:hi * d] if bd is not None else None
-    if xkv is None:
-        qkv, _ = F.linear_fwd(xq, Wc, bd)
-        p5 = qkv.view(B, Lq, 3, H, D)
-        q, k, v = p5[:, :, 0], p5[:, :, 1], p5[:, :, 2]
-    else:
-        q = F.linear_fwd(xq, Wc[:d], bsl(0, 1))[0].view(B, Lq, H, D)
-        kv, _ = F.linear_fwd(xkv, Wc[d:], bsl(1, 3))
-        p5 = kv.view(B, S, 2, H, D)
-        k, v = p5[:, :, 0], p5[:, :, 1]
-    o, lse = ops.attention_fwd(q, k, v, bias, pad, causal, scale, p_attn, seed)
-    o2 = o.view(B * Lq, d)
-    out, _ = F.linear_fwd(o2, Woc, bo.detach() if bo is not None else None, res=res, drop=drop)
-    kept = (q, k, lse, bias, pad, causal, scale, p_attn, seed)
-    if not need:
-        return out, None, kept
-
-    def bwd(dy, res_q=None, res_kv=None):
-        do2, _ = F.linear_bwd(dy, o2, Woc, None, L.ACT_NONE, None, 1.0, F.gacc(Wo), F.gacc(bo), drop=drop)
-        do = do2.view(B, Lq, H, D)
-        gW, gb = F.gacc(Wi), F.gacc(bi)
-
-        def gsl(g, lo, hi):
-            return g[lo * d:hi * d] if g is not None else None
-        if xkv is None:
-            g5 = torch.empty((B, Lq, 3, H, D), dtype=dtype, device=dev)
-            ops.attention_bwd(do, q, k, v, o, lse, bias, pad, causal, scale, p_attn, seed, dq=g5[:, :, 0], dk=g5[:, :, 1], dv=g5[:, :, 2])
-            dx, _ = F.linear_bwd(g5.view(B * Lq, 3 * d), xq, Wc, None, L.ACT_NONE, None, 1.0, gW, gb, res_grad=res_q)
-            return dx, None
-        dq = torch.empty((B, Lq, H, D), dtype=dtype, device=dev)
-        g5 = torch.empty((B, S, 2, H, D), dtype=dtype, device=dev)
-        ops.attention_bwd(do, q, k, v, o, lse, bias, pad, causal, scale, p_attn, seed, dq=dq, dk=g5[:, :, 0], dv=g5[:, :, 1])
-        dxq, _ = F.linear_bwd(dq.view(B * Lq, d), xq, Wc[:d], None, L.ACT_NONE, None, 1.0, gsl(gW, 0, 1), gsl(gb, 0, 1), res_grad=res_q)
-        dxkv, _ = F.linear_bwd(g5.view(B * S, 2 * d), xkv, Wc[d:], None, L.ACT_NONE, None, 1.0, gsl(gW, 1, 3), gsl(gb, 1, 3),
-                               need_dx=need_dkv, res_grad=res_kv if need_dkv else None)
-        return dxq, (dxkv if need_dkv else res_kv)
-    return out, bwd, kept
-
-
-def _weights(kept):
-    q, k, lse, bias, pad, causal, scale, p, seed = kept
-    with torch.no_grad():
-        return ops.attention_weights(q, k, lse, bias, pad, causal, scale, p, seed)
-
-
 class TransformerDecoderLayer(nn.Module):
     def __init__(self, d_ffn, nhead, d_model, kdim=None, vdim=None, dropout=0.0, activation=nn.ReLU, normalize_before=False,
                  attention_type="regularMHA", causal=None):
@@ -212,7 +153,9 @@ class TransformerDecoderLayer(nn.Module):
         p = self.p_drop if self.training else 0.0
         n1, n2, n3 = self.norm1.norm, self.norm2.norm, self.norm3.norm
         f0, f3 = self.pos_ffn.ffn[0], self.pos_ffn.ffn[3]
-        act = self.act
+        act, H = self.act, self.nhead
+        sa, ca = self.self_attn.att, self.multihead_attn.att
+        need_dx = (True, need_dmem)
 
         def site():
             return (p, ops.new_dropout_seed()) if p > 0.0 else None
@@ -220,9 +163,10 @@ class TransformerDecoderLayer(nn.Module):
         def run(x, need):
             if pre:
                 h1, lb1 = F.ln_fwd(x, n1.weight, n1.bias, n1.eps, need, out_dtype=compute)
-                x1, ab1, ks = _attn(self.self_attn, h1, None, B, U, U, sbias, tpad, causal, p, x, site(), need)
+                x1, ab1, ks = F.attention_sublayer(sa, H, h1, None, None, B, U, U, sbias, tpad, causal, p, res=x, drop=site(), need=need)
                 h2, lb2 = F.ln_fwd(x1, n2.weight, n2.bias, n2.eps, need, out_dtype=compute)
-                x2, ab2, kc = _attn(self.multihead_attn, h2, mem2, B, U, S, mbias, mpad, False, p, x1, site(), need, need_dmem)
+                x2, ab2, kc = F.attention_sublayer(ca, H, h2, mem2, None, B, U, S, mbias, mpad, False, p, res=x1, drop=site(), need=need,
+                                                    need_dx=need_dx)
                 P = {"ln_w": n3.weight, "ln_b": n3.bias, "W1": f0.weight, "b1": f0.bias, "W2": f3.weight, "b2": f3.bias}
                 y, fb = F.ffn_module_fwd(x2, P, act, need, compute, alpha=1.0, p=p, eps=n3.eps)
                 if not need:
@@ -230,14 +174,15 @@ class TransformerDecoderLayer(nn.Module):
 
                 def bwd(dy, dmem):
                     g2 = fb(dy)
-                    dh2, dmem = ab2(g2, None, dmem)
+                    dh2, dmem, _ = ab2(g2, None, dmem)
                     g1 = lb2(dh2, res=g2)
-                    dh1, _ = ab1(g1)
+                    dh1 = ab1(g1)[0]
                     return lb1(dh1, res=g1), dmem
                 return y, bwd, ks, kc
-            t1, ab1, ks = _attn(self.self_attn, x, None, B, U, U, sbias, tpad, causal, p, x, site(), need)
+            t1, ab1, ks = F.attention_sublayer(sa, H, x, None, None, B, U, U, sbias, tpad, causal, p, res=x, drop=site(), need=need)
             x1, lb1 = F.ln_fwd(t1, n1.weight, n1.bias, n1.eps, need)
-            t2, ab2, kc = _attn(self.multihead_attn, x1, mem2, B, U, S, mbias, mpad, False, p, x1, site(), need, need_dmem)
+            t2, ab2, kc = F.attention_sublayer(ca, H, x1, mem2, None, B, U, S, mbias, mpad, False, p, res=x1, drop=site(), need=need,
+                                                need_dx=need_dx)
             x2, lb2 = F.ln_fwd(t2, n2.weight, n2.bias, n2.eps, need)
             W1, W2 = F.wcast(f0.weight, compute), F.wcast(f3.weight, compute)
             d1, d2 = site(), site()
@@ -253,10 +198,9 @@ class TransformerDecoderLayer(nn.Module):
                                       up=(z1, act, None, 1.0, d1, None), wparam=f3.weight)
                 g2, _ = F.linear_bwd(dz1, x2, W1, z1, act, None, 1.0, F.gacc(f0.weight), F.gacc(f0.bias), dz_ready=True, res_grad=g3)
                 g2 = lb2(g2)
-                g1, dmem = ab2(g2, g2, dmem)
+                g1, dmem, _ = ab2(g2, g2, dmem)
                 g1 = lb1(g1)
-                dx, _ = ab1(g1, g1)
-                return dx, dmem
+                return ab1(g1, g1)[0], dmem
             return y, bwd, ks, kc
         return run
 
@@ -266,21 +210,6 @@ class TransformerDecoderLayer(nn.Module):
         out, sa, ca = _decode_stack([self], None, tgt, memory, tgt_mask, memory_mask, tgt_key_padding_mask, memory_key_padding_mask,
                                     pos_embs_tgt, pos_embs_src, "all")
         return out, sa[0], ca[0]
-
-
-class _DecFn(torch.autograd.Function):
-    """(tgt, memory) -> out through a (forward, backward-closure) pair: functional._BlockFn with two activations in."""
-
-    @staticmethod
-    def forward(ctx, run, tgt, memory, *params):
-        out, ctx.bwd = run(True)
-        ctx.n = len(params)
-        return out
-
-    @staticmethod
-    def backward(ctx, dy):
-        dt, dm = ctx.bwd(dy)
-        return (None, dt, dm) + (None,) * ctx.n
 
 
 def _decode_stack(layers, norm, tgt, memory, tgt_mask, memory_mask, tgt_kpm, mem_kpm, pos_embs_tgt, pos_embs_src, weights):
@@ -350,11 +279,10 @@ def _decode_stack(layers, norm, tgt, memory, tgt_mask, memory_mask, tgt_kpm, mem
             return g.view(B, U, d), (dmem.view(B, S, d) if dmem is not None else None)
         return x.view(B, U, d), bwd
 
-    need = torch.is_grad_enabled() and (tgt.requires_grad or memory.requires_grad or any(p.requires_grad for p in params))
-    out = _DecFn.apply(run, tgt, memory, *params) if need else run(False)[0]
+    out = F.node(run, (tgt, memory), params)
     n = len(layers)
-    sa = [_weights(ks) if weights == "all" else None for ks, _ in kept]
-    ca = [_weights(kc) if (weights == "all" or (weights == "last_cross" and i == n - 1)) else None for i, (_, kc) in enumerate(kept)]
+    sa = [F.attention_sublayer_weights(ks) if weights == "all" else None for ks, _ in kept]
+    ca = [F.attention_sublayer_weights(kc) if (weights == "all" or (weights == "last_cross" and i == n - 1)) else None for i, (_, kc) in enumerate(kept)]
     return out, sa, ca
 
 

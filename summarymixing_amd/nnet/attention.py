@@ -4,8 +4,10 @@ is made of): batch-first multi-head scaled-dot-product attention.  Parameters li
 (``att.in_proj_weight`` (3d, d), ``att.in_proj_bias``, ``att.out_proj.weight``, ``att.out_proj.bias``), so a reference checkpoint - or a
 ``torch.nn.MultiheadAttention`` state dict prefixed with ``att.`` - loads with ``strict=True``.
 
-The projections run on the package's Linear route (``functional.linear_fwd`` / ``linear_bwd``): ONE d -> 3d GEMM when
-``query is key is value``, d -> d plus d -> 2d when ``key is value``, three GEMMs otherwise.  The fused attention kernels
+``forward`` holds the checks and the mask conversion; the sublayer itself - projections, fused attention, out-projection and the
+backward through all three - is ``functional.attention_sublayer``, the one a decoder layer runs too, here as one autograd node over
+(query, key, value) (``functional.node``).  The projections run on the package's Linear route (``functional.linear_fwd`` /
+``linear_bwd``): ONE d -> 3d GEMM when ``query is key is value``, d -> d plus d -> 2d when ``key is value``, three GEMMs otherwise.  The fused attention kernels
 (csrc/attention.hip) read q / k / v through strides out of the packed projection outputs and write their gradients into the packed
 gradient buffer; no (B, H, L, S) tensor exists in the training path.  GPU only; computes in the dtype of ``query`` (float32 or
 bfloat16, like ``nnet.linear.Linear``).
@@ -13,8 +15,6 @@ bfloat16, like ``nnet.linear.Linear``).
 Deviations, all stated: a query row whose keys are all masked yields zeros (torch: NaN); the returned attention weights are
 DETACHED (no gradient flows through them; upstream's do carry one, nothing in the recipes uses it); ``forward`` takes an extra
 ``causal=False`` keyword that stands for the (L, L) look-ahead mask without building it."""
-import math
-
 import torch
 from torch import nn
 
@@ -35,23 +35,6 @@ class _AttParams(nn.Module):
         nn.init.xavier_uniform_(self.in_proj_weight)
         if bias:
             nn.init.zeros_(self.out_proj.bias)
-
-
-class _MhaFn(torch.autograd.Function):
-    """(query, key, value) -> out through a (forward, backward-closure) pair, like functional._BlockFn with three activations in.
-    Parameter gradients are accumulated into ``param.grad`` by the kernels inside the closure."""
-
-    @staticmethod
-    def forward(ctx, run, query, key, value, *params):
-        out, ctx.bwd = run(True)
-        ctx.n = len(params)
-        return out
-
-    @staticmethod
-    def backward(ctx, dy):
-        dq, dk, dv = ctx.bwd(dy)
-        F.flush_deferred()
-        return (None, dq, dk, dv) + (None,) * ctx.n
 
 
 def _rows(x):
@@ -100,7 +83,7 @@ class MultiheadAttention(nn.Module):
         if not (query.is_cuda and key.is_cuda and value.is_cuda):
             raise RuntimeError(ops.NO_CPU)
         B, Lq, d = query.shape
-        S, H, D = key.shape[1], self.nhead, self.head_dim
+        S, H = key.shape[1], self.nhead
         assert d == self.d_model and key.shape[2] == d
         if attn_mask is not None and tuple(attn_mask.shape) != (Lq, S):
             raise ValueError(f"attn_mask must be ({Lq}, {S}), got {tuple(attn_mask.shape)}")
@@ -108,79 +91,26 @@ class MultiheadAttention(nn.Module):
         pad = F.key_pad_u8(key_padding_mask, B, S, query.device)
         p = self.dropout if self.training else 0.0
         seed = ops.new_dropout_seed() if p > 0.0 else 0
-        scale = 1.0 / math.sqrt(D)
-        Wi, bi, Wo, bo = self.att.in_proj_weight, self.att.in_proj_bias, self.att.out_proj.weight, self.att.out_proj.bias
-        self_attn, kv_same = (query is key and key is value), key is value
-        dtype, dev = query.dtype, query.device
-        kept = {}
+        att, inputs, kept = self.att, (query, key, value), []
 
-        def run(need_bwd):
-            Wc, Woc = F.wcast(Wi, dtype), F.wcast(Wo, dtype)
-            bd = bi.detach() if bi is not None else None
-
-            def bsl(lo, hi):
-                return bd[lo * d:hi * d] if bd is not None else None
+        def run(need):
             xq = _rows(query)
-            if self_attn:
-                xk = xv = xq
-                qkv, _ = F.linear_fwd(xq, Wc, bd)
-                p5 = qkv.view(B, Lq, 3, H, D)
-                q, k, v = p5[:, :, 0], p5[:, :, 1], p5[:, :, 2]
-            elif kv_same:
-                xk = xv = _rows(key)
-                q = F.linear_fwd(xq, Wc[:d], bsl(0, 1))[0].view(B, Lq, H, D)
-                kv, _ = F.linear_fwd(xk, Wc[d:], bsl(1, 3))
-                p5 = kv.view(B, S, 2, H, D)
-                k, v = p5[:, :, 0], p5[:, :, 1]
+            if query is key and key is value:
+                xk = xv = None
             else:
-                xk, xv = _rows(key), _rows(value)
-                q = F.linear_fwd(xq, Wc[:d], bsl(0, 1))[0].view(B, Lq, H, D)
-                k = F.linear_fwd(xk, Wc[d:2 * d], bsl(1, 2))[0].view(B, S, H, D)
-                v = F.linear_fwd(xv, Wc[2 * d:], bsl(2, 3))[0].view(B, S, H, D)
-            o, lse = ops.attention_fwd(q, k, v, bias, pad, causal, scale, p, seed)
-            o2 = o.view(B * Lq, d)
-            out, _ = F.linear_fwd(o2, Woc, bo.detach() if bo is not None else None)
-            kept["qk"] = (q, k, lse)
-            if not need_bwd:
+                xk = _rows(key)
+                xv = None if key is value else _rows(value)
+            out, bwd2, k = F.attention_sublayer(att, H, xq, xk, xv, B, Lq, S, bias, pad, causal, p, seed=seed, need=need,
+                                                need_dx=[t.requires_grad for t in inputs])
+            kept.append(k)
+            if not need:
                 return out.view(B, Lq, d), None
 
             def bwd(dy):
-                do2, _ = F.linear_bwd(_rows(dy), o2, Woc, None, ops.L.ACT_NONE, None, 1.0, F.gacc(Wo), F.gacc(bo))
-                do = do2.view(B, Lq, H, D)
-                gW, gb = F.gacc(Wi), F.gacc(bi)
-
-                def gsl(g, lo, hi):
-                    return g[lo * d:hi * d] if g is not None else None
-                nq, nk, nv = query.requires_grad, key.requires_grad, value.requires_grad
-                if self_attn:
-                    g5 = torch.empty((B, Lq, 3, H, D), dtype=dtype, device=dev)
-                    ops.attention_bwd(do, q, k, v, o, lse, bias, pad, causal, scale, p, seed, dq=g5[:, :, 0], dk=g5[:, :, 1], dv=g5[:, :, 2])
-                    dx, _ = F.linear_bwd(g5.view(B * Lq, 3 * d), xq, Wc, None, ops.L.ACT_NONE, None, 1.0, gW, gb, need_dx=nq)
-                    return (dx.view(B, Lq, d) if dx is not None else None), None, None
-                dq = torch.empty((B, Lq, H, D), dtype=dtype, device=dev)
-                if kv_same:
-                    g5 = torch.empty((B, S, 2, H, D), dtype=dtype, device=dev)
-                    ops.attention_bwd(do, q, k, v, o, lse, bias, pad, causal, scale, p, seed, dq=dq, dk=g5[:, :, 0], dv=g5[:, :, 1])
-                    dxq, _ = F.linear_bwd(dq.view(B * Lq, d), xq, Wc[:d], None, ops.L.ACT_NONE, None, 1.0, gsl(gW, 0, 1), gsl(gb, 0, 1), need_dx=nq)
-                    dxk, _ = F.linear_bwd(g5.view(B * S, 2 * d), xk, Wc[d:], None, ops.L.ACT_NONE, None, 1.0, gsl(gW, 1, 3), gsl(gb, 1, 3), need_dx=nk or nv)
-                    return (dxq.view(B, Lq, d) if dxq is not None else None), (dxk.view(B, S, d) if dxk is not None else None), None
-                dk = torch.empty((B, S, H, D), dtype=dtype, device=dev)
-                dv = torch.empty((B, S, H, D), dtype=dtype, device=dev)
-                ops.attention_bwd(do, q, k, v, o, lse, bias, pad, causal, scale, p, seed, dq=dq, dk=dk, dv=dv)
-                dxq, _ = F.linear_bwd(dq.view(B * Lq, d), xq, Wc[:d], None, ops.L.ACT_NONE, None, 1.0, gsl(gW, 0, 1), gsl(gb, 0, 1), need_dx=nq)
-                dxk, _ = F.linear_bwd(dk.view(B * S, d), xk, Wc[d:2 * d], None, ops.L.ACT_NONE, None, 1.0, gsl(gW, 1, 2), gsl(gb, 1, 2), need_dx=nk)
-                dxv, _ = F.linear_bwd(dv.view(B * S, d), xv, Wc[2 * d:], None, ops.L.ACT_NONE, None, 1.0, gsl(gW, 2, 3), gsl(gb, 2, 3), need_dx=nv)
-                return tuple(g.view(shape) if g is not None else None
-                             for g, shape in ((dxq, (B, Lq, d)), (dxk, (B, S, d)), (dxv, (B, S, d))))
+                return tuple(g.view(t.shape) if g is not None else None for g, t in zip(bwd2(_rows(dy)), inputs))
             return out.view(B, Lq, d), bwd
 
-        params = [t for t in (Wi, bi, Wo, bo) if t is not None]
-        need = torch.is_grad_enabled() and (query.requires_grad or key.requires_grad or value.requires_grad
-                                            or any(t.requires_grad for t in params))
-        out = _MhaFn.apply(run, query, key, value, *params) if need else run(False)[0]
+        out = F.node(run, inputs, (att.in_proj_weight, att.in_proj_bias, att.out_proj.weight, att.out_proj.bias))
         if not return_attn_weights:
             return out
-        q, k, lse = kept["qk"]
-        with torch.no_grad():
-            weights = ops.attention_weights(q, k, lse, bias, pad, causal, scale, p, seed)
-        return out, weights
+        return out, F.attention_sublayer_weights(kept[0])

@@ -87,3 +87,31 @@ def autocast_reference_layer(name):
 def autocast_floor_layer(name):
     """(forward, dL/dx, worst parameter-gradient) max-rel error of the reference's own bf16 autocast against the float32 golden."""
     return autocast_reference_layer(name)["floor"]
+
+
+def pattern(rows, cols, mul, mod, div, emin, espan):
+    """x[i, j] = ((mul[0] i + mul[1] j) % mod - mod // 2) / div * 2^((7 i + 5 j) % espan + emin) in float64: an integer of at most
+    six bits times a power of two, exact in bf16; the spread makes a float32 sum round, so that its order shows in the bits."""
+    i = torch.arange(rows, dtype=torch.int64).view(-1, 1)
+    j = torch.arange(cols, dtype=torch.int64).view(1, -1)
+    x = ((mul[0] * i + mul[1] * j) % mod - mod // 2).double() / div
+    return x * torch.exp2(((7 * i + 5 * j) % espan + emin).double())
+
+
+def describe(v):
+    """A launch argument as a short string: tensors by dtype, shape, leading dimension (when not the width) and storage offset."""
+    if isinstance(v, torch.Tensor):
+        s = {torch.bfloat16: "bf16", torch.float32: "f32", torch.uint8: "u8", torch.int64: "i64", torch.int32: "i32",
+             torch.bool: "bool"}[v.dtype] + "[" + "x".join(str(n) for n in v.shape) + "]"
+        if v.dim() == 2 and v.shape[0] > 1 and v.stride(0) != v.shape[1]:
+            s += f"/ld{v.stride(0)}"
+        if v.storage_offset():
+            s += f"+{v.storage_offset()}"
+        return s
+    if isinstance(v, (tuple, list)):
+        return "(" + ",".join(describe(x) for x in v) + ")"
+    if isinstance(v, float):
+        return f"{v:g}"
+    if isinstance(v, dict):
+        return "{" + ",".join(f"{k}={describe(x)}" for k, x in sorted(v.items())) + "}"
+    return str(v)

@@ -16,29 +16,11 @@ from summarymixing_amd import functional as F
 from summarymixing_amd import ops
 from summarymixing_amd import sequence_parallel as SP
 from summarymixing_amd.nnet.summary_mixing import SummaryMixing
+from tests._util import describe as _d
 
 BF = torch.bfloat16
 B, T, D = 4, 48, 64                  # 192 frames: a shape smx_pool_bcast accepts; 48 = 6 chunks of 8
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "cell_routes.json")
-
-
-def _d(v):
-    """A launch argument as a short string: tensors by dtype, shape, leading dimension (when not the width) and storage offset."""
-    if isinstance(v, torch.Tensor):
-        s = {torch.bfloat16: "bf16", torch.float32: "f32", torch.uint8: "u8", torch.int64: "i64", torch.int32: "i32",
-             torch.bool: "bool"}[v.dtype] + "[" + "x".join(str(n) for n in v.shape) + "]"
-        if v.dim() == 2 and v.shape[0] > 1 and v.stride(0) != v.shape[1]:
-            s += f"/ld{v.stride(0)}"
-        if v.storage_offset():
-            s += f"+{v.storage_offset()}"
-        return s
-    if isinstance(v, (tuple, list)):
-        return "(" + ",".join(_d(x) for x in v) + ")"
-    if isinstance(v, float):
-        return f"{v:g}"
-    if isinstance(v, dict):
-        return "{" + ",".join(f"{k}={_d(x)}" for k, x in sorted(v.items())) + "}"
-    return str(v)
 
 
 _EPI_DEFAULTS = {"c0_mode": L.C0_NONE, "c0_div": 0, "act": L.ACT_NONE, "out_mode": L.OUT_T, "alpha": 1.0, "bias_batch_stride": 0,

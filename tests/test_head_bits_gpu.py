@@ -17,6 +17,9 @@ import sys
 import pytest
 import torch
 
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))      # (for --write: run as a script)
+from tests._util import pattern as _pattern  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "head_bits.json")
@@ -24,15 +27,6 @@ DTYPES = {"f32": torch.float32, "bf16": torch.bfloat16}
 NAN, INF = float("nan"), float("inf")
 ROWS = 9                                                 # three blocks of four waves: the last block has one live wave
 TIE, NEG, ONE_NAN, ALL_NAN = 2, 4, 6, 7                  # the special rows of a row-pass input
-
-
-def _pattern(rows, cols, mul, mod, div, emin, espan):
-    """x[i, j] = ((mul[0] i + mul[1] j) % mod - mod // 2) / div * 2^((7 i + 5 j) % espan + emin) in float64: an integer of at most
-    six bits times a power of two, exact in bf16; the spread makes a float32 sum round, so that its order shows in the bits."""
-    i = torch.arange(rows, dtype=torch.int64).view(-1, 1)
-    j = torch.arange(cols, dtype=torch.int64).view(1, -1)
-    x = ((mul[0] * i + mul[1] * j) % mod - mod // 2).double() / div
-    return x * torch.exp2(((7 * i + 5 * j) % espan + emin).double())
 
 
 def _digest(t):
@@ -222,7 +216,6 @@ def test_fixture_sees_the_fp32_rounding_of_the_head_product(golden):
 if __name__ == "__main__":
     if len(sys.argv) != 3 or sys.argv[1] != "--write":
         sys.exit("usage: python tests/test_head_bits_gpu.py --write <path>")
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     with open(sys.argv[2], "w") as f:
         json.dump({name: _run(name) for name in sorted(CASES)}, f, indent=0, sort_keys=True)
         f.write("\n")
