@@ -1010,6 +1010,74 @@ int smx_tgt_embed_fwd(int out_dtype, const int32_t* tok, const float* table, int
 int smx_tgt_embed_bwd(int dy_dtype, const int32_t* tok, const void* dY, int64_t lddy, float* gTable, int64_t ldg, int rows, int V, int D,
                       int pad_idx, void* stream);
 
+/* ---- one KV-cached decoding step of the seq2seq decoder (csrc/attn_step.hip) ----------------------------------------------------------
+ * What a greedy / teacher-forced search over [TransformerASR.decode, seq_lin] needs per new token instead of running the whole prefix
+ * again.  Every position is a device counter the kernels read and advance, so the host issues identical launches at every step.
+ * smx_attn_step: one query row per (batch row, head) over a cache.  q, k_new, v_new, o are (B, H, D) (smx_attn_operand; sr is not
+ *   read), K and V the caches (B, cap, H, D); sd must be 1 and the base and every stride read 16-byte aligned (SMX_EUNSUPPORTED
+ *   otherwise), so q / k_new / v_new may be views into the packed (B, 3, H, D) in-projection output of the step and K / V the two
+ *   halves of a packed (B, cap, 2, H, D) cache.  n_keys (B) int32 ON THE DEVICE: the number of visible keys of row b, n; NULL: cap.
+ *   With k_new / v_new (self-attention) the call first stores k_new[b], v_new[b] into cache slot n - 1, then attends over slots [0, n);
+ *   without (both NULL: cross-attention over the layer's projected memory) it only attends.
+ *     o[b,h,:] = softmax_j(scale <q[b,h], K[b,j,h]>) V[b,j,h],  j < n;  fp32 scores, softmax and accumulators, row maximum subtracted.
+ *   n outside [1, cap]: o = 0 for that row and nothing is stored.  Slots at or beyond n are never read (they may hold anything), nor
+ *   is slot n - 1 of a self-attention call (its key comes from k_new).  F32 or BF16, D in {64, 128, 256, 512}, cap <= 65536 (other:
+ *   SMX_EUNSUPPORTED).  Inference only: no dropout, bias, mask or weights output.
+ *   Structure: 16-byte loads of K / V from global memory into registers, no LDS tiles, no MFMA; the keys of a row are cut into
+ *   plan.splits contiguous chunks of plan.chunk keys (a function of cap alone), one 4-wave workgroup each; the partial (max, sum,
+ *   accumulator) triples meet in a fixed order - lane groups, waves, then chunks (a second launch when splits > 1, through
+ *   `workspace`, plan.workspace_bytes, 16-byte aligned).  No atomics: two runs agree bit for bit, and row b's output depends neither on
+ *   B nor on the other rows.
+ * smx_attn_step_plan_query: that geometry for the descriptor's sizes and dtype; needs no GPU and no pointers (those present are checked).
+ * smx_s2s_embed_step: Y[b ldy + c] = table[tok[b] ldt + c] * sqrt(D) + pe[pos[b] ldpe + c] in out_dtype (smx_tgt_embed_fwd's formula
+ *   and conventions: a token outside [0, V) reads as a zero row; pe NULL adds nothing), then pos[b] += 1 for rows with done[b] == 0:
+ *   afterwards pos[b] is the self-attention n_keys[b] of the step.  A row with pos[b] outside [0, max_pos) reads no positional row, is
+ *   not advanced and gets done[b] = 1.  D and the leading dimensions multiples of 8 elements, 16-byte aligned bases.
+ * smx_s2s_select: per row b of the logits z (B, V) with done[b] == 0, at step n = n_tok[b]:
+ *     k = the lowest index of the row maximum (a NaN never wins; -1 when no entry is a number), eos left out while n < min_steps;
+ *         forced[b] instead when `forced` is given (teacher forcing / scoring a given hypothesis);
+ *     lp = (z[k] - max z) inv_temp - log sum_j exp((z[j] - max z) inv_temp)   (one fp64 inv_temp throughout; fp32 expf of the fp64
+ *         exponent, fp32 per-lane sums, the 64 lanes and the final expression in fp64; NaN when the row holds one, -inf for a forced
+ *         token outside [0, V));
+ *     tokens[b, n] = k, logp_tok[b, n] = lp, score[b] += lp, n_tok[b] = n + 1;  done[b] = 1 when k == eos or n_tok[b] == cap;
+ *     tok[b] = k (the next step's input).  A row with done[b] != 0 changes nothing.  One wave per row, no atomics.
+ * All: SMX_EINVAL for a NULL pointer the call needs, sizes < 1, a leading dimension smaller than its row, inv_temp <= 0.  Nothing
+ * allocates or synchronises with the host: capturable. */
+typedef struct smx_attn_step_args {
+  int32_t dtype, pad_;
+  smx_attn_operand q, k_new, v_new, K, V, o;
+  const int32_t* n_keys;   /* (B) device, or NULL */
+  void* workspace;         /* plan.workspace_bytes, or NULL when plan.splits == 1 */
+  int32_t B, H, D, cap;
+  float scale;
+  int32_t pad2_;
+} smx_attn_step_args;      /* 288 bytes */
+typedef struct smx_attn_step_plan {
+  int32_t lanes_per_key, keys_per_wave, waves, threads;
+  int32_t splits, chunk, launches, lds_bytes;
+  int32_t grid[3];
+  int32_t pad_;
+  int64_t workspace_bytes;
+} smx_attn_step_plan;      /* 56 bytes */
+typedef struct smx_s2s_select_args {
+  const void* logits;      /* (B, V) in dtype */
+  int64_t ldz;
+  const int32_t* forced;   /* (B) or NULL */
+  int32_t* tok;            /* (B) */
+  uint8_t* done;           /* (B) */
+  int32_t* n_tok;          /* (B) */
+  float* score;            /* (B) */
+  int32_t* tokens;         /* (B, cap) */
+  float* logp_tok;         /* (B, cap) */
+  double inv_temp;
+  int32_t dtype, B, V, cap, eos, min_steps;
+} smx_s2s_select_args;     /* 104 bytes */
+int smx_attn_step(const smx_attn_step_args* a, void* stream);
+int smx_attn_step_plan_query(const smx_attn_step_args* a, smx_attn_step_plan* plan);
+int smx_s2s_embed_step(int out_dtype, const int32_t* tok, const float* table, int64_t ldt, const float* pe, int64_t ldpe, void* Y,
+                       int64_t ldy, int32_t* pos, uint8_t* done, int B, int V, int D, int max_pos, void* stream);
+int smx_s2s_select(const smx_s2s_select_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -140,6 +140,29 @@ class AttnPlan(ctypes.Structure):
 
 ATTN_FWD, ATTN_BWD_DQ, ATTN_BWD_DKV, ATTN_WEIGHTS = 0, 1, 2, 3      # `pass` of smx_attn_plan_query
 
+
+class AttnStepArgs(ctypes.Structure):
+    """smx_attn_step_args of include/smx.h."""
+    _fields_ = [("dtype", ctypes.c_int32), ("pad_", ctypes.c_int32)] + [
+                (n, AttnOperand) for n in ("q", "k_new", "v_new", "K", "V", "o")] + [
+                ("n_keys", c_vp), ("workspace", c_vp)] + [(n, ctypes.c_int32) for n in ("B", "H", "D", "cap")] + [
+                ("scale", c_f), ("pad2_", ctypes.c_int32)]
+
+
+class AttnStepPlan(ctypes.Structure):
+    """smx_attn_step_plan of include/smx.h (smx_attn_step_plan_query)."""
+    _fields_ = [(n, ctypes.c_int32 * 3 if n == "grid" else ctypes.c_int32)
+                for n in ("lanes_per_key", "keys_per_wave", "waves", "threads", "splits", "chunk", "launches", "lds_bytes", "grid",
+                          "pad_")] + [("workspace_bytes", c_i64)]
+
+
+class S2SSelectArgs(ctypes.Structure):
+    """smx_s2s_select_args of include/smx.h."""
+    _fields_ = [("logits", c_vp), ("ldz", c_i64), ("forced", c_vp), ("tok", c_vp), ("done", c_vp), ("n_tok", c_vp), ("score", c_vp),
+                ("tokens", c_vp), ("logp_tok", c_vp), ("inv_temp", ctypes.c_double)] + [
+                (n, ctypes.c_int32) for n in ("dtype", "B", "V", "cap", "eos", "min_steps")]
+
+
 # name -> (restype, argtypes); mirrors include/smx.h one to one (tests/test_abi.py checks the export list)
 SIGNATURES = {
     "smx_version": (c_i, []),
@@ -292,6 +315,10 @@ SIGNATURES = {
     "smx_attn_plan_query": (c_i, [ctypes.POINTER(AttnArgs), c_i, ctypes.POINTER(AttnPlan)]),
     "smx_tgt_embed_fwd": (c_i, [c_i, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i, c_i, c_i, c_i, c_i, c_vp]),
     "smx_tgt_embed_bwd": (c_i, [c_i, c_vp, c_vp, c_i64, c_vp, c_i64, c_i, c_i, c_i, c_i, c_vp]),
+    "smx_attn_step": (c_i, [ctypes.POINTER(AttnStepArgs), c_vp]),
+    "smx_attn_step_plan_query": (c_i, [ctypes.POINTER(AttnStepArgs), ctypes.POINTER(AttnStepPlan)]),
+    "smx_s2s_embed_step": (c_i, [c_i, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i, c_i, c_i, c_i, c_vp]),
+    "smx_s2s_select": (c_i, [ctypes.POINTER(S2SSelectArgs), c_vp]),
 }
 
 _lib = None

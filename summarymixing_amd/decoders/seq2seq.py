@@ -1,0 +1,192 @@
+"""Greedy seq2seq decoding over ``[Transformer, seq_lin]``, the pair the Branchformer recipes hand to
+``speechbrain.decoders.S2STransformerBeamSearcher`` (recipes/*/ASR/transformer/hparams/branchformer_summarymixing.yaml,
+``valid_search`` / ``test_search``), with the whole search on the device:
+
+  one step = TransformerASR.decode_step (KV-cached: smx_s2s_embed_step, per layer smx_attn_step over the caches, csrc/attn_step.hip)
+             -> seq_lin (the package's Linear route) -> smx_s2s_select (arg-max, log-probability, append, end-of-sequence flags).
+
+Every position - the decoder position, the hypothesis length, the done flags - is a device counter the kernels read and advance, so
+the host issues the same launches at every step: ``greedy_search`` loops over them and reads the ``done`` vector (B bytes) every
+``poll_every`` steps, its only synchronisation; ``CapturedS2SGreedy`` captures ONE step as a graph - a plain chain, no parallel
+branches - and replays it in the same loop for every step of every utterance of its (B, S).
+
+``S2STransformerGreedySearcher`` and ``S2STransformerBeamSearcher`` take the recipes' constructor arguments.  Beam search
+(``beam_size > 1``), scorers (CTC / LM), ``TransformerLM`` and the beam options (eos threshold, attention shift, top-k) are not built
+and are refused by name; ``beam_size=1`` without a scorer runs the greedy search (``length_normalization`` is accepted: one hypothesis
+has nothing to rank, and the score stays the plain sum).  No parameters of their own: the modules are plain
+attributes, as SpeechBrain's searchers hold them outside the checkpointed ``modules``.  SpeechBrain's ``decoders/seq2seq.py`` is not
+part of the reference tree: the constructor arguments are the recipes', the returned tuple ``(hyps, lengths, scores, log_probs)`` is
+written from memory."""
+import collections
+
+import torch
+
+from .. import functional as F
+from .. import ops
+
+S2SGreedyResult = collections.namedtuple("S2SGreedyResult", "tokens counts scores log_probs state")
+S2SGreedyResult.__doc__ = """tokens (B, cap) int32 (entries at and beyond counts[b] are -1), counts (B) int32, scores (B) fp32 = the sum of
+the row's log_probs, log_probs (B, cap) fp32 per emitted token, state: the Transformer.DecodeState - all on the device, all views of
+the state's buffers (clone what must outlive the next search over the same state)."""
+
+
+def _check_args(bos, eos, min_steps, max_steps, temperature):
+    if max_steps < 1:
+        raise ValueError(f"seq2seq search: max_steps must be >= 1, got {max_steps}")
+    if min_steps < 0 or min_steps > max_steps:
+        raise ValueError(f"seq2seq search: need 0 <= min_steps <= max_steps, got {min_steps}, {max_steps}")
+    if not temperature > 0.0:
+        raise ValueError(f"seq2seq search: temperature must be > 0, got {temperature}")
+    if bos < 0 or eos < 0:
+        raise ValueError(f"seq2seq search: bos / eos must be token indices, got {bos}, {eos}")
+
+
+def search_step(model, seq_lin, state, eos, min_steps, inv_temp):
+    """The launches of one step on the current stream: decode_step on state.tok -> seq_lin -> smx_s2s_select into the state.  -> the
+    logits (B, V) the selection read."""
+    pred = model.decode_step(state.tok, state)
+    W, b = seq_lin.w.weight, seq_lin.w.bias
+    logits, _ = F.linear_fwd(pred, F.wcast(W, pred.dtype), b.detach() if b is not None else None)
+    ops.s2s_select(logits, state.tok, state.done, state.n_tok, state.score, state.tokens, state.logp_tok, eos, min_steps, inv_temp)
+    return logits
+
+
+def _poll_loop(step, state, max_steps, poll_every):
+    """step() max_steps times, or until the done vector, read every poll_every steps, is all set (poll_every=0: never read)."""
+    for i in range(max_steps):
+        step()
+        if poll_every and (i + 1) % poll_every == 0 and i + 1 < max_steps and bool(state.done.all()):
+            break
+
+
+def _begin(model, encoder_out, enc_len, bos, max_steps, state):
+    if not encoder_out.is_cuda:
+        raise RuntimeError(ops.NO_CPU)
+    state = model.make_decode_state(encoder_out, enc_len, max_steps, state=state)
+    if state.cap != max_steps:
+        raise ValueError(f"seq2seq search: max_steps {max_steps} exceeds the positional table ({state.cap} positions)")
+    state.tok.fill_(bos)
+    return state
+
+
+def _result(state):
+    return S2SGreedyResult(state.tokens, state.n_tok, state.score, state.logp_tok, state)
+
+
+@torch.no_grad()
+def greedy_search(model, seq_lin, encoder_out, enc_len, bos, eos, min_steps, max_steps, temperature=1.0, state=None, poll_every=8):
+    """Greedy search of model (a TransformerASR in eval mode) and seq_lin (nnet.linear.Linear d -> V) over encoder_out (B, S, d) with
+    the absolute encoder lengths enc_len (B) or None: from bos, at most max_steps tokens per row, a row ends with its first eos (which
+    is stored and counted), eos cannot be chosen before min_steps.  state: a DecodeState of this (B, S, max_steps, dtype) to reuse.
+    -> S2SGreedyResult."""
+    _check_args(bos, eos, min_steps, max_steps, temperature)
+    state = _begin(model, encoder_out, enc_len, bos, max_steps, state)
+    inv_temp = 1.0 / float(temperature)
+    _poll_loop(lambda: search_step(model, seq_lin, state, eos, min_steps, inv_temp), state, max_steps, poll_every)
+    return _result(state)
+
+
+class CapturedS2SGreedy:
+    """greedy_search with ONE step captured as a graph: every position lives on the device, so the same graph serves every step and
+    every utterance of its (B, S, max_steps, dtype).  The captured step is search_step - a plain chain of launches on one stream.
+    search(encoder_out, enc_len) refills the state in place (eager: the cross-attention projections of the new utterance) and replays
+    the graph in greedy_search's polling loop; its result equals greedy_search's bit for bit."""
+
+    def __init__(self, model, seq_lin, B, S, max_steps, dtype, bos, eos, min_steps=0, temperature=1.0, device="cuda"):
+        _check_args(bos, eos, min_steps, max_steps, temperature)
+        self.model, self.seq_lin, self.bos, self.max_steps = model, seq_lin, int(bos), int(max_steps)
+        d = model.custom_tgt_module.layers[0].d_model
+        eos, min_steps, inv_temp = int(eos), int(min_steps), 1.0 / float(temperature)
+        with torch.no_grad():
+            mem = torch.zeros((B, S, d), dtype=dtype, device=device)
+            self.state = _begin(model, mem, None, self.bos, self.max_steps, None)
+
+            def run():
+                search_step(model, seq_lin, self.state, eos, min_steps, inv_temp)
+            s = torch.cuda.Stream(device=device)
+            s.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(s):
+                run()                                         # warm-up: weight casts and packed images exist before the capture
+            torch.cuda.current_stream().wait_stream(s)
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph, stream=s):
+                run()
+            self.state.reset()
+
+    @torch.no_grad()
+    def search(self, encoder_out, enc_len=None, poll_every=8):
+        state = _begin(self.model, encoder_out, enc_len, self.bos, self.max_steps, self.state)
+        _poll_loop(self.graph.replay, state, self.max_steps, poll_every)
+        return _result(state)
+
+
+# beam-search options and the one value of each that leaves the greedy search what it is
+_BEAM_ONLY = {"topk": 1, "using_eos_threshold": False, "eos_threshold": 1.5, "using_max_attn_shift": False, "max_attn_shift": 60,
+              "minus_inf": -1e20}
+
+
+class S2STransformerGreedySearcher(torch.nn.Module):
+    """speechbrain.decoders.S2STransformerGreedySearcher(modules=[model, seq_lin], bos_index, eos_index, min_decode_ratio,
+    max_decode_ratio, temperature): forward(enc_states (B, S, d), wav_len (B) relative) -> (hyps: B lists of ints up to and excluding
+    the first eos, lengths (B) of them, scores (B) = the summed log-probabilities of the emitted tokens (eos included), log_probs
+    (B, max_steps) per emitted token) - the last three tensors on the host, from the ONE copy at the end; the tuple's layout is written
+    from memory (module docstring).  max_steps = int(S * max_decode_ratio), min_steps = int(S * min_decode_ratio), enc_len =
+    round(S * wav_len)."""
+
+    def __init__(self, modules, bos_index, eos_index, min_decode_ratio, max_decode_ratio, temperature=1.0):
+        super().__init__()
+        mods = list(modules)
+        if len(mods) != 2:
+            raise NotImplementedError("S2STransformerGreedySearcher: modules = [Transformer, seq_lin] (the Branchformer recipes') is what "
+                                      f"the kernels cover, got {len(mods)} modules")
+        if not temperature > 0.0:
+            raise ValueError(f"S2STransformerGreedySearcher: temperature must be > 0, got {temperature}")
+        if not 0.0 <= min_decode_ratio <= max_decode_ratio:
+            raise ValueError(f"S2STransformerGreedySearcher: need 0 <= min_decode_ratio <= max_decode_ratio, got {min_decode_ratio}, "
+                             f"{max_decode_ratio}")
+        # plain attributes, not registered submodules: the searcher adds nothing to any state_dict
+        object.__setattr__(self, "model", mods[0])
+        object.__setattr__(self, "fc", mods[1])
+        self.bos_index, self.eos_index = int(bos_index), int(eos_index)
+        self.min_decode_ratio, self.max_decode_ratio, self.temperature = float(min_decode_ratio), float(max_decode_ratio), float(temperature)
+
+    def forward(self, enc_states, wav_len):
+        if not enc_states.is_cuda:
+            raise RuntimeError(ops.NO_CPU)
+        B, S, _ = enc_states.shape
+        max_steps, min_steps = int(S * self.max_decode_ratio), int(S * self.min_decode_ratio)
+        enc_len = None if wav_len is None else torch.round(wav_len.to(enc_states.device) * S)
+        r = greedy_search(self.model, self.fc, enc_states, enc_len, self.bos_index, self.eos_index, min_steps, max_steps, self.temperature)
+        cap = r.tokens.shape[1]
+        packed = torch.cat([r.tokens.double(), r.log_probs.double(), r.counts.view(B, 1).double(), r.scores.view(B, 1).double()], 1).cpu()
+        tokens, log_probs = packed[:, :cap].long(), packed[:, cap:2 * cap].float()          # the one host copy, taken apart
+        counts, scores = packed[:, 2 * cap].long(), packed[:, 2 * cap + 1].float()
+        hyps = []
+        for b in range(B):
+            h = [int(k) for k in tokens[b, :int(counts[b])]]
+            hyps.append(h[:h.index(self.eos_index)] if self.eos_index in h else h)
+        return hyps, torch.tensor([len(h) for h in hyps]), scores, log_probs
+
+
+class S2STransformerBeamSearcher(S2STransformerGreedySearcher):
+    """speechbrain.decoders.S2STransformerBeamSearcher with the recipes' arguments.  beam_size=1 without a scorer is the greedy search
+    above; beam search proper, a scorer (CTC / LM rescoring) and the beam options are not built and are refused by name."""
+
+    def __init__(self, modules, bos_index, eos_index, min_decode_ratio, max_decode_ratio, beam_size, scorer=None, temperature=1.0,
+                 **beam_options):
+        if scorer is not None:
+            raise NotImplementedError("S2STransformerBeamSearcher: a scorer (CTC / LM scoring) belongs to beam search, which is not built "
+                                      "(greedy decoding, beam_size=1 without a scorer, is)")
+        if beam_size != 1:
+            raise NotImplementedError(f"S2STransformerBeamSearcher: beam search (beam_size={beam_size}) is not built; beam_size=1 runs "
+                                      "greedy decoding")
+        # length_normalization (the recipes pass True) ranks the hypotheses of a beam: with one hypothesis there is nothing to rank, and
+        # the score returned stays the plain sum of the log-probabilities either way
+        beam_options.pop("length_normalization", None)
+        for k, v in beam_options.items():
+            if k not in _BEAM_ONLY:
+                raise TypeError(f"S2STransformerBeamSearcher: unknown argument {k!r}")
+            if v != _BEAM_ONLY[k]:
+                raise NotImplementedError(f"S2STransformerBeamSearcher: {k}={v!r} is a beam-search option, which is not built")
+        super().__init__(modules, bos_index, eos_index, min_decode_ratio, max_decode_ratio, temperature)
+        self.beam_size = 1

@@ -1643,6 +1643,38 @@ def scaled_dot_product_attention(q, k, v, *, attn_bias=None, key_padding_mask=No
     return _SdpaFn.apply(q, k, v, attn_bias, pad, bool(causal), float(dropout_p), seed or 0, scale)
 
 
+def attention_in_proj(att, x, lo, hi, out=None):
+    """Thirds [lo, hi) of a MultiheadAttention's packed in-projection on the rows x (N, d) -> (N, (hi - lo) d) in x's dtype: (0, 3) the
+    d -> 3d self-attention GEMM, (0, 1) the query Linear, (1, 3) the d -> 2d key / value Linear over a memory.  ONE GEMM on the
+    matching rows of in_proj_weight / in_proj_bias; what attention_sublayer runs per projection and the decoding state runs once per
+    utterance on the encoder output."""
+    Wi, bi = att.in_proj_weight, att.in_proj_bias
+    d = Wi.shape[1]
+    Wc = wcast(Wi, x.dtype)
+    bd = bi.detach() if bi is not None else None
+    if hi - lo != 3:
+        Wc, bd = Wc[lo * d:hi * d], (bd[lo * d:hi * d] if bd is not None else None)
+    return linear_fwd(x, Wc, bd, out=out)[0]
+
+
+def attention_step_sublayer(att, H, x, kv, n_keys, res, self_attn, out=None, workspace=None):
+    """The attention sublayer of ONE decoding position over a cache, inference only: x (B, d) rows, kv the packed cache (B, cap, 2, H, D)
+    - a layer's self-attention keys / values so far (self_attn: the d -> 3d GEMM on x, whose k / v rows smx_attn_step stores at slot
+    n_keys - 1 before it attends) or its projected memory (cross-attention: the d -> d query Linear alone) - and n_keys (B) int32 on the
+    device.  out (B, H, D) / workspace: the attention launch's output and split workspace when the caller owns them (ops.attention_step).
+    -> res + out_proj(attention), the out-projection's residual epilogue as in attention_sublayer."""
+    Wo, bo = att.out_proj.weight, att.out_proj.bias
+    B, d = x.shape
+    D = d // H
+    if self_attn:
+        q, kn, vn = attention_in_proj(att, x, 0, 3).view(B, 3, H, D).unbind(1)
+    else:
+        q, kn, vn = attention_in_proj(att, x, 0, 1).view(B, H, D), None, None
+    K, V = kv.unbind(2)
+    o = ops.attention_step(q, K, V, n_keys, kn, vn, scale=1.0 / math.sqrt(D), out=out, workspace=workspace)
+    return linear_fwd(o.view(B, d), wcast(Wo, x.dtype), bo.detach() if bo is not None else None, res=res)[0]
+
+
 def attention_sublayer(att, H, xq, xk, xv, B, Lq, S, bias, pad, causal, p_attn, *, seed=None, res=None, drop=None, need=True,
                        need_dx=(True, True, True)):
     """The attention sublayer of nnet.attention.MultiheadAttention and of a decoder layer, on 2-D row views:
@@ -1660,7 +1692,6 @@ def attention_sublayer(att, H, xq, xk, xv, B, Lq, S, bias, pad, causal, p_attn, 
     dtype, dev = xq.dtype, xq.device
     scale = 1.0 / math.sqrt(D)
     Wc, Woc = wcast(Wi, dtype), wcast(Wo, dtype)
-    bd = bi.detach() if bi is not None else None
     if seed is None:
         seed = ops.new_dropout_seed() if p_attn > 0.0 else 0
     # (input, first and one-past-last third of in_proj, rows per utterance) per projection GEMM
@@ -1673,8 +1704,7 @@ def attention_sublayer(att, H, xq, xk, xv, B, Lq, S, bias, pad, causal, p_attn, 
 
     def thirds(t, lo, hi):
         return t if (t is None or hi - lo == 3) else t[lo * d:hi * d]
-    q, k, v = (t for x, lo, hi, n in segs
-               for t in linear_fwd(x, thirds(Wc, lo, hi), thirds(bd, lo, hi))[0].view(B, n, hi - lo, H, D).unbind(2))
+    q, k, v = (t for x, lo, hi, n in segs for t in attention_in_proj(att, x, lo, hi).view(B, n, hi - lo, H, D).unbind(2))
     o, lse = ops.attention_fwd(q, k, v, bias, pad, causal, scale, p_attn, seed)
     o2 = o.view(B * Lq, d)
     out, _ = linear_fwd(o2, Woc, bo.detach() if bo is not None else None, res=res, drop=drop)

@@ -17,6 +17,9 @@ Residual stream: functional.stream_dtype - float32 for a bf16 model with normali
 normalize_before=False the LayerNorm output IS the stream and stays in the compute dtype.  ``memory`` is cast to the compute dtype
 once per forward.  GPU only (a CPU tensor raises ops.NO_CPU).
 
+Decoding one position at a time (TransformerDecoder.step, TransformerDecoderLayer._step, DecodeState): the same sublayers at inference,
+the two attention launches replaced by smx_attn_step over a self-attention cache and the once-projected memory.
+
 Deviations, all stated: a query row whose keys are all masked yields zeros (torch: NaN); returned attention weights are detached;
 ``tgt_mask`` may be the module constant LOOKAHEAD instead of the dense matrix (what TransformerASR.forward / decode pass); the
 embedding maps a token outside [0, V) to a zero row where torch raises."""
@@ -204,6 +207,31 @@ class TransformerDecoderLayer(nn.Module):
             return y, bwd, ks, kc
         return run
 
+    def _step(self, x, compute, self_kv, cross_kv, pos, mem_len, attn_out=None, attn_ws=None):
+        """ONE decoding position, inference only: x (B, d) stream rows -> the layer's output rows.  _run's sublayers at need=False in
+        the same order and dtypes, the two smx_attn_fwd calls replaced by smx_attn_step over the layer's caches (self_kv (B, cap, 2,
+        H, D), the keys / values so far, slot pos - 1 written here; cross_kv (B, S, 2, H, D), the projected memory); no weights.
+        attn_out / attn_ws: the state's attention output and workspace, shared by the launches of a step (each is consumed by its
+        out-projection before the next attention writes it: one stream)."""
+        kw = {"out": attn_out, "workspace": attn_ws}
+        n1, n2, n3 = self.norm1.norm, self.norm2.norm, self.norm3.norm
+        f0, f3 = self.pos_ffn.ffn[0], self.pos_ffn.ffn[3]
+        sa, ca, H = self.self_attn.att, self.multihead_attn.att, self.nhead
+        if self.normalize_before:
+            h1, _ = F.ln_fwd(x, n1.weight, n1.bias, n1.eps, False, out_dtype=compute)
+            x1 = F.attention_step_sublayer(sa, H, h1, self_kv, pos, x, True, **kw)
+            h2, _ = F.ln_fwd(x1, n2.weight, n2.bias, n2.eps, False, out_dtype=compute)
+            x2 = F.attention_step_sublayer(ca, H, h2, cross_kv, mem_len, x1, False, **kw)
+            P = {"ln_w": n3.weight, "ln_b": n3.bias, "W1": f0.weight, "b1": f0.bias, "W2": f3.weight, "b2": f3.bias}
+            return F.ffn_module_fwd(x2, P, self.act, False, compute, alpha=1.0, p=0.0, eps=n3.eps)[0]
+        t1 = F.attention_step_sublayer(sa, H, x, self_kv, pos, x, True, **kw)
+        x1, _ = F.ln_fwd(t1, n1.weight, n1.bias, n1.eps, False)
+        t2 = F.attention_step_sublayer(ca, H, x1, cross_kv, mem_len, x1, False, **kw)
+        x2, _ = F.ln_fwd(t2, n2.weight, n2.bias, n2.eps, False)
+        a, _ = F.linear_fwd(x2, F.wcast(f0.weight, compute), f0.bias, self.act, None, wparam=f0.weight)
+        t3, _ = F.linear_fwd(a, F.wcast(f3.weight, compute), f3.bias, L.ACT_NONE, None, res=x2, wparam=f3.weight)
+        return F.ln_fwd(t3, n3.weight, n3.bias, n3.eps, False)[0]
+
     def forward(self, tgt, memory, tgt_mask=None, memory_mask=None, tgt_key_padding_mask=None, memory_key_padding_mask=None,
                 pos_embs_tgt=None, pos_embs_src=None):
         """-> (out (B, U, d) in tgt's dtype, self-attention weights (B, U, U), cross-attention weights (B, U, S)), Transformer.py:806-859."""
@@ -306,3 +334,46 @@ class TransformerDecoder(nn.Module):
         (TransformerASR.forward asks for none, decode for the last layer's cross-attention)."""
         return _decode_stack(list(self.layers), self.norm.norm, tgt, memory, tgt_mask, memory_mask, tgt_key_padding_mask,
                              memory_key_padding_mask, pos_embs_tgt, pos_embs_src, _weights)
+
+    @torch.no_grad()
+    def step(self, x, state):
+        """ONE decoding position through every layer and the final LayerNorm: x (B, d) stream rows (the embedding of the step, after
+        which state.pos counts this position) -> (B, d) in the compute dtype.  Writes slot pos - 1 of every layer's self-attention
+        cache; nothing synchronises with the host."""
+        for layer, skv, ckv in zip(self.layers, state.self_kv, state.cross_kv):
+            x = layer._step(x, state.compute, skv, ckv, state.pos, state.mem_len, state.attn_out, state.attn_ws)
+        n = self.norm.norm
+        return F.ln_fwd(x, n.weight, n.bias, n.eps, False, out_dtype=state.compute)[0]
+
+
+class DecodeState:
+    """What KV-cached decoding carries from step to step (TransformerASR.make_decode_state), all on the device.  Per decoder layer:
+    self_kv[i] (B, cap, 2, H, D), the self-attention keys / values of the positions fed so far, and cross_kv[i] (B, S, 2, H, D), the
+    layer's d -> 2d projection of the encoder output, computed once.  pos (B) int32: positions fed (the self-attention key count);
+    mem_len (B) int32: encoder lengths (the cross-attention key count).  The search's own vectors: tok (B) int32 the next input token,
+    done (B) uint8, n_tok (B) int32, score (B) fp32, tokens (B, cap) int32, logp_tok (B, cap) fp32.  Every step reads and advances
+    these in kernels; the host never needs their values to issue the next step.  attn_out (B, H, D) / attn_ws: the output and the split
+    workspace of the step's attention launches, owned here so that a step's 2 x layers smx_attn_step calls allocate nothing."""
+
+    def __init__(self, B, S, cap, H, D, layers, compute, stream, device):
+        self.B, self.S, self.cap, self.compute, self.stream = B, S, cap, compute, stream
+        self.self_kv = [torch.zeros((B, cap, 2, H, D), dtype=compute, device=device) for _ in range(layers)]
+        self.cross_kv = [torch.empty((B, S, 2, H, D), dtype=compute, device=device) for _ in range(layers)]
+        self.attn_out = torch.empty((B, H, D), dtype=compute, device=device)
+        self.attn_ws = torch.empty((max(1, ops.attention_step_workspace(B, H, D, cap, compute), ops.attention_step_workspace(B, H, D, S, compute)),),
+                                   dtype=torch.float32, device=device)
+        self.pos = torch.zeros((B,), dtype=torch.int32, device=device)
+        self.mem_len = torch.empty((B,), dtype=torch.int32, device=device)
+        self.tok = torch.zeros((B,), dtype=torch.int32, device=device)
+        self.done = torch.zeros((B,), dtype=torch.uint8, device=device)
+        self.n_tok = torch.zeros((B,), dtype=torch.int32, device=device)
+        self.score = torch.zeros((B,), dtype=torch.float32, device=device)
+        self.tokens = torch.full((B, cap), -1, dtype=torch.int32, device=device)
+        self.logp_tok = torch.zeros((B, cap), dtype=torch.float32, device=device)
+
+    def reset(self):
+        """Back to position 0 with an empty hypothesis, in place (the buffers a captured step points at stay where they are).  The
+        caches need no clearing: slots at or beyond pos are never read."""
+        for t in (self.pos, self.tok, self.done, self.n_tok, self.score, self.logp_tok):
+            t.zero_()
+        self.tokens.fill_(-1)

@@ -10,7 +10,9 @@ causal) and `custom_tgt_module` (NormalizedEmbedding); forward(src, tgt, wav_len
 decode(tgt, encoder_out, enc_len) -> (prediction, last cross-attention weights).  The tokens become the decoder input in ONE launch
 (smx_tgt_embed_fwd: embedding * sqrt(d) + positional rows + the key-padding mask); the look-ahead mask is the attention kernels'
 causal flag.  Deviation: forward with wav_len=None runs the decoder without a memory padding mask (upstream crashes on
-logical_not(None) there).
+logical_not(None) there).  make_decode_state(encoder_out, enc_len, max_steps) / decode_step(tokens, state) are decode's KV-cached form:
+one new position per call over per-layer caches whose positions are device counters (csrc/attn_step.hip; the seq2seq searchers of
+summarymixing_amd.decoders.seq2seq run on them).
 
 Streaming (:562-685,731-741): make_streaming_context / encode_streaming run a Dynamic-Chunk-trained Conformer encoder one chunk at a
 time, from the encoder input on (the front-end is not streamed).  Chunk c gets rows [c C, c C + C_cur) of the positional table, as
@@ -37,7 +39,7 @@ from ....utils.dynamic_chunk_training import DynChunkTrainConfig  # noqa: F401
 from ...models.VanillaNN import Linear
 from .Branchformer import BranchformerEncoder
 from .Conformer import ConformerEncoder, _slot_commit
-from .Transformer import (LOOKAHEAD, NormalizedEmbedding, TransformerDecoder, get_key_padding_mask,  # noqa: F401
+from .Transformer import (LOOKAHEAD, DecodeState, NormalizedEmbedding, TransformerDecoder, get_key_padding_mask,  # noqa: F401
                           get_lookahead_mask)
 from ....nnet.attention import HEAD_DIMS
 
@@ -243,6 +245,69 @@ class TransformerASR(nn.Module):
         prediction, _, multihead_attns = self.decoder(x, encoder_out, tgt_mask=LOOKAHEAD, memory_key_padding_mask=mem_pad,
                                                       _weights="last_cross")
         return prediction, multihead_attns[-1]
+
+    @torch.no_grad()
+    def make_decode_state(self, encoder_out, enc_len=None, max_steps=None, state=None):
+        """The state of KV-cached decoding over encoder_out (B, S, d) (Transformer.DecodeState): per decoder layer an empty
+        self-attention cache of cap = max_steps positions (default and bound: the positional table's max_length) and the layer's
+        cross-attention keys / values, computed HERE, once, by the d -> 2d Linear on rows [d, 3d) of multihead_attn's in_proj_weight
+        (functional.attention_in_proj, the projection decode runs again for every prefix).  enc_len: the absolute encoder lengths (B),
+        as decode takes them; None: all S.  state: a state of the same (B, S, cap, dtype) to refill in place for the next utterance -
+        its buffers stay where a captured step expects them.  Nothing synchronises with the host."""
+        if self.num_decoder_layers <= 0:
+            raise RuntimeError("TransformerASR was built with num_decoder_layers=0: there is no decoder to make a decoding state for")
+        if self.training:
+            raise RuntimeError("TransformerASR.make_decode_state: decoding runs in eval mode only (self.training is set)")
+        if not encoder_out.is_cuda:
+            raise RuntimeError(ops.NO_CPU)
+        if encoder_out.dim() != 3 or encoder_out.dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"encoder_out must be (B, S, d) float32 or bfloat16, got {encoder_out.dtype} {tuple(encoder_out.shape)}")
+        B, S, d = encoder_out.shape
+        limit = self.positional_encoding.max_len if self.positional_encoding_type == "fixed_abs_sine" else None
+        if max_steps is None and limit is None:
+            raise ValueError("make_decode_state: max_steps is needed without a positional table to bound it")
+        cap = limit if max_steps is None else (int(max_steps) if limit is None else min(int(max_steps), limit))
+        if cap < 1:
+            raise ValueError(f"make_decode_state: max_steps must be >= 1, got {max_steps}")
+        layers = self.decoder.layers
+        H = layers[0].nhead
+        compute = encoder_out.dtype
+        stream = F.stream_dtype(compute) if layers[0].normalize_before else compute
+        if state is None:
+            state = DecodeState(B, S, cap, H, d // H, len(layers), compute, stream, encoder_out.device)
+        elif (state.B, state.S, state.cap, state.compute) != (B, S, cap, compute) or state.pos.device != encoder_out.device:
+            raise ValueError(f"make_decode_state: the state holds (B, S, cap, dtype) = {(state.B, state.S, state.cap, state.compute)}, "
+                             f"this call needs {(B, S, cap, compute)}")
+        else:
+            state.reset()
+        mem2 = ops.rows2d(encoder_out if encoder_out.is_contiguous() else encoder_out.contiguous())
+        for layer, ckv in zip(layers, state.cross_kv):
+            F.attention_in_proj(layer.multihead_attn.att, mem2, 1, 3, out=ckv.view(B * S, 2 * d))
+        if enc_len is None:
+            state.mem_len.fill_(S)
+        else:
+            state.mem_len.copy_(enc_len.reshape(B))           # (cast to int32 on the device; a length outside [1, S] gives a zero row)
+        return state
+
+    @torch.no_grad()
+    def decode_step(self, tokens, state):
+        """One KV-cached decoding step: tokens (B,) integer on the device, the input at position state.pos -> prediction (B, d), what
+        decode(prefix, encoder_out, enc_len)[0][:, -1] computes for the prefix fed so far, at the cost of ONE row per utterance:
+        smx_s2s_embed_step (embedding * sqrt(d) + the positional row of the DEVICE counter state.pos, which it advances), then per
+        layer the sublayers of decode with smx_attn_step over the state's caches in place of smx_attn_fwd, then the final LayerNorm.
+        No attention weights.  A row fed beyond the state's cap positions is marked done (state.done) and yields zeros from its
+        self-attention; the host is never asked.  Eval mode only."""
+        if self.training:
+            raise RuntimeError("TransformerASR.decode_step: decoding runs in eval mode only (self.training is set)")
+        if not tokens.is_cuda:
+            raise RuntimeError(ops.NO_CPU)
+        if tokens.dim() != 1 or tokens.is_floating_point() or tokens.shape[0] != state.B:
+            raise ValueError(f"tokens must be ({state.B},) integer tokens, got {tokens.dtype} {tuple(tokens.shape)}")
+        tok = tokens if (tokens.dtype == torch.int32 and tokens.is_contiguous()) else tokens.to(torch.int32).contiguous()
+        emb = self.custom_tgt_module.layers[0]
+        pe = self.positional_encoding.pe[0] if self.positional_encoding_type == "fixed_abs_sine" else None
+        x = ops.s2s_embed_step(tok, emb.emb.Embedding.weight.detach(), pe, state.pos, state.done, state.cap, out_dtype=state.stream)
+        return self.decoder.step(x, state)
 
     def encode(self, src, wav_len=None, pad_idx=0, dynchunktrain_config=None, masked_false_or_true: Optional[bool] = True):
         """TransformerASR.py:501-560.  masked_false_or_true is honoured exactly like the reference: the SummaryMixing cell

@@ -1668,3 +1668,110 @@ def tgt_embed_bwd(tokens, dy, gtable, pad_idx=0):
     L.check(L.lib().smx_tgt_embed_bwd(dt(dy2), _p(tk), pd, ldd, pg, ldg, tk.numel(), V, D, int(pad_idx), _stream()), "smx_tgt_embed_bwd")
     _pe(tok)
     return gtable
+
+
+# ---- one KV-cached decoding step (csrc/attn_step.hip).  Positions are device counters; no call here synchronises with the host.
+def _step_operand(t, B, H, D, what, cap=None):
+    """(B, H, D), or a cache (B, cap, H, D), as an smx_attn_operand."""
+    if t is None:
+        return L.AttnOperand()
+    if not t.is_cuda:
+        raise RuntimeError(NO_CPU)
+    want = (B, H, D) if cap is None else (B, cap, H, D)
+    assert tuple(t.shape) == want, f"attention_step: {what} must be {want}, got {tuple(t.shape)}"
+    st = t.stride()
+    sb, sh, sd = st[0], st[-2], st[-1]
+    return L.AttnOperand(t.data_ptr(), sb if B > 1 else 0, (st[1] if cap > 1 else 0) if cap is not None else 0, sh if H > 1 else 0, sd)
+
+
+def attention_step_plan(B, H, D, cap, dtype=torch.float32):
+    """smx_attn_step_plan_query for a problem size (needs no GPU): a dict of the launch geometry.  Raises where the library refuses."""
+    a = L.AttnStepArgs(dtype=_DT.get(dtype, -1), B=B, H=H, D=D, cap=cap, scale=1.0)
+    p = L.AttnStepPlan()
+    L.check(L.lib().smx_attn_step_plan_query(ctypes.byref(a), ctypes.byref(p)), "smx_attn_step_plan_query")
+    return dict(lanes_per_key=p.lanes_per_key, keys_per_wave=p.keys_per_wave, waves=p.waves, threads=p.threads, splits=p.splits,
+                chunk=p.chunk, launches=p.launches, lds_bytes=p.lds_bytes, grid=tuple(p.grid), workspace_bytes=p.workspace_bytes)
+
+
+_STEP_WS = {}   # (B, H, D, cap, dtype code) -> workspace floats of smx_attn_step (a function of the sizes alone: asked once)
+
+
+def attention_step_workspace(B, H, D, cap, dtype=torch.float32):
+    """fp32 elements of workspace ops.attention_step needs at these sizes (0: a single launch); the plan query runs once per size."""
+    key = (B, H, D, cap, _DT.get(dtype, -1))
+    n = _STEP_WS.get(key)
+    if n is None:
+        n = _STEP_WS[key] = attention_step_plan(B, H, D, cap, dtype)["workspace_bytes"] // 4
+    return n
+
+
+def attention_step(q, K, V, n_keys=None, k_new=None, v_new=None, scale=None, out=None, workspace=None):
+    """One query row per (batch row, head) over a cache: q (B, H, D), K / V (B, cap, H, D), n_keys (B) int32 on the device (None:
+    all cap keys) -> o (B, H, D) in q's dtype (smx_attn_step).  With k_new / v_new (B, H, D) the call first stores them into cache slot
+    n_keys[b] - 1.  All operands are read in place through their strides (unit stride along D, 16-byte aligned rows).  out / workspace
+    (fp32, at least attention_step_workspace elements): buffers the caller owns - a decoding state hands in its own, so a step
+    allocates nothing here; fresh ones otherwise."""
+    if not (q.is_cuda and K.is_cuda and V.is_cuda):
+        raise RuntimeError(NO_CPU)
+    B, H, D = q.shape
+    cap = K.shape[1]
+    assert K.dtype == q.dtype and V.dtype == q.dtype and (k_new is None) == (v_new is None)
+    assert k_new is None or (k_new.dtype == q.dtype and v_new.dtype == q.dtype)
+    assert n_keys is None or (n_keys.is_cuda and n_keys.dtype == torch.int32 and n_keys.is_contiguous() and n_keys.shape == (B,))
+    if out is None:
+        out = torch.empty((B, H, D), dtype=q.dtype, device=q.device)
+    a = L.AttnStepArgs(dtype=dt(q), B=B, H=H, D=D, cap=cap, scale=float(D ** -0.5 if scale is None else scale), n_keys=_p(n_keys))
+    a.q, a.o = _step_operand(q, B, H, D, "q"), _step_operand(out, B, H, D, "out")
+    a.k_new, a.v_new = _step_operand(k_new, B, H, D, "k_new"), _step_operand(v_new, B, H, D, "v_new")
+    a.K, a.V = _step_operand(K, B, H, D, "K", cap), _step_operand(V, B, H, D, "V", cap)
+    need = attention_step_workspace(B, H, D, cap, q.dtype)
+    if need:
+        if workspace is None:
+            workspace = torch.empty((need,), dtype=torch.float32, device=q.device)
+        assert workspace.is_cuda and workspace.dtype == torch.float32 and workspace.is_contiguous() and workspace.numel() >= need
+        a.workspace = workspace.data_ptr()
+    tok = _pb(f"attn_step {'bf16' if _es(q) == 2 else 'f32'} (B {B}, cap {cap}, H {H}, D {D})" + (" self" if k_new is not None else ""),
+              2 * B * cap * H * D * _es(q), 4.0 * B * H * cap * D)
+    L.check(L.lib().smx_attn_step(ctypes.byref(a), _stream()), "smx_attn_step")
+    _pe(tok)
+    return out
+
+
+def s2s_embed_step(tok, table, pe, pos, done, max_pos, out_dtype=torch.float32, out=None):
+    """y (B, d) = table[tok] * sqrt(d) + pe[pos] in out_dtype, then pos += 1 on the rows with done == 0 (smx_s2s_embed_step): tok (B)
+    int32, table (V, d) fp32, pe (>= max_pos, d) fp32 or None, pos (B) int32 and done (B) uint8 on the device, updated IN PLACE.  A row
+    at pos >= max_pos is marked done instead of advanced."""
+    if not (tok.is_cuda and table.is_cuda and pos.is_cuda and done.is_cuda and (pe is None or pe.is_cuda)):
+        raise RuntimeError(NO_CPU)
+    B = tok.shape[0]
+    V, D = table.shape
+    assert tok.dtype == torch.int32 and tok.is_contiguous() and tok.dim() == 1
+    assert pos.dtype == torch.int32 and pos.is_contiguous() and pos.shape == (B,) and done.dtype == torch.uint8 and done.is_contiguous() and done.shape == (B,)
+    assert table.dtype == torch.float32 and (pe is None or (pe.dtype == torch.float32 and pe.dim() == 2 and pe.shape[1] == D and pe.shape[0] >= max_pos))
+    y = torch.empty((B, D), dtype=out_dtype, device=table.device) if out is None else out
+    assert y.dtype == out_dtype and tuple(y.shape) == (B, D)
+    pt, ldt = _mat(table)
+    pp, ldp = _mat(pe) if pe is not None else (None, 0)
+    py, ldy = _mat(y)
+    L.check(L.lib().smx_s2s_embed_step(_DT[out_dtype], _p(tok), pt, ldt, pp, ldp, py, ldy, _p(pos), _p(done), B, V, D, int(max_pos), _stream()),
+            "smx_s2s_embed_step")
+    return y
+
+
+def s2s_select(logits, tok, done, n_tok, score, tokens, logp_tok, eos, min_steps=0, inv_temp=1.0, forced=None):
+    """The token selection of one search step over logits (B, V) (smx_s2s_select): arg-max (or forced (B) int32), its log-probability at
+    temperature 1 / inv_temp, appended to tokens / logp_tok (B, cap) at n_tok; score, n_tok, done, tok updated IN PLACE on the rows with
+    done == 0."""
+    if not logits.is_cuda:
+        raise RuntimeError(NO_CPU)
+    pz, ldz = _mat(logits)
+    B, V = logits.shape
+    cap = tokens.shape[1]
+    assert all(t.is_cuda and t.is_contiguous() for t in (tok, done, n_tok, score, tokens, logp_tok))
+    assert tok.dtype == torch.int32 and n_tok.dtype == torch.int32 and tokens.dtype == torch.int32 and done.dtype == torch.uint8
+    assert score.dtype == torch.float32 and logp_tok.dtype == torch.float32
+    assert tok.shape == (B,) and done.shape == (B,) and n_tok.shape == (B,) and score.shape == (B,) and tuple(tokens.shape) == (B, cap) and tuple(logp_tok.shape) == (B, cap)
+    assert forced is None or (forced.is_cuda and forced.dtype == torch.int32 and forced.is_contiguous() and forced.shape == (B,))
+    a = L.S2SSelectArgs(logits=pz, ldz=ldz, forced=_p(forced), tok=_p(tok), done=_p(done), n_tok=_p(n_tok), score=_p(score), tokens=_p(tokens),
+                        logp_tok=_p(logp_tok), inv_temp=float(inv_temp), dtype=dt(logits), B=B, V=V, cap=cap, eos=int(eos), min_steps=int(min_steps))
+    L.check(L.lib().smx_s2s_select(ctypes.byref(a), _stream()), "smx_s2s_select")
