@@ -54,9 +54,12 @@ typedef struct smx_config {
   int32_t t256;             /* SMX_T256: 256 x 256 GEMM tile (one workgroup per CU, software-pipelined K loop)
                                0 off, 1 for K >= 2048 (1), 2 for every eligible shape (tests)                  */
   int32_t panel_rows;       /* SMX_PANEL_ROWS: rows per panel of smx_gemm_panel (128 / 64 / 32); 0 = by frame count  */
-  int32_t pool_fuse_max_rows;  /* SMX_POOL_FUSE_MAX_ROWS: smx_pool_bcast_ok up to this many frames (B * T)            */
+  int32_t pool_fuse_max_rows;  /* SMX_POOL_FUSE_MAX_ROWS (16 384): smx_pool_bcast_ok(B, T, D) = T <= 4096 and
+                                  (B * T <= this many frames or B * ceil(D / 64) >= 256)                            */
   int32_t ln_tile64;        /* SMX_LN_TILE64: the 64 x 256 LayerNorm-fused tile: 0 never, 1 where it fills its rounds better (default), 2 always */
-  int32_t pad_;
+  int32_t lnb_lds;          /* SMX_LNB_LDS: the LayerNorm-backward epilogue of the 128 x 256 tile lands its side rows (ln_x, res, z) in
+                               LDS by LDS-DMA, each half-phase's request in flight under the previous one: 1 on (default), 0 the
+                               register path (bit-identical results) */
 } smx_config;
 int smx_get_config(smx_config* out);
 /* rows per tile of the LayerNorm-fused GEMMs (SMX_EPI_LN_BWD writes ceil(N / rows) partial row pairs into ln_partial) */

@@ -40,6 +40,7 @@ const smx_config& cfg() {
     k.panel_rows = env_i("SMX_PANEL_ROWS", 0);
     k.pool_fuse_max_rows = env_i("SMX_POOL_FUSE_MAX_ROWS", 16384);
     k.ln_tile64 = env_i("SMX_LN_TILE64", 1);
+    k.lnb_lds = env_i("SMX_LNB_LDS", 1);
 #ifdef SMX_DIAG
     k.gemm_ablate = env_i("SMX_GEMM_ABLATE", 0);
     k.wgroup_ablate = env_i("SMX_WGROUP_ABLATE", 0);

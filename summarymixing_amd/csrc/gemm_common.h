@@ -29,6 +29,7 @@ struct GemmParams {
   int nt;       // non-temporal store hints: 1 = saved pre-activation Z, 2 = the output C
   int epi_simple;  // no element-wise side input, no column sums: the SIMPLE instantiation of epilogue_phase
   int ablate;   // debug (env SMX_GEMM_ABLATE): 1 = no epilogue stores, 2 = no MFMA, 4 = no global loads
+  int lnb_lds;  // 128 x 256 LayerNorm-backward epilogue: side rows through the LDS landing zone (SMX_LNB_LDS; launch_ln)
   smx_gemm_plan* plan;   // smx_gemm_plan_query: the dispatch records the instantiation here instead of launching it
   // implicit 3x3 / stride 2 / reflect-pad-1 patch matrix (gemm_kernel<..., GATHER>): the operand "rows x 9 C" is never
   // materialised - row n = (b, t2, f2), columns [tap * 64, tap * 64 + 64) = the 64 channels of input pixel
@@ -869,6 +870,224 @@ __device__ __forceinline__ void epilogue_phase_lnbwd(const GemmParams& p, const 
   }
 }
 
+// LDS-DMA issue of one 1 KB piece (global_load_lds_dwordx4: lane i lands at lds_dst + 16 i; M0 carries the wave-uniform
+// LDS base and is compiler-reserved, so it is saved / restored inside the statement).  hipcc does not count this
+// load: the kernel waits for it with explicit s_waitcnt vmcnt(N).
+__device__ __forceinline__ void glds16(const void* gsrc, uint32_t lds_dst) {
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
+}
+// ... of one dword / one byte per active lane (lane i lands at lds_dst + 4 i in both forms)
+__device__ __forceinline__ void glds4(const void* gsrc, uint32_t lds_dst) {
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
+}
+__device__ __forceinline__ void glds1(const void* gsrc, uint32_t lds_dst) {
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_ubyte %1, off\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
+}
+
+// ---- the same on the 128 x 256 tile with the side ROWS landed in LDS by LDS-DMA (SMX_LNB_LDS; the phase loop of gemm_kernel.h).
+// The generic phase above waits for every half's ln_x / res (/ z) in the open, and a register request set next to the 128
+// accumulators spills; an LDS-DMA load has no destination register.  Each wave lands exactly the rows it consumes itself - an ITEM
+// k of a half is its row pair (2 w + 8 k, 2 w + 8 k + 1), one row per half wave - so the zone needs no barrier, only the wave's own
+// vmcnt, and 8 KB + 128 B per wave, item k at k * (4 KB + 64 B):
+//   [0, 2048)  ln_x   float32: row h of the pair at h KB, the row's 16-byte chunks 2 j | 2 j + 1 at j | 32 + j (both reads of a half
+//                     wave are 512 contiguous bytes); bf16: the two rows as they lie in the first KB
+//   [2048, 3072) res, [3072, 4096) z: the two rows as they lie;  [4096, 4112) the (mean, rstd) pairs of the two rows (one dword
+//                     from each of four lanes: a 16-byte piece would need ln_stats 16-byte aligned);  [4112, 4120) the second
+//                     output's mask bytes of the two rows, one per dword (a byte from each of two lanes; only byte 0 is read back)
+// An item copies its landed rows into the registers the generic phase loads (ds_read_b128, conflict-free), waits lgkmcnt(0) and
+// issues the DMA of the same item of the NEXT half into the same 4 KB before its own arithmetic and stores.  NOTHING stays on the
+// register path, and the DMA is inline assembly, for two reasons found in the ISA hipcc emitted:
+//  * a DMA hipcc knows of (the raw_ptr_buffer_load_lds builtin) is waited for with vmcnt(0) in front of EVERY LDS access that may
+//    alias it - the accumulator dump and the gamma reads included;
+//  * with the DMA invisible, any vmcnt(k) hipcc places for a load of its own (k from the operations it knows of) behind a DMA waits
+//    for the rows just requested; the statistics and the mask byte as plain loads (8 + 1 bytes per row) cost exactly that, and
+//    their copy into loop-carried registers at the end of a half was a vmcnt(0) behind the stores as well.
+// The expressions, their order and the store order are those of epilogue_phase_lnbwd: results are bit-identical.
+// hipcc does not wait for an LDS-DMA load: lnb_wait_vm(n) does, n = the vector-memory operations known to be YOUNGER than the
+// item's DMA (vmcnt retires in order and counts stores).  With D = the DMA instructions of an item, S = the stores of an item (1,
+// 2 with a second output; taken as 0 in a tail tile, whose waves skip the stores of dead rows - fewer is always correct), the
+// stream of a wave is  D0 D1 | W0 D2 S0 | W1 D3 S1 | W2 D4 S2 | ... | W15 S15:  younger than D(i) at W(i) are D(i+1) for i = 0,
+// D(i+1) S(i-1) for i = 1, S(i-2) D(i+1) S(i-1) from there on (no D behind the last item).
+constexpr int LNB_ZONE_ST = 4096, LNB_ZONE_MK = 4112, LNB_ZONE_ITEM = 4096 + 64, LNB_ZONE_WAVE = 2 * LNB_ZONE_ITEM, LNB_ZONE_BYTES = 4 * LNB_ZONE_WAVE, LNB_ZONE_R = 2048, LNB_ZONE_Z = 3072;
+template <int N> __device__ __forceinline__ void lnb_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+__device__ __forceinline__ void lnb_wait_vm(int n) {     // (n wave-uniform, 0 .. 8)
+  switch (n) {
+    case 0: lnb_vm<0>(); break; case 1: lnb_vm<1>(); break; case 2: lnb_vm<2>(); break; case 3: lnb_vm<3>(); break; case 4: lnb_vm<4>(); break;
+    case 5: lnb_vm<5>(); break; case 6: lnb_vm<6>(); break; case 7: lnb_vm<7>(); break; default: lnb_vm<8>(); break;
+  }
+}
+struct LnbLdsSrc {
+  bool hasR, hasZ, hasM;
+  int nd, ns;                                            // D and S above
+  // the second output's dropout, fetched ONCE per tile: epoch_seed reads the device step counter, and inside an item that load (and
+  // its vmcnt(0)) would sit behind the DMA the item has just issued
+  uint32_t thresh2, seed2_lo, seed2_hi;
+};
+template <typename T, bool EXT, bool XF32>
+__device__ __forceinline__ LnbLdsSrc lnb_lds_src(const GemmParams& p, bool full_tile) {
+  const smx_epilogue& e = p.e;
+  LnbLdsSrc s;
+  s.hasR = e.res != nullptr;
+  s.hasZ = EXT && e.z != nullptr && e.ln_dx2 != nullptr;
+  s.hasM = e.ln_dx2 != nullptr && e.ln_mask2 != nullptr;
+  s.nd = (XF32 ? 2 : 1) + (s.hasR ? 1 : 0) + (s.hasZ ? 1 : 0) + 1 + (s.hasM ? 1 : 0);
+  s.ns = full_tile ? (e.ln_dx2 ? 2 : 1) : 0;
+  s.thresh2 = e.ln_dx2 ? (uint32_t)((double)e.ln_drop_p2 * 4294967296.0) : 0u;
+  const uint64_t seed2 = s.thresh2 ? epoch_seed(e.ln_drop_seed2, p.epoch) : 0;
+  s.seed2_lo = __builtin_amdgcn_readfirstlane((uint32_t)seed2);
+  s.seed2_hi = __builtin_amdgcn_readfirstlane((uint32_t)(seed2 >> 32));
+  return s;
+}
+// the DMA of one item (row pair nrow, nrow + 1; rows >= N re-read row N - 1, as the generic phase does) into its `zone`; nrow and
+// zone are wave-uniform
+template <typename T, bool EXT, bool XF32>
+__device__ __forceinline__ void lnb_lds_dma(const GemmParams& p, const LnbLdsSrc& src, const unsigned char* zone, int nrow, int lane) {
+  typedef typename std::conditional<XF32, float, T>::type XT;
+  const smx_epilogue& e = p.e;
+  const uint32_t zi = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)zone);   // LDS byte address of the item's 4 KB
+  asm volatile("" : "+v"(lane));                         // (the lane's addresses are built HERE, a few VALU operations per item: hoisted
+                                                         //  out of the phase loop they were 6 registers the EXT forms do not have)
+  const int h = lane >> 5, j = lane & 31;
+  const long nl = min(nrow + h, p.N - 1);                // this lane's row of the pair
+  const XT* X = reinterpret_cast<const XT*>(e.ln_x);
+  if constexpr (XF32) {
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh) {                      // (one row per instruction)
+      const long nu = min(nrow + hh, p.N - 1);
+      glds16(X + nu * e.ln_ldx + (2 * j + h) * 4, zi + hh * 1024);
+    }
+  } else {
+    glds16(X + nl * e.ln_ldx + j * 8, zi);
+  }
+  if (src.hasR) glds16(reinterpret_cast<const T*>(e.res) + nl * e.ldr + j * 8, zi + LNB_ZONE_R);
+  if constexpr (EXT) {
+    if (src.hasZ) glds16(reinterpret_cast<const T*>(e.z) + nl * e.ldz + j * 8, zi + LNB_ZONE_Z);
+  }
+  if (lane < 4) glds4(e.ln_stats + 2 * (long)min(nrow + (lane >> 1), p.N - 1) + (lane & 1), zi + LNB_ZONE_ST);
+  if (src.hasM) {
+    if (lane < 2) glds1(e.ln_mask2 + min(nrow + lane, p.N - 1), zi + LNB_ZONE_MK);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+}
+// one item: sm = the staged row of this thread, n = its output row, nwait: see above.  nrow_next >= 0: request the same item of the next half (first row nrow_next) once the zone is read.
+template <typename T, bool EXT, bool XF32>
+__device__ __forceinline__ void lnb_lds_item(const GemmParams& p, const LnbLdsSrc& src, const char* sm, const float* lng, const unsigned char* zone, int n,
+                                             int lane, int nwait, int nrow_next, float (&dgam)[8], float (&dbet)[8]) {
+  constexpr int W = 256, SWX = XF32 ? 8 : 4;
+  constexpr float INVW = 1.f / W;
+  const smx_epilogue& e = p.e;
+  const int c = (lane & 31) * 8;
+  float gam[8];
+#pragma unroll
+  for (int q4 = 0; q4 < 2; ++q4) {
+    const float4 g4 = *reinterpret_cast<const float4*>(lng + c + 4 * q4);
+    gam[4 * q4] = g4.x; gam[4 * q4 + 1] = g4.y; gam[4 * q4 + 2] = g4.z; gam[4 * q4 + 3] = g4.w;
+  }
+  const int lact = EXT ? e.lnf_act : SMX_ACT_NONE;
+  uint32_t xw[SWX], rw[4], zw[4];
+  lnb_wait_vm(nwait);                                      // this item's rows have landed
+  if constexpr (XF32) {
+    const unsigned char* xp = zone + (lane >> 5) * 1024 + (lane & 31) * 16;
+    const uint4 a_ = *reinterpret_cast<const uint4*>(xp), b_ = *reinterpret_cast<const uint4*>(xp + 512);
+    xw[0] = a_.x; xw[1] = a_.y; xw[2] = a_.z; xw[3] = a_.w; xw[4] = b_.x; xw[5] = b_.y; xw[6] = b_.z; xw[7] = b_.w;
+  } else {
+    ld_words<4>(zone + lane * 16, xw);
+  }
+  if (src.hasR) ld_words<4>(zone + LNB_ZONE_R + lane * 16, rw);
+  else rw[0] = rw[1] = rw[2] = rw[3] = 0u;
+  if constexpr (EXT) {
+    if (src.hasZ) ld_words<4>(zone + LNB_ZONE_Z + lane * 16, zw);
+  }
+  const float2 st = *reinterpret_cast<const float2*>(zone + LNB_ZONE_ST + (lane >> 5) * 8);
+  uint32_t mkb = 1u;
+  if (src.hasM) mkb = zone[LNB_ZONE_MK + (lane >> 5) * 4];
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // the item's zone is read: it can take the next half's rows
+  if (nrow_next >= 0) lnb_lds_dma<T, EXT, XF32>(p, src, zone, nrow_next, lane);   // (uniform)
+  const uint32_t thresh2 = src.thresh2;
+  const float scale2 = 1.f / (1.f - e.ln_drop_p2);
+  const uint64_t seed2 = ((uint64_t)src.seed2_hi << 32) | src.seed2_lo;
+  const bool rok = n < p.N;
+  float v[8], xh[8], rf[8];
+#pragma unroll
+  for (int q4 = 0; q4 < 2; ++q4) {
+    const float4 a4 = *reinterpret_cast<const float4*>(sm + (c + 4 * q4) * 4);
+    v[4 * q4] = a4.x; v[4 * q4 + 1] = a4.y; v[4 * q4 + 2] = a4.z; v[4 * q4 + 3] = a4.w;
+  }
+  if constexpr (XF32) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) xh[q] = __uint_as_float(xw[q]);
+  } else {
+    unpack_words<T, 8>(xw, xh);
+  }
+  unpack_words<T, 8>(rw, rf);
+  float s1 = 0.f, s2 = 0.f;
+  if (EXT && lact != SMX_ACT_NONE) {                     // (uniform; beta sits behind gamma in LDS)
+    float ag[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) ag[q] = (xh[q] - st.x) * st.y * gam[q] + lng[W + c + q];
+    switch (lact) {
+      case SMX_ACT_GELU: act_grad_mul_n<SMX_ACT_GELU, 8>(v, ag); break;
+      case SMX_ACT_SWISH: act_grad_mul_n<SMX_ACT_SWISH, 8>(v, ag); break;
+      case SMX_ACT_LEAKY_RELU: act_grad_mul_n<SMX_ACT_LEAKY_RELU, 8>(v, ag); break;
+      case SMX_ACT_RELU: act_grad_mul_n<SMX_ACT_RELU, 8>(v, ag); break;
+      default: break;
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    xh[q] = (xh[q] - st.x) * st.y;
+    const float g = rok ? v[q] : 0.f;
+    dgam[q] += g * xh[q];
+    dbet[q] += g;
+    v[q] = g * gam[q];
+    s1 += v[q];
+    s2 += v[q] * xh[q];
+  }
+  s1 = ln_row_sum<W>(s1) * INVW;
+  s2 = ln_row_sum<W>(s2) * INVW;
+  if (rok) {
+#pragma unroll
+  for (int q = 0; q < 8; ++q) v[q] = st.y * (v[q] - s1 - xh[q] * s2) + rf[q];
+  st_elems<T, 8>(reinterpret_cast<T*>(p.C) + (long)n * p.ldc + c, v);
+  if (e.ln_dx2) {                                        // (uniform)
+    const float mk = (mkb ? 1.f : 0.f) * e.ln_alpha2;
+    if constexpr (EXT) {
+      if (src.hasZ) {
+        float zf[8];
+        unpack_words<T, 8>(zw, zf);
+        switch (e.act) {
+          case SMX_ACT_GELU: act_grad_mul_n<SMX_ACT_GELU, 8>(v, zf); break;
+          case SMX_ACT_SWISH:
+            // v * (s * u) under -ffast-math: in epilogue_phase_lnbwd hipcc evaluates it as (s * v) * u, here it chose (u * s) * v -
+            // one dX2 element in ~10^5 rounded the other way.  The grouping of the generic phase, pinned:
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+              const float s_ = sigmoidf_(zf[q]);
+              float sv = s_ * v[q];
+              settle(sv);
+              v[q] = sv * (1.0f + zf[q] * (1.0f - s_));
+            }
+            break;
+          case SMX_ACT_LEAKY_RELU: act_grad_mul_n<SMX_ACT_LEAKY_RELU, 8>(v, zf); break;
+          case SMX_ACT_RELU: act_grad_mul_n<SMX_ACT_RELU, 8>(v, zf); break;
+          default: break;
+        }
+      }
+    }
+    if (thresh2) dropout_apply<8>(v, seed2, (uint64_t)n * W + c, thresh2, scale2);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) v[q] *= mk;
+    st_elems<T, 8>(reinterpret_cast<T*>(e.ln_dx2) + (long)n * e.ln_lddx2 + c, v);
+  }
+  }
+}
+
 // ---- the same, split into REQUEST and CONSUME: the side inputs of 16 rows (a half phase: rows r0 + RSTEP k, k < NH, of the thread's
 // half wave / wave) - LayerNorm input, statistics, residual gradient, the second output's mask byte and saved pre-activation - go
 // into ONE register set; the first half of a phase is requested BEFORE the accumulator dump of that phase, so its round trip runs
@@ -1310,15 +1529,6 @@ __device__ __forceinline__ void ln1p_store_stats(const GemmParams& p, const floa
     *reinterpret_cast<float2*>(p.e.lnf_stats + 2 * (long)(n0 + t)) = *reinterpret_cast<const float2*>(lnst + 2 * t);
   if (p.e.lnf2_y && p.e.lnf2_stats && t >= 128 && t - 128 < rows && n0 + t - 128 < p.N)
     *reinterpret_cast<float2*>(p.e.lnf2_stats + 2 * (long)(n0 + t - 128)) = *reinterpret_cast<const float2*>(lnst + 2 * t);
-}
-
-// LDS-DMA issue of one 1 KB piece (global_load_lds_dwordx4: lane i lands at lds_dst + 16 i; M0 carries the wave-uniform
-// LDS base and is compiler-reserved, so it is saved / restored inside the statement).  hipcc does not count this
-// load: the kernel waits for it with explicit s_waitcnt vmcnt(N).
-__device__ __forceinline__ void glds16(const void* gsrc, uint32_t lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
 }
 
 // fragment of a reduce-strided stage with 256-byte k rows (128 columns), granule XOR 4 * (k & 3): see gemm_tn_dma_kernel

@@ -68,14 +68,21 @@ __global__ __launch_bounds__(256, ((TILE_N == 256 || TILE_M == 512) ? 1 : ((TILE
   // in 32-element steps: both operands double-buffered in LDS (2 x 24 KB = the one 48 KB stage of the serial loop)
   constexpr bool W128P = sizeof(T) == 2 && VEC && A_KC && (TILE_N == 128 || TILE_N == 64) && TILE_M == 256 && GATHER == 0;
   constexpr int AB_BYTES = T256P ? 2 * (A_BYTES + B_BYTES) : A_BYTES + B_BYTES;
-  constexpr int SMEM_BYTES = AB_BYTES > EPI_BYTES ? AB_BYTES : EPI_BYTES;
+  // LNB_LDS (SMX_LNB_LDS): the LayerNorm-backward epilogue of the 128 x 256 tile lands its side rows in a 32 KB zone (gemm_common.h,
+  // lnb_lds_item) in FRONT of the staging rows: 32.5 + 32.5 KB where the 48 KB operand ring was, 71 168 B with the small arrays -
+  // above the 64 KB of the other instantiations (a static array, like the 128 x 512 tile's 160 KB) and under the 80 KB that keep two
+  // workgroups per CU
+  constexpr bool LNB_LDS = ((LNF & 3) == 1 || (LNF & 3) == 3) && TILE_N == 128 && TILE_M == 256;
+  constexpr int ZONE_BYTES = LNB_LDS ? LNB_ZONE_BYTES : 0;
+  constexpr int SMEM_BYTES = AB_BYTES > EPI_BYTES + ZONE_BYTES ? AB_BYTES : EPI_BYTES + ZONE_BYTES;
   constexpr int RED_BYTES = TILE_M * 4;                          // colsum: phase-0 column sums
   // bias[TILE_M] | row factors[TILE_N] (mask * alpha) [| LN gamma | beta [LN forward: | the tile's (mean, rstd) pairs of both
   // LayerNorms | gamma | beta of the second LayerNorm]]
   constexpr int SIDE_BYTES = (TILE_M + TILE_N + (LNF ? 2 * TILE_M : 0) + (LNF == 2 ? 4 * 128 + 2 * TILE_M : 0)) * 4;   // (statistics block: [2][128][2] whatever TILE_N)
   // when the block would pass the 64 KB static LDS limit its small epilogue arrays live behind the epilogue staging rows
   // inside the (by then dead) operand stage, fenced by one extra barrier
-  constexpr bool ALIAS_SIDE = SMEM_BYTES + RED_BYTES + SIDE_BYTES > 65536;
+  constexpr bool ALIAS_SIDE = !LNB_LDS && SMEM_BYTES + RED_BYTES + SIDE_BYTES > 65536;
+  static_assert(!LNB_LDS || SMEM_BYTES + RED_BYTES + SIDE_BYTES <= 81920, "two workgroups per CU");
   static_assert(!ALIAS_SIDE || EPI_BYTES + RED_BYTES + SIDE_BYTES + 64 <= SMEM_BYTES, "epilogue arrays do not fit");
   __shared__ __attribute__((aligned(16))) char smem[ALIAS_SIDE ? SMEM_BYTES : SMEM_BYTES + RED_BYTES + SIDE_BYTES];
   float* red = reinterpret_cast<float*>(smem + (ALIAS_SIDE ? (EPI_BYTES + 63) / 64 * 64 : SMEM_BYTES));
@@ -658,8 +665,56 @@ __global__ __launch_bounds__(256, ((TILE_N == 256 || TILE_M == 512) ? 1 : ((TILE
       return;
     }
   }
+  bool generic = true;
+  if constexpr (LNB_LDS) {
+    if (p.lnb_lds) {                                      // (uniform, chosen ONCE: its own loop, like the one-pass forward above)
+      // The zone lies inside the operand ring: every step of the main loop ends with a barrier behind its last fragment read, so
+      // the ring is dead here and the first half's rows fly under the dump of phase 0 and its two barriers.
+      constexpr bool EXT_ = (LNF & 3) == 3, XF_ = (LNF & 4) != 0;
+      generic = false;
+      const int wv = __builtin_amdgcn_readfirstlane(wave);
+      unsigned char* zone = reinterpret_cast<unsigned char*>(smem) + wv * LNB_ZONE_WAVE;
+      char* stg = smem + ZONE_BYTES;
+      const LnbLdsSrc src = lnb_lds_src<T, EXT_, XF_>(p, n0 + TILE_N <= p.N);
+      const int r0 = t >> 5;                               // this thread's row of item 0 of a half (item 1: r0 + 8)
 #pragma unroll 1
-  for (int ph = 0; ph < NPH; ++ph) {
+      for (int ph = 0; ph < NPH; ++ph) {
+        if (ph == 0) {                                     // (inside the loop: hipcc drains vmcnt in the loop's preheader)
+          lnb_lds_dma<T, EXT_, XF_>(p, src, zone, n0 + 2 * wv, lane);
+          lnb_lds_dma<T, EXT_, XF_>(p, src, zone + LNB_ZONE_ITEM, n0 + 2 * wv + 8, lane);
+        }
+        lds_barrier();
+        if (wn == (ph * 32) / WN) {                        // the wave row that owns these accumulator rows
+#pragma unroll
+          for (int i = 0; i < FN; ++i) {
+            if (i == ((ph * 32) % WN) / 32) {
+#pragma unroll
+              for (int j = 0; j < FM; ++j)
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+                  *reinterpret_cast<float4*>(stg + l31 * STG_LD + (wm * WM + j * 32 + g * 8 + hi * 4) * 4) =
+                      make_float4(acc[i][j][g * 4], acc[i][j][g * 4 + 1], acc[i][j][g * 4 + 2], acc[i][j][g * 4 + 3]);
+            }
+          }
+        }
+        lds_barrier();
+        if (ph < 2) SMX_STAMP(3 + 2 * ph);
+#pragma unroll 1
+        for (int half = 0; half < 2; ++half) {
+          const int hb = ph * 2 + half, nb = n0 + hb * 16;                  // items 2 hb, 2 hb + 1 of the wave's stream
+          const int nx = hb + 1 < 2 * NPH ? nb + 16 + 2 * wv : -1;         // first row of item 0 of the next half
+          const char* smh = stg + (half * 16 + r0) * STG_LD;
+          lnb_lds_item<T, EXT_, XF_>(p, src, smh, lng, zone, nb + r0, lane, hb == 0 ? src.nd : 2 * src.ns + src.nd,
+                                     nx, dgam, dbet);
+          lnb_lds_item<T, EXT_, XF_>(p, src, smh + 8 * STG_LD, lng, zone + LNB_ZONE_ITEM, nb + r0 + 8, lane,
+                                     (hb == 0 ? src.ns : 2 * src.ns) + (nx >= 0 ? src.nd : 0), nx >= 0 ? nx + 8 : -1, dgam, dbet);
+        }
+        if (ph < 2) SMX_STAMP(4 + 2 * ph);
+      }
+    }
+  }
+#pragma unroll 1
+  for (int ph = 0; generic && ph < NPH; ++ph) {
     const int row_in_tile = ph * PH_ROWS;
     lds_barrier();
     if (wn == row_in_tile / WN) {                         // the wave row that owns these accumulator rows
