@@ -1081,6 +1081,87 @@ int smx_s2s_embed_step(int out_dtype, const int32_t* tok, const float* table, in
                        int64_t ldy, int32_t* pos, uint8_t* done, int B, int V, int D, int max_pos, void* stream);
 int smx_s2s_select(const smx_s2s_select_args* a, void* stream);
 
+/* ---- beam search over an indexed KV cache (csrc/attn_step.hip: smx_attn_step_rows; csrc/beam.hip: smx_s2s_beam_select) -----------------
+ * R = B W hypothesis rows, utterance b owns rows [b W, (b + 1) W).  No K / V is copied when the beams of an utterance reorder: the
+ * attention step looks the cache row of every key up instead (DESIGN.md I.22 holds the search's definition).
+ * smx_attn_step_rows: smx_attn_step (descriptor `s`, s.B = the query rows) with the cache row of a key looked up:
+ *   kv_div >= 1: query row r reads cache row r / kv_div and the n_keys entry r / kv_div, so K / V hold ceil(s.B / kv_div) rows and
+ *     n_keys as many entries (cross-attention: the W rows of an utterance share its projected memory; nothing is replicated).
+ *     kv_div > 1 takes neither k_new / v_new nor anc (SMX_EINVAL).
+ *   anc (s.B, cap) int32 on the device, leading dimension ld_anc >= cap, or NULL (self-attention): key j < n - 1 of row r is read from
+ *     cache row anc[r, j] at slot j; the step's own key is stored into row r, slot n - 1, and read from k_new / v_new as in
+ *     smx_attn_step.  An entry outside [0, s.B) makes that key contribute nothing (as if it were not there); it is compared before it
+ *     is used and never becomes an address.  Without k_new / v_new every key j < n goes through anc.  anc must not name, for one
+ *     row, the slot the call stores for another (row r', slot n[r'] - 1): the rows that read each other's cache rows are at the same
+ *     position, as the hypotheses of an utterance are.
+ *   Slots at or beyond n are never read, nor is any (row, slot) anc does not name.  The loads, the splits (a function of cap alone),
+ *   the workspace and the combination order are smx_attn_step's, the arithmetic is the same code: with anc[r, j] = r and kv_div = 1
+ *   the output has smx_attn_step's bits, with kv_div = W those of smx_attn_step over the cache replicated W times.  One extra 4-byte
+ *   load per key per lane group.  No atomics, nothing allocates or synchronises: capturable.
+ * smx_attn_step_rows_plan_query: smx_attn_step_plan_query for the indexed entry (the same geometry; kv_div / anc are checked).
+ * smx_s2s_beam_select: one step of the search over logits (R, V), two launches that are the same at every step.  Per utterance b
+ *   with done[b] == 0, at step n = n_tok[b]:
+ *   row launch (one wave per row r with score[r] > -inf): lp[r, v] exactly as smx_s2s_select computes it; the row's first
+ *     min(W, V) candidates in the order (logit descending, v ascending) - with `extra` (fp32 (R, V), leading dimension ldx: the hook of
+ *     a scorer) in the order (lp + extra descending, v ascending) - found by repeated arg-max "strictly after the previous
+ *     (value, index)", the logits are not changed; v == eos is left out while n < min_steps; candidate score = score[r] + lp[r, v]
+ *     (+ extra[r, v]: score[r] + (lp + extra)) in fp32; a candidate whose score is NaN or -inf is no candidate (a row holding a NaN
+ *     has none).  They go to the (R, W) workspace cand_val / cand_lp / cand_idx, their number to cand_n (R).
+ *   utterance launch (one workgroup per utterance): the W best candidates of the utterance's lists, by score descending, then by
+ *     (r - b W) V + v ascending; the i-th (parent p, token v) becomes slot i: tokens / logp_tok / anc rows of the parent (read into the
+ *     scratch tables s_*, a workgroup barrier, written back) plus [n] = v / lp / b W + p, score = the candidate score, tok = v.
+ *     A winner with v == eos - or any winner when n + 1 == cap - enters the utterance's pool instead (eos stored and counted;
+ *     final score = sum / (n + 1) when length_norm, else sum; the pool keeps the best W by final score, ties to the earlier
+ *     insertion: a full pool replaces its worst entry by a strictly better one) and its slot is dead: score -inf, tok = eos.  So is
+ *     every slot beyond the winners.  n_tok[b] = n + 1.  When the pool holds W entries, n + 1 == cap, or no slot is alive, done[b] and
+ *     done_row[b W .. (b + 1) W) are set and the pool is written, sorted by final score, to res_*.  A done utterance changes nothing.
+ *   W in [1, 128]; SMX_EINVAL for a NULL pointer (extra may be), sizes < 1, ldz < V, inv_temp <= 0, R beyond 2^24.  No atomics. */
+typedef struct smx_attn_step_rows_args {
+  smx_attn_step_args s;
+  const int32_t* anc;      /* (s.B, cap) device, or NULL */
+  int64_t ld_anc;
+  int32_t kv_div, pad_;
+} smx_attn_step_rows_args; /* 312 bytes */
+typedef struct smx_s2s_beam_args {
+  const void* logits;      /* (R, V) in dtype */
+  int64_t ldz;
+  const float* extra;      /* (R, V) fp32 or NULL */
+  int64_t ldx;
+  int32_t* tok;            /* (R) the next step's input tokens */
+  float* score;            /* (R) the running sums, -inf: a dead slot */
+  uint8_t* done_row;       /* (R) what smx_s2s_embed_step reads */
+  uint8_t* done;           /* (B) what the host polls */
+  int32_t* n_tok;          /* (B) */
+  int32_t* tokens;         /* (R, cap) */
+  float* logp_tok;         /* (R, cap) */
+  int32_t* anc;            /* (R, cap) */
+  int32_t* s_tokens;       /* (R, cap) scratch of the gathers */
+  float* s_logp;
+  int32_t* s_anc;
+  float* cand_val;         /* (R, W) workspace of the row launch */
+  float* cand_lp;
+  int32_t* cand_idx;
+  int32_t* cand_n;         /* (R) */
+  int32_t* pool_tokens;    /* (B, W, cap) the pool in insertion slots */
+  float* pool_logp;        /* (B, W, cap) */
+  int32_t* pool_len;       /* (B, W) */
+  float* pool_final;       /* (B, W) */
+  float* pool_sum;         /* (B, W) */
+  int32_t* pool_seq;       /* (B, W) insertion serial */
+  int32_t* pool_cnt;       /* (B) */
+  int32_t* pool_ins;       /* (B) insertions so far */
+  int32_t* res_tokens;     /* (B, W, cap) the pool sorted, written when the utterance ends */
+  float* res_logp;         /* (B, W, cap) */
+  int32_t* res_len;        /* (B, W) */
+  float* res_final;        /* (B, W) */
+  float* res_sum;          /* (B, W) */
+  double inv_temp;
+  int32_t dtype, B, W, V, cap, eos, min_steps, length_norm;
+} smx_s2s_beam_args;       /* 296 bytes */
+int smx_attn_step_rows(const smx_attn_step_rows_args* r, void* stream);
+int smx_attn_step_rows_plan_query(const smx_attn_step_rows_args* r, smx_attn_step_plan* plan);
+int smx_s2s_beam_select(const smx_s2s_beam_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -163,6 +163,21 @@ class S2SSelectArgs(ctypes.Structure):
                 (n, ctypes.c_int32) for n in ("dtype", "B", "V", "cap", "eos", "min_steps")]
 
 
+class AttnStepRowsArgs(ctypes.Structure):
+    """smx_attn_step_rows_args of include/smx.h."""
+    _fields_ = [("s", AttnStepArgs), ("anc", c_vp), ("ld_anc", c_i64), ("kv_div", ctypes.c_int32), ("pad_", ctypes.c_int32)]
+
+
+class S2SBeamArgs(ctypes.Structure):
+    """smx_s2s_beam_args of include/smx.h."""
+    _fields_ = [("logits", c_vp), ("ldz", c_i64), ("extra", c_vp), ("ldx", c_i64)] + [
+                (n, c_vp) for n in ("tok", "score", "done_row", "done", "n_tok", "tokens", "logp_tok", "anc", "s_tokens", "s_logp", "s_anc",
+                                    "cand_val", "cand_lp", "cand_idx", "cand_n", "pool_tokens", "pool_logp", "pool_len", "pool_final",
+                                    "pool_sum", "pool_seq", "pool_cnt", "pool_ins", "res_tokens", "res_logp", "res_len", "res_final",
+                                    "res_sum")] + [("inv_temp", ctypes.c_double)] + [
+                (n, ctypes.c_int32) for n in ("dtype", "B", "W", "V", "cap", "eos", "min_steps", "length_norm")]
+
+
 # name -> (restype, argtypes); mirrors include/smx.h one to one (tests/test_abi.py checks the export list)
 SIGNATURES = {
     "smx_version": (c_i, []),
@@ -319,6 +334,9 @@ SIGNATURES = {
     "smx_attn_step_plan_query": (c_i, [ctypes.POINTER(AttnStepArgs), ctypes.POINTER(AttnStepPlan)]),
     "smx_s2s_embed_step": (c_i, [c_i, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i, c_i, c_i, c_i, c_vp]),
     "smx_s2s_select": (c_i, [ctypes.POINTER(S2SSelectArgs), c_vp]),
+    "smx_attn_step_rows": (c_i, [ctypes.POINTER(AttnStepRowsArgs), c_vp]),
+    "smx_attn_step_rows_plan_query": (c_i, [ctypes.POINTER(AttnStepRowsArgs), ctypes.POINTER(AttnStepPlan)]),
+    "smx_s2s_beam_select": (c_i, [ctypes.POINTER(S2SBeamArgs), c_vp]),
 }
 
 _lib = None

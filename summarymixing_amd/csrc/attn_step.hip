@@ -45,9 +45,18 @@ __device__ __forceinline__ void as_meet(float& m, float& s, float (&acc)[E], flo
   m = M;
 }
 
+// what smx_attn_step_rows adds to the descriptor (read by the ROWS instantiations alone)
+struct AsRows {
+  const int32_t* anc; long ld_anc;      // (B, cap): the cache row that holds key j of query row b, or null
+  int kv_div;                           // query row b reads cache row (and n_keys entry) b / kv_div
+  int rows;                             // cache rows: an anc entry outside [0, rows) is a key that contributes nothing
+};
+
 // grid = (nsplit, H, B), block = 256.  ws (nsplit > 1): per (b, h, split) D + 2 floats [max, sum, acc (D)].
-template <typename T, int D>
-__global__ __launch_bounds__(AS_THREADS) void attn_step_kernel(smx_attn_step_args a, int nsplit, int chunk) {
+// ROWS (smx_attn_step_rows): the cache row of a key is looked up, not b - one 4-byte load per key per lane group, all AS_UNROLL of
+// them requested before the first K / V load that depends on one.  The arithmetic is the same code either way.
+template <typename T, int D, bool ROWS>
+__global__ __launch_bounds__(AS_THREADS) void attn_step_kernel(smx_attn_step_args a, AsRows x, int nsplit, int chunk) {
   constexpr int N = Grp16<T>::N;
   constexpr int LPK = (D / N) < 64 ? (D / N) : 64;      // lanes that share a key
   constexpr int G = D / (N * LPK);                      // 16-byte groups a lane holds of it
@@ -57,11 +66,15 @@ __global__ __launch_bounds__(AS_THREADS) void attn_step_kernel(smx_attn_step_arg
   const int split = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int l = lane % LPK, ks = lane / LPK;
-  int n = a.n_keys ? a.n_keys[b] : a.cap;
+  const int bk = ROWS ? b / x.kv_div : b;               // the cache row (and key count) of this query row
+  int n = a.n_keys ? a.n_keys[bk] : a.cap;
   if (n < 1 || n > a.cap) n = 0;                        // outside [1, cap]: a zero row, no store, no access
   const T* q = (const T*)a.q.p + (long)b * a.q.sb + (long)h * a.q.sh;
-  const T* K = (const T*)a.K.p + (long)b * a.K.sb + (long)h * a.K.sh;
-  const T* V = (const T*)a.V.p + (long)b * a.V.sb + (long)h * a.V.sh;
+  const T* Kh = (const T*)a.K.p + (long)h * a.K.sh;
+  const T* Vh = (const T*)a.V.p + (long)h * a.V.sh;
+  const T* K = Kh + (long)bk * a.K.sb;
+  const T* V = Vh + (long)bk * a.V.sb;
+  const int32_t* anc = ROWS && x.anc ? x.anc + (long)b * x.ld_anc : nullptr;
   const T* kn = a.k_new.p ? (const T*)a.k_new.p + (long)b * a.k_new.sb + (long)h * a.k_new.sh : nullptr;
   const T* vn = a.k_new.p ? (const T*)a.v_new.p + (long)b * a.v_new.sb + (long)h * a.v_new.sh : nullptr;
   const int last = kn && n > 0 ? n - 1 : -1;            // the key that is read from k_new / v_new
@@ -91,12 +104,21 @@ __global__ __launch_bounds__(AS_THREADS) void attn_step_kernel(smx_attn_step_arg
   for (int jw = j_lo + wave * KPW; jw < j_hi; jw += AS_WAVES * KPW * AS_UNROLL) {
     const int j0 = jw + ks;
     float kf[AS_UNROLL][E], vf[AS_UNROLL][E];
+    int row[AS_UNROLL];                                 // ROWS: the cache row of key u, -1: the key contributes nothing
+    if constexpr (ROWS) {
+#pragma unroll
+      for (int u = 0; u < AS_UNROLL; ++u) {
+        const int j = j0 + u * AS_WAVES * KPW;
+        row[u] = j < j_hi ? (anc && j != last ? anc[j] : bk) : -1;
+        if (row[u] < 0 || row[u] >= x.rows) row[u] = -1;  // compared BEFORE it becomes an address
+      }
+    }
 #pragma unroll
     for (int u = 0; u < AS_UNROLL; ++u) {
       const int j = j0 + u * AS_WAVES * KPW;
-      if (j < j_hi) {
-        const T* kr = j == last ? kn : K + (long)j * a.K.sr;
-        const T* vr = j == last ? vn : V + (long)j * a.V.sr;
+      if (ROWS ? row[u] >= 0 : j < j_hi) {
+        const T* kr = j == last ? kn : (ROWS ? Kh + (long)row[u] * a.K.sb : K) + (long)j * a.K.sr;
+        const T* vr = j == last ? vn : (ROWS ? Vh + (long)row[u] * a.V.sb : V) + (long)j * a.V.sr;
 #pragma unroll
         for (int g = 0; g < G; ++g) {
           float f[N];
@@ -120,7 +142,7 @@ __global__ __launch_bounds__(AS_THREADS) void attn_step_kernel(smx_attn_step_arg
       for (int e = 0; e < E; ++e) d = fmaf(qv[e], kf[u][e], d);
 #pragma unroll
       for (int off = LPK / 2; off > 0; off >>= 1) d += __shfl_xor(d, off, 64);     // (every lane of the wave takes part)
-      if (j < j_hi) {
+      if (ROWS ? row[u] >= 0 : j < j_hi) {
         const float sc = d * a.scale;
         const float M = fmaxf(m, sc);
         const float f = m == NEG_INF ? 0.f : expf(m - M), p = expf(sc - M);
@@ -237,35 +259,6 @@ __global__ __launch_bounds__(256) void s2s_embed_step_kernel(const int32_t* __re
   }
 }
 
-// what one lane has seen of its row: the running arg-max over the columns that take part, the online (max, sum exp((z - max) / T))
-// over the entries that are numbers, and whether any entry was a NaN
-struct SelRow {
-  float bv; int bi;
-  float m, s;
-  int nan;
-};
-
-// (the exponent is formed in fp64 from the ONE inverse temperature the whole kernel uses, then rounded once for expf)
-template <int N>
-__device__ __forceinline__ void sel_row_take(SelRow& r, const float (&x)[N], int c0, int skip, double inv_temp) {
-  float gm = NEG_INF;
-#pragma unroll
-  for (int j = 0; j < N; ++j) {
-    if (c0 + j != skip) argmax_take(r.bv, r.bi, x[j], c0 + j);
-    if (x[j] > gm) gm = x[j];
-    r.nan |= __builtin_isnan(x[j]) ? 1 : 0;
-  }
-  if (gm > r.m) {
-    r.s = r.m == NEG_INF ? 0.f : r.s * expf((float)((double)(r.m - gm) * inv_temp));
-    r.m = gm;
-  }
-  if (r.m != NEG_INF) {
-#pragma clang fp reassociate(off)
-#pragma unroll
-    for (int j = 0; j < N; ++j) r.s += __builtin_isnan(x[j]) ? 0.f : expf((float)((double)(x[j] - r.m) * inv_temp));
-  }
-}
-
 // grid = ceil(B / 4), block = 256: wave w of a block owns row 4 blockIdx.x + w
 template <typename T>
 __global__ __launch_bounds__(256) void s2s_select_kernel(smx_s2s_select_args a) {
@@ -316,7 +309,8 @@ static int as_check_op(const char* name, const smx_attn_operand& o, int es, bool
   return SMX_OK;
 }
 
-static int as_check(const smx_attn_step_args* a, bool need) {
+// cache_rows: the rows K / V hold (smx_attn_step: B; the indexed entry: ceil(B / kv_div))
+static int as_check(const smx_attn_step_args* a, bool need, int cache_rows = 0) {
   SMX_REQUIRE(a, "smx_attn_step: null descriptor");
   SMX_REQUIRE(a->B >= 1 && a->H >= 1 && a->D >= 1 && a->cap >= 1, "smx_attn_step: bad sizes B=%d H=%d D=%d cap=%d", a->B, a->H, a->D, a->cap);
   if (a->dtype != SMX_F32 && a->dtype != SMX_BF16) return fail(SMX_EUNSUPPORTED, "smx_attn_step: dtype %d (F32 or BF16)", a->dtype);
@@ -333,7 +327,8 @@ static int as_check(const smx_attn_step_args* a, bool need) {
   if ((rc = as_check_op("v_new", a->v_new, es, false, false))) return rc;
   SMX_REQUIRE((a->k_new.p == nullptr) == (a->v_new.p == nullptr), "smx_attn_step: k_new and v_new come together");
   if (need) {
-    SMX_REQUIRE(a->B == 1 || (a->K.sb >= (int64_t)a->D && a->V.sb >= (int64_t)a->D), "smx_attn_step: cache batch stride smaller than a row");
+    SMX_REQUIRE((cache_rows ? cache_rows : a->B) == 1 || (a->K.sb >= (int64_t)a->D && a->V.sb >= (int64_t)a->D),
+                "smx_attn_step: cache batch stride smaller than a row");
     SMX_REQUIRE(a->cap == 1 || (a->K.sr >= a->D && a->V.sr >= a->D), "smx_attn_step: cache row stride smaller than a row");
     SMX_REQUIRE(as_nsplit(a->cap) == 1 || a->workspace, "smx_attn_step: workspace is NULL (smx_attn_step_plan_query: workspace_bytes)");
     if (a->workspace && !aligned16(a->workspace)) return fail(SMX_EUNSUPPORTED, "smx_attn_step: workspace is not 16-byte aligned");
@@ -346,10 +341,7 @@ static int as_check(const smx_attn_step_args* a, bool need) {
 using namespace smx;
 #define STREAM reinterpret_cast<hipStream_t>(stream)
 
-extern "C" int smx_attn_step_plan_query(const smx_attn_step_args* a, smx_attn_step_plan* plan) {
-  SMX_REQUIRE(plan, "smx_attn_step_plan_query: plan is NULL");
-  const int rc = as_check(a, false);
-  if (rc) return rc;
+static int as_plan(const smx_attn_step_args* a, smx_attn_step_plan* plan) {
   const int n16 = a->dtype == SMX_BF16 ? 8 : 4;
   memset(plan, 0, sizeof(*plan));
   plan->lanes_per_key = a->D / n16 < 64 ? a->D / n16 : 64;
@@ -367,9 +359,8 @@ extern "C" int smx_attn_step_plan_query(const smx_attn_step_args* a, smx_attn_st
   return SMX_OK;
 }
 
-extern "C" int smx_attn_step(const smx_attn_step_args* a, void* stream) {
-  const int rc = as_check(a, true);
-  if (rc) return rc;
+template <bool ROWS>
+static void as_launch(const smx_attn_step_args* a, const AsRows& x, hipStream_t st) {
   const int nsplit = as_nsplit(a->cap), chunk = as_chunk(a->cap);
   smx_attn_step_args k = *a;
   if (nsplit == 1) k.workspace = nullptr;
@@ -377,13 +368,54 @@ extern "C" int smx_attn_step(const smx_attn_step_args* a, void* stream) {
   dispatch_dtype(a->dtype, [&](auto tag) {
     using T = decltype(tag);
     switch (a->D) {
-      case 64: hipLaunchKernelGGL((attn_step_kernel<T, 64>), grid, dim3(AS_THREADS), 0, STREAM, k, nsplit, chunk); break;
-      case 128: hipLaunchKernelGGL((attn_step_kernel<T, 128>), grid, dim3(AS_THREADS), 0, STREAM, k, nsplit, chunk); break;
-      case 256: hipLaunchKernelGGL((attn_step_kernel<T, 256>), grid, dim3(AS_THREADS), 0, STREAM, k, nsplit, chunk); break;
-      default: hipLaunchKernelGGL((attn_step_kernel<T, 512>), grid, dim3(AS_THREADS), 0, STREAM, k, nsplit, chunk); break;
+      case 64: hipLaunchKernelGGL((attn_step_kernel<T, 64, ROWS>), grid, dim3(AS_THREADS), 0, st, k, x, nsplit, chunk); break;
+      case 128: hipLaunchKernelGGL((attn_step_kernel<T, 128, ROWS>), grid, dim3(AS_THREADS), 0, st, k, x, nsplit, chunk); break;
+      case 256: hipLaunchKernelGGL((attn_step_kernel<T, 256, ROWS>), grid, dim3(AS_THREADS), 0, st, k, x, nsplit, chunk); break;
+      default: hipLaunchKernelGGL((attn_step_kernel<T, 512, ROWS>), grid, dim3(AS_THREADS), 0, st, k, x, nsplit, chunk); break;
     }
-    if (nsplit > 1) hipLaunchKernelGGL(attn_step_combine_kernel<T>, dim3(a->H, a->B), dim3(AS_THREADS), 0, STREAM, k, nsplit);
+    if (nsplit > 1) hipLaunchKernelGGL(attn_step_combine_kernel<T>, dim3(a->H, a->B), dim3(AS_THREADS), 0, st, k, nsplit);
   });
+}
+
+// what the indexed entry adds to as_check: -> the kernel's AsRows
+static int as_check_rows(const smx_attn_step_rows_args* r, bool need, AsRows* x) {
+  SMX_REQUIRE(r, "smx_attn_step_rows: null descriptor");
+  SMX_REQUIRE(r->kv_div >= 1, "smx_attn_step_rows: kv_div %d (must be >= 1)", r->kv_div);
+  const int rc = as_check(&r->s, need, r->s.B >= 1 ? (r->s.B + r->kv_div - 1) / r->kv_div : 0);
+  if (rc) return rc;
+  SMX_REQUIRE(r->kv_div == 1 || !r->anc, "smx_attn_step_rows: anc and kv_div %d do not combine (anc names cache rows itself)", r->kv_div);
+  SMX_REQUIRE(r->kv_div == 1 || !r->s.k_new.p, "smx_attn_step_rows: k_new / v_new with kv_div %d (the rows of a cache row would store into one slot)", r->kv_div);
+  SMX_REQUIRE(!r->anc || r->ld_anc >= r->s.cap, "smx_attn_step_rows: ld_anc %lld smaller than cap %d", (long long)r->ld_anc, r->s.cap);
+  x->anc = r->anc; x->ld_anc = (long)r->ld_anc; x->kv_div = r->kv_div;
+  x->rows = (r->s.B + r->kv_div - 1) / r->kv_div;
+  return SMX_OK;
+}
+
+extern "C" int smx_attn_step_plan_query(const smx_attn_step_args* a, smx_attn_step_plan* plan) {
+  SMX_REQUIRE(plan, "smx_attn_step_plan_query: plan is NULL");
+  const int rc = as_check(a, false);
+  return rc ? rc : as_plan(a, plan);
+}
+
+extern "C" int smx_attn_step_rows_plan_query(const smx_attn_step_rows_args* r, smx_attn_step_plan* plan) {
+  SMX_REQUIRE(plan, "smx_attn_step_rows_plan_query: plan is NULL");
+  AsRows x;
+  const int rc = as_check_rows(r, false, &x);
+  return rc ? rc : as_plan(&r->s, plan);
+}
+
+extern "C" int smx_attn_step_rows(const smx_attn_step_rows_args* r, void* stream) {
+  AsRows x;
+  const int rc = as_check_rows(r, true, &x);
+  if (rc) return rc;
+  as_launch<true>(&r->s, x, STREAM);
+  return check_launch("smx_attn_step_rows");
+}
+
+extern "C" int smx_attn_step(const smx_attn_step_args* a, void* stream) {
+  const int rc = as_check(a, true);
+  if (rc) return rc;
+  as_launch<false>(a, AsRows{nullptr, 0, 1, a->B}, STREAM);
   return check_launch("smx_attn_step");
 }
 

@@ -1,7 +1,10 @@
 // row_scan.h — the one-wave-per-row pass over a row of scores: users seqloss.hip (the forward reads with row_scan; the backward, whose
-// row is optional and which writes group by group, walks the same geometry with Grp16 and ROW_DEPTH) and ctcdec.hip (best path).
+// row is optional and which writes group by group, walks the same geometry with Grp16 and ROW_DEPTH), ctcdec.hip (best path) and the
+// seq2seq selection kernels (attn_step.hip, beam.hip), whose reading of a row (SelRow) is below.
 #pragma once
 #include "smx_common.h"
+
+#include <limits.h>
 
 namespace smx {
 
@@ -66,6 +69,36 @@ __device__ __forceinline__ void row_scan(const T* x, int V, int lane, F&& f) {
   for (int c = Vv + lane; c < V; c += 64) {              // the tail: fewer than N columns
     const float g[1] = {to_f32(x[c])};
     f(g, c);
+  }
+}
+
+// ---- the selection kernels' reading of a row of logits (attn_step.hip: smx_s2s_select; beam.hip: smx_s2s_beam_select)
+// what one lane has seen of its row: the running arg-max over the columns that take part, the online (max, sum exp((z - max) / T))
+// over the entries that are numbers, and whether any entry was a NaN
+struct SelRow {
+  float bv; int bi;
+  float m, s;
+  int nan;
+};
+
+// (the exponent is formed in fp64 from the ONE inverse temperature the whole kernel uses, then rounded once for expf)
+template <int N>
+__device__ __forceinline__ void sel_row_take(SelRow& r, const float (&x)[N], int c0, int skip, double inv_temp) {
+  float gm = NEG_INF;
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    if (c0 + j != skip) argmax_take(r.bv, r.bi, x[j], c0 + j);
+    if (x[j] > gm) gm = x[j];
+    r.nan |= __builtin_isnan(x[j]) ? 1 : 0;
+  }
+  if (gm > r.m) {
+    r.s = r.m == NEG_INF ? 0.f : r.s * expf((float)((double)(r.m - gm) * inv_temp));
+    r.m = gm;
+  }
+  if (r.m != NEG_INF) {
+#pragma clang fp reassociate(off)
+#pragma unroll
+    for (int j = 0; j < N; ++j) r.s += __builtin_isnan(x[j]) ? 0.f : expf((float)((double)(x[j] - r.m) * inv_temp));
   }
 }
 

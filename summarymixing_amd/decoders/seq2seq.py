@@ -1,4 +1,4 @@
-"""Greedy seq2seq decoding over ``[Transformer, seq_lin]``, the pair the Branchformer recipes hand to
+"""Greedy and beam seq2seq decoding over ``[Transformer, seq_lin]``, the pair the Branchformer recipes hand to
 ``speechbrain.decoders.S2STransformerBeamSearcher`` (recipes/*/ASR/transformer/hparams/branchformer_summarymixing.yaml,
 ``valid_search`` / ``test_search``), with the whole search on the device:
 
@@ -10,10 +10,18 @@ the host issues the same launches at every step: ``greedy_search`` loops over th
 ``poll_every`` steps, its only synchronisation; ``CapturedS2SGreedy`` captures ONE step as a graph - a plain chain, no parallel
 branches - and replays it in the same loop for every step of every utterance of its (B, S).
 
-``S2STransformerGreedySearcher`` and ``S2STransformerBeamSearcher`` take the recipes' constructor arguments.  Beam search
-(``beam_size > 1``), scorers (CTC / LM), ``TransformerLM`` and the beam options (eos threshold, attention shift, top-k) are not built
-and are refused by name; ``beam_size=1`` without a scorer runs the greedy search (``length_normalization`` is accepted: one hypothesis
-has nothing to rank, and the score stays the plain sum).  No parameters of their own: the modules are plain
+Beam search is the same step over R = B W hypothesis rows (``beam_search``, ``CapturedS2SBeam``, the module ``S2SBeamSearcher``):
+decode_step over a beam state - the self-attention caches are read through an ancestor table (smx_attn_step_rows), so no K / V is
+copied when the beams reorder, and the W rows of an utterance share its projected memory - -> seq_lin -> smx_s2s_beam_select (the W
+best candidates per utterance, the pool of finished hypotheses, the gathers of the histories and of the ancestor table, in place).
+The search is defined in DESIGN.md §I.22.  Still one captured chain, still polled through ``done`` (B bytes).
+
+``S2STransformerGreedySearcher`` and ``S2STransformerBeamSearcher`` take the recipes' constructor arguments and are what they were
+before beam search existed: ``S2STransformerBeamSearcher`` refuses ``beam_size > 1`` by name and ``beam_size=1`` without a scorer runs
+the greedy search (``length_normalization`` is accepted: one hypothesis has nothing to rank, and the score stays the plain sum).  A
+recipe that wants ``beam_size: 10`` points ``valid_search`` at ``summarymixing_amd.decoders.S2SBeamSearcher``, which takes the same
+arguments.  Scorers (CTC / LM), ``TransformerLM`` and the remaining beam options (eos threshold, attention shift, top-k) are not built
+and are refused by name everywhere.  No parameters of their own: the modules are plain
 attributes, as SpeechBrain's searchers hold them outside the checkpointed ``modules``.  SpeechBrain's ``decoders/seq2seq.py`` is not
 part of the reference tree: the constructor arguments are the recipes', the returned tuple ``(hyps, lengths, scores, log_probs)`` is
 written from memory."""
@@ -59,10 +67,10 @@ def _poll_loop(step, state, max_steps, poll_every):
             break
 
 
-def _begin(model, encoder_out, enc_len, bos, max_steps, state):
+def _begin(model, encoder_out, enc_len, bos, max_steps, state, **beam):
     if not encoder_out.is_cuda:
         raise RuntimeError(ops.NO_CPU)
-    state = model.make_decode_state(encoder_out, enc_len, max_steps, state=state)
+    state = model.make_decode_state(encoder_out, enc_len, max_steps, state=state, **beam)
     if state.cap != max_steps:
         raise ValueError(f"seq2seq search: max_steps {max_steps} exceeds the positional table ({state.cap} positions)")
     state.tok.fill_(bos)
@@ -118,6 +126,82 @@ class CapturedS2SGreedy:
         state = _begin(self.model, encoder_out, enc_len, self.bos, self.max_steps, self.state)
         _poll_loop(self.graph.replay, state, self.max_steps, poll_every)
         return _result(state)
+
+
+S2SBeamResult = collections.namedtuple("S2SBeamResult", "tokens lengths scores sums log_probs counts state")
+S2SBeamResult.__doc__ = """The pool of finished hypotheses per utterance, best first: tokens (B, W, cap) int32 (-1 at and beyond lengths),
+lengths (B, W) int32 (eos counted; 0: no such entry), scores (B, W) fp32 final scores (-inf: no such entry) = sums / lengths under
+length_normalization, else sums; sums (B, W) fp32 the summed log-probabilities, log_probs (B, W, cap) fp32 per token, counts (B) int32
+entries per utterance, state: the beam DecodeState - all on the device, all views of the state's buffers."""
+
+
+def _check_beam(beam_size):
+    if not 1 <= int(beam_size) <= 128:
+        raise ValueError(f"seq2seq beam search: beam_size must be in [1, 128], got {beam_size}")
+
+
+def beam_step(model, seq_lin, state, eos, min_steps, inv_temp, length_normalization):
+    """The launches of one beam-search step on the current stream: decode_step over the B W rows of the beam state -> seq_lin ->
+    smx_s2s_beam_select into the state.  -> the logits (B W, V) the selection read."""
+    pred = model.decode_step(state.tok, state)
+    W, b = seq_lin.w.weight, seq_lin.w.bias
+    logits, _ = F.linear_fwd(pred, F.wcast(W, pred.dtype), b.detach() if b is not None else None)
+    ops.s2s_beam_select(logits, state, eos, min_steps, inv_temp, length_normalization)
+    return logits
+
+
+def _beam_result(state):
+    return S2SBeamResult(state.res_tokens, state.res_len, state.res_final, state.res_sum, state.res_logp, state.pool_cnt, state)
+
+
+@torch.no_grad()
+def beam_search(model, seq_lin, encoder_out, enc_len, bos, eos, min_steps, max_steps, beam_size, temperature=1.0, length_normalization=True,
+                state=None, poll_every=8):
+    """Beam search of beam_size hypotheses per utterance over encoder_out (B, S, d), greedy_search's arguments otherwise (DESIGN.md
+    §I.22 defines the search): a hypothesis ends with its eos, an utterance ends when beam_size hypotheses have ended or at max_steps,
+    where the ones alive end as they are.  beam_size=1 gives greedy_search's bits.  state: a beam DecodeState of this (B, S, max_steps,
+    dtype, beam_size) to reuse.  -> S2SBeamResult."""
+    _check_args(bos, eos, min_steps, max_steps, temperature)
+    _check_beam(beam_size)
+    state = _begin(model, encoder_out, enc_len, bos, max_steps, state, beam=int(beam_size))
+    inv_temp, norm = 1.0 / float(temperature), bool(length_normalization)
+    _poll_loop(lambda: beam_step(model, seq_lin, state, eos, min_steps, inv_temp, norm), state, max_steps, poll_every)
+    return _beam_result(state)
+
+
+class CapturedS2SBeam:
+    """beam_search with ONE step captured as a graph, as CapturedS2SGreedy captures the greedy step: beam_step is a plain chain of
+    launches on one stream and every position is a device counter, so the same graph serves every step and every utterance of its
+    (B, S, max_steps, dtype, beam_size).  search(encoder_out, enc_len) equals beam_search bit for bit."""
+
+    def __init__(self, model, seq_lin, B, S, max_steps, dtype, bos, eos, beam_size, min_steps=0, temperature=1.0, length_normalization=True,
+                 device="cuda"):
+        _check_args(bos, eos, min_steps, max_steps, temperature)
+        _check_beam(beam_size)
+        self.model, self.seq_lin, self.bos, self.max_steps, self.beam_size = model, seq_lin, int(bos), int(max_steps), int(beam_size)
+        d = model.custom_tgt_module.layers[0].d_model
+        eos, min_steps, inv_temp, norm = int(eos), int(min_steps), 1.0 / float(temperature), bool(length_normalization)
+        with torch.no_grad():
+            mem = torch.zeros((B, S, d), dtype=dtype, device=device)
+            self.state = _begin(model, mem, None, self.bos, self.max_steps, None, beam=self.beam_size)
+
+            def run():
+                beam_step(model, seq_lin, self.state, eos, min_steps, inv_temp, norm)
+            s = torch.cuda.Stream(device=device)
+            s.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(s):
+                run()                                         # warm-up: weight casts and packed images exist before the capture
+            torch.cuda.current_stream().wait_stream(s)
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph, stream=s):
+                run()
+            self.state.reset()
+
+    @torch.no_grad()
+    def search(self, encoder_out, enc_len=None, poll_every=8):
+        state = _begin(self.model, encoder_out, enc_len, self.bos, self.max_steps, self.state, beam=self.beam_size)
+        _poll_loop(self.graph.replay, state, self.max_steps, poll_every)
+        return _beam_result(state)
 
 
 # beam-search options and the one value of each that leaves the greedy search what it is
@@ -190,3 +274,52 @@ class S2STransformerBeamSearcher(S2STransformerGreedySearcher):
                 raise NotImplementedError(f"S2STransformerBeamSearcher: {k}={v!r} is a beam-search option, which is not built")
         super().__init__(modules, bos_index, eos_index, min_decode_ratio, max_decode_ratio, temperature)
         self.beam_size = 1
+
+
+# the beam options S2SBeamSearcher does not build, and the one value of each that it takes
+_BEAM_UNBUILT = {"topk": 1, "using_eos_threshold": False, "using_max_attn_shift": False}
+_BEAM_IGNORED = ("eos_threshold", "max_attn_shift", "minus_inf")      # parameters of options that are off
+
+
+class S2SBeamSearcher(S2STransformerGreedySearcher):
+    """Beam search over modules = [Transformer, seq_lin] with the recipes' ``valid_search`` / ``test_search`` arguments (upstream's
+    base-class name; here it is the Transformer searcher).  forward(enc_states (B, S, d), wav_len (B) relative) -> (hyps, lengths,
+    scores, log_probs) of the BEST hypothesis per utterance, the greedy searcher's tuple: hyps exclude eos, scores are the final scores
+    (the summed log-probabilities over the length, eos counted, under length_normalization), log_probs (B, max_steps) per token - from
+    ONE host copy at the end.  beam_size in [1, 128]; a scorer, using_eos_threshold, using_max_attn_shift and topk > 1 are not built and
+    are refused by name."""
+
+    def __init__(self, modules, bos_index, eos_index, min_decode_ratio, max_decode_ratio, beam_size, scorer=None, temperature=1.0,
+                 length_normalization=True, **beam_options):
+        if scorer is not None:
+            raise NotImplementedError("S2SBeamSearcher: a scorer (CTC / LM scoring) is not built (the selection kernel has the hook, "
+                                      "smx_s2s_beam_select's extra)")
+        if isinstance(beam_size, bool) or int(beam_size) != beam_size or not 1 <= beam_size <= 128:
+            raise NotImplementedError(f"S2SBeamSearcher: beam_size={beam_size} is outside [1, 128], what the selection kernel holds")
+        for k, v in beam_options.items():
+            if k in _BEAM_IGNORED:
+                continue
+            if k not in _BEAM_UNBUILT:
+                raise TypeError(f"S2SBeamSearcher: unknown argument {k!r}")
+            if v != _BEAM_UNBUILT[k]:
+                raise NotImplementedError(f"S2SBeamSearcher: {k}={v!r} is not built")
+        super().__init__(modules, bos_index, eos_index, min_decode_ratio, max_decode_ratio, temperature)
+        self.beam_size, self.length_normalization = int(beam_size), bool(length_normalization)
+
+    def forward(self, enc_states, wav_len):
+        if not enc_states.is_cuda:
+            raise RuntimeError(ops.NO_CPU)
+        B, S, _ = enc_states.shape
+        max_steps, min_steps = int(S * self.max_decode_ratio), int(S * self.min_decode_ratio)
+        enc_len = None if wav_len is None else torch.round(wav_len.to(enc_states.device) * S)
+        r = beam_search(self.model, self.fc, enc_states, enc_len, self.bos_index, self.eos_index, min_steps, max_steps, self.beam_size,
+                        self.temperature, self.length_normalization)
+        cap = r.tokens.shape[2]
+        packed = torch.cat([r.tokens[:, 0].double(), r.log_probs[:, 0].double(), r.lengths[:, :1].double(), r.scores[:, :1].double()], 1).cpu()
+        tokens, log_probs = packed[:, :cap].long(), packed[:, cap:2 * cap].float()          # the one host copy, taken apart
+        counts, scores = packed[:, 2 * cap].long(), packed[:, 2 * cap + 1].float()
+        hyps = []
+        for b in range(B):
+            h = [int(k) for k in tokens[b, :int(counts[b])]]
+            hyps.append(h[:h.index(self.eos_index)] if self.eos_index in h else h)
+        return hyps, torch.tensor([len(h) for h in hyps]), scores, log_probs

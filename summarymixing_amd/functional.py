@@ -1657,11 +1657,12 @@ def attention_in_proj(att, x, lo, hi, out=None):
     return linear_fwd(x, Wc, bd, out=out)[0]
 
 
-def attention_step_sublayer(att, H, x, kv, n_keys, res, self_attn, out=None, workspace=None):
+def attention_step_sublayer(att, H, x, kv, n_keys, res, self_attn, out=None, workspace=None, anc=None, kv_div=None):
     """The attention sublayer of ONE decoding position over a cache, inference only: x (B, d) rows, kv the packed cache (B, cap, 2, H, D)
     - a layer's self-attention keys / values so far (self_attn: the d -> 3d GEMM on x, whose k / v rows smx_attn_step stores at slot
     n_keys - 1 before it attends) or its projected memory (cross-attention: the d -> d query Linear alone) - and n_keys (B) int32 on the
     device.  out (B, H, D) / workspace: the attention launch's output and split workspace when the caller owns them (ops.attention_step).
+    anc / kv_div: the indexed cache of a beam search, handed to ops.attention_step as they are (neither: exactly the plain call).
     -> res + out_proj(attention), the out-projection's residual epilogue as in attention_sublayer."""
     Wo, bo = att.out_proj.weight, att.out_proj.bias
     B, d = x.shape
@@ -1671,7 +1672,8 @@ def attention_step_sublayer(att, H, x, kv, n_keys, res, self_attn, out=None, wor
     else:
         q, kn, vn = attention_in_proj(att, x, 0, 1).view(B, H, D), None, None
     K, V = kv.unbind(2)
-    o = ops.attention_step(q, K, V, n_keys, kn, vn, scale=1.0 / math.sqrt(D), out=out, workspace=workspace)
+    rows = {} if anc is None and kv_div is None else {"anc": anc, "kv_div": kv_div}
+    o = ops.attention_step(q, K, V, n_keys, kn, vn, scale=1.0 / math.sqrt(D), out=out, workspace=workspace, **rows)
     return linear_fwd(o.view(B, d), wcast(Wo, x.dtype), bo.detach() if bo is not None else None, res=res)[0]
 
 

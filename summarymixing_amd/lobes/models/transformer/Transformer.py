@@ -207,26 +207,29 @@ class TransformerDecoderLayer(nn.Module):
             return y, bwd, ks, kc
         return run
 
-    def _step(self, x, compute, self_kv, cross_kv, pos, mem_len, attn_out=None, attn_ws=None):
+    def _step(self, x, compute, self_kv, cross_kv, pos, mem_len, attn_out=None, attn_ws=None, anc=None, kv_div=None):
         """ONE decoding position, inference only: x (B, d) stream rows -> the layer's output rows.  _run's sublayers at need=False in
         the same order and dtypes, the two smx_attn_fwd calls replaced by smx_attn_step over the layer's caches (self_kv (B, cap, 2,
         H, D), the keys / values so far, slot pos - 1 written here; cross_kv (B, S, 2, H, D), the projected memory); no weights.
         attn_out / attn_ws: the state's attention output and workspace, shared by the launches of a step (each is consumed by its
-        out-projection before the next attention writes it: one stream)."""
+        out-projection before the next attention writes it: one stream).  anc / kv_div (a beam state): x holds B W rows, the
+        self-attention reads its keys through the ancestor table anc, the W rows of an utterance share its row of cross_kv / mem_len."""
         kw = {"out": attn_out, "workspace": attn_ws}
+        skw = dict(kw, anc=anc) if anc is not None else kw
+        ckw = dict(kw, kv_div=kv_div) if kv_div is not None else kw
         n1, n2, n3 = self.norm1.norm, self.norm2.norm, self.norm3.norm
         f0, f3 = self.pos_ffn.ffn[0], self.pos_ffn.ffn[3]
         sa, ca, H = self.self_attn.att, self.multihead_attn.att, self.nhead
         if self.normalize_before:
             h1, _ = F.ln_fwd(x, n1.weight, n1.bias, n1.eps, False, out_dtype=compute)
-            x1 = F.attention_step_sublayer(sa, H, h1, self_kv, pos, x, True, **kw)
+            x1 = F.attention_step_sublayer(sa, H, h1, self_kv, pos, x, True, **skw)
             h2, _ = F.ln_fwd(x1, n2.weight, n2.bias, n2.eps, False, out_dtype=compute)
-            x2 = F.attention_step_sublayer(ca, H, h2, cross_kv, mem_len, x1, False, **kw)
+            x2 = F.attention_step_sublayer(ca, H, h2, cross_kv, mem_len, x1, False, **ckw)
             P = {"ln_w": n3.weight, "ln_b": n3.bias, "W1": f0.weight, "b1": f0.bias, "W2": f3.weight, "b2": f3.bias}
             return F.ffn_module_fwd(x2, P, self.act, False, compute, alpha=1.0, p=0.0, eps=n3.eps)[0]
-        t1 = F.attention_step_sublayer(sa, H, x, self_kv, pos, x, True, **kw)
+        t1 = F.attention_step_sublayer(sa, H, x, self_kv, pos, x, True, **skw)
         x1, _ = F.ln_fwd(t1, n1.weight, n1.bias, n1.eps, False)
-        t2 = F.attention_step_sublayer(ca, H, x1, cross_kv, mem_len, x1, False, **kw)
+        t2 = F.attention_step_sublayer(ca, H, x1, cross_kv, mem_len, x1, False, **ckw)
         x2, _ = F.ln_fwd(t2, n2.weight, n2.bias, n2.eps, False)
         a, _ = F.linear_fwd(x2, F.wcast(f0.weight, compute), f0.bias, self.act, None, wparam=f0.weight)
         t3, _ = F.linear_fwd(a, F.wcast(f3.weight, compute), f3.bias, L.ACT_NONE, None, res=x2, wparam=f3.weight)
@@ -341,7 +344,7 @@ class TransformerDecoder(nn.Module):
         which state.pos counts this position) -> (B, d) in the compute dtype.  Writes slot pos - 1 of every layer's self-attention
         cache; nothing synchronises with the host."""
         for layer, skv, ckv in zip(self.layers, state.self_kv, state.cross_kv):
-            x = layer._step(x, state.compute, skv, ckv, state.pos, state.mem_len, state.attn_out, state.attn_ws)
+            x = layer._step(x, state.compute, skv, ckv, state.pos, state.mem_len, state.attn_out, state.attn_ws, **state.rows_kw)
         n = self.norm.norm
         return F.ln_fwd(x, n.weight, n.bias, n.eps, False, out_dtype=state.compute)[0]
 
@@ -353,23 +356,50 @@ class DecodeState:
     mem_len (B) int32: encoder lengths (the cross-attention key count).  The search's own vectors: tok (B) int32 the next input token,
     done (B) uint8, n_tok (B) int32, score (B) fp32, tokens (B, cap) int32, logp_tok (B, cap) fp32.  Every step reads and advances
     these in kernels; the host never needs their values to issue the next step.  attn_out (B, H, D) / attn_ws: the output and the split
-    workspace of the step's attention launches, owned here so that a step's 2 x layers smx_attn_step calls allocate nothing."""
+    workspace of the step's attention launches, owned here so that a step's 2 x layers smx_attn_step calls allocate nothing.
 
-    def __init__(self, B, S, cap, H, D, layers, compute, stream, device):
-        self.B, self.S, self.cap, self.compute, self.stream = B, S, cap, compute, stream
-        self.self_kv = [torch.zeros((B, cap, 2, H, D), dtype=compute, device=device) for _ in range(layers)]
+    beam=W (beam search, decoders.seq2seq.beam_search): R = B W hypothesis rows, utterance b owns rows [b W, (b + 1) W).  self_kv,
+    attn_out, pos, tok, score, tokens, logp_tok have R rows; cross_kv and mem_len stay per utterance (kv_div = W: nothing is
+    replicated); done and n_tok stay per utterance, row_done (R) is what the embedding step reads.  anc (R, cap) int32 names, per
+    row and position, the cache row that holds that position's key - the beams reorder by rewriting anc, no K / V moves
+    (smx_attn_step_rows).  Then the buffers of smx_s2s_beam_select: the scratch tables of its gathers (s_*), the candidate workspace
+    (cand_*), the pool of finished hypotheses (pool_*) and the sorted result (res_*).  Without beam none of these exist, row_done is
+    done and every call is the plain one."""
+
+    def __init__(self, B, S, cap, H, D, layers, compute, stream, device, beam=None):
+        self.B, self.S, self.cap, self.compute, self.stream, self.beam = B, S, cap, compute, stream, beam
+        R = self.rows = B if beam is None else B * beam
+        self.self_kv = [torch.zeros((R, cap, 2, H, D), dtype=compute, device=device) for _ in range(layers)]
         self.cross_kv = [torch.empty((B, S, 2, H, D), dtype=compute, device=device) for _ in range(layers)]
-        self.attn_out = torch.empty((B, H, D), dtype=compute, device=device)
-        self.attn_ws = torch.empty((max(1, ops.attention_step_workspace(B, H, D, cap, compute), ops.attention_step_workspace(B, H, D, S, compute)),),
+        self.attn_out = torch.empty((R, H, D), dtype=compute, device=device)
+        self.attn_ws = torch.empty((max(1, ops.attention_step_workspace(R, H, D, cap, compute), ops.attention_step_workspace(R, H, D, S, compute)),),
                                    dtype=torch.float32, device=device)
-        self.pos = torch.zeros((B,), dtype=torch.int32, device=device)
+        self.pos = torch.zeros((R,), dtype=torch.int32, device=device)
         self.mem_len = torch.empty((B,), dtype=torch.int32, device=device)
-        self.tok = torch.zeros((B,), dtype=torch.int32, device=device)
+        self.tok = torch.zeros((R,), dtype=torch.int32, device=device)
         self.done = torch.zeros((B,), dtype=torch.uint8, device=device)
         self.n_tok = torch.zeros((B,), dtype=torch.int32, device=device)
-        self.score = torch.zeros((B,), dtype=torch.float32, device=device)
-        self.tokens = torch.full((B, cap), -1, dtype=torch.int32, device=device)
-        self.logp_tok = torch.zeros((B, cap), dtype=torch.float32, device=device)
+        self.score = torch.zeros((R,), dtype=torch.float32, device=device)
+        self.tokens = torch.full((R, cap), -1, dtype=torch.int32, device=device)
+        self.logp_tok = torch.zeros((R, cap), dtype=torch.float32, device=device)
+        self.row_done, self.rows_kw = self.done, {}
+        if beam is not None:
+            W = beam
+
+            def buf(shape, dtype):
+                return torch.zeros(shape, dtype=dtype, device=device)
+            i32, f32 = torch.int32, torch.float32
+            self.row_done = buf((R,), torch.uint8)
+            self.anc = buf((R, cap), i32)
+            self.rows_kw = {"anc": self.anc, "kv_div": W}
+            self.s_tokens, self.s_logp, self.s_anc = buf((R, cap), i32), buf((R, cap), f32), buf((R, cap), i32)
+            self.cand_val, self.cand_lp, self.cand_idx, self.cand_n = buf((R, W), f32), buf((R, W), f32), buf((R, W), i32), buf((R,), i32)
+            self.pool_tokens, self.pool_logp = buf((B, W, cap), i32), buf((B, W, cap), f32)
+            self.pool_len, self.pool_final, self.pool_sum, self.pool_seq = buf((B, W), i32), buf((B, W), f32), buf((B, W), f32), buf((B, W), i32)
+            self.pool_cnt, self.pool_ins = buf((B,), i32), buf((B,), i32)
+            self.res_tokens, self.res_logp = buf((B, W, cap), i32), buf((B, W, cap), f32)
+            self.res_len, self.res_final, self.res_sum = buf((B, W), i32), buf((B, W), f32), buf((B, W), f32)
+            self._reset_beam()
 
     def reset(self):
         """Back to position 0 with an empty hypothesis, in place (the buffers a captured step points at stay where they are).  The
@@ -377,3 +407,16 @@ class DecodeState:
         for t in (self.pos, self.tok, self.done, self.n_tok, self.score, self.logp_tok):
             t.zero_()
         self.tokens.fill_(-1)
+        if self.beam is not None:
+            self._reset_beam()
+
+    def _reset_beam(self):
+        """Slot 0 of every utterance alive with score 0, the others dead; no ancestors (-1 names no row); an empty pool and result.
+        The pool's rows, the scratch tables and the candidate workspace are written before they are read: no clearing."""
+        self.score.fill_(float("-inf"))
+        self.score.view(self.B, self.beam)[:, 0] = 0.0
+        self.anc.fill_(-1)
+        for t in (self.row_done, self.pool_cnt, self.pool_ins, self.res_len, self.res_sum, self.res_logp):
+            t.zero_()
+        self.res_tokens.fill_(-1)
+        self.res_final.fill_(float("-inf"))

@@ -247,13 +247,17 @@ class TransformerASR(nn.Module):
         return prediction, multihead_attns[-1]
 
     @torch.no_grad()
-    def make_decode_state(self, encoder_out, enc_len=None, max_steps=None, state=None):
+    def make_decode_state(self, encoder_out, enc_len=None, max_steps=None, state=None, beam=None):
         """The state of KV-cached decoding over encoder_out (B, S, d) (Transformer.DecodeState): per decoder layer an empty
         self-attention cache of cap = max_steps positions (default and bound: the positional table's max_length) and the layer's
         cross-attention keys / values, computed HERE, once, by the d -> 2d Linear on rows [d, 3d) of multihead_attn's in_proj_weight
         (functional.attention_in_proj, the projection decode runs again for every prefix).  enc_len: the absolute encoder lengths (B),
         as decode takes them; None: all S.  state: a state of the same (B, S, cap, dtype) to refill in place for the next utterance -
-        its buffers stay where a captured step expects them.  Nothing synchronises with the host."""
+        its buffers stay where a captured step expects them.  beam=W: the state of a beam search of W hypotheses per utterance
+        (Transformer.DecodeState): self-attention caches of B W rows read through an ancestor table, the cross-attention keys /
+        values still projected once per utterance; beam=None is the state it always was.  Nothing synchronises with the host."""
+        if beam is not None and not 1 <= int(beam) <= 128:
+            raise ValueError(f"make_decode_state: beam must be in [1, 128], got {beam}")
         if self.num_decoder_layers <= 0:
             raise RuntimeError("TransformerASR was built with num_decoder_layers=0: there is no decoder to make a decoding state for")
         if self.training:
@@ -274,10 +278,13 @@ class TransformerASR(nn.Module):
         compute = encoder_out.dtype
         stream = F.stream_dtype(compute) if layers[0].normalize_before else compute
         if state is None:
-            state = DecodeState(B, S, cap, H, d // H, len(layers), compute, stream, encoder_out.device)
+            state = (DecodeState(B, S, cap, H, d // H, len(layers), compute, stream, encoder_out.device) if beam is None else
+                     DecodeState(B, S, cap, H, d // H, len(layers), compute, stream, encoder_out.device, beam=int(beam)))
         elif (state.B, state.S, state.cap, state.compute) != (B, S, cap, compute) or state.pos.device != encoder_out.device:
             raise ValueError(f"make_decode_state: the state holds (B, S, cap, dtype) = {(state.B, state.S, state.cap, state.compute)}, "
                              f"this call needs {(B, S, cap, compute)}")
+        elif state.beam != beam:
+            raise ValueError(f"make_decode_state: the state holds beam = {state.beam}, this call needs {beam}")
         else:
             state.reset()
         mem2 = ops.rows2d(encoder_out if encoder_out.is_contiguous() else encoder_out.contiguous())
@@ -296,17 +303,19 @@ class TransformerASR(nn.Module):
         smx_s2s_embed_step (embedding * sqrt(d) + the positional row of the DEVICE counter state.pos, which it advances), then per
         layer the sublayers of decode with smx_attn_step over the state's caches in place of smx_attn_fwd, then the final LayerNorm.
         No attention weights.  A row fed beyond the state's cap positions is marked done (state.done) and yields zeros from its
-        self-attention; the host is never asked.  Eval mode only."""
+        self-attention; the host is never asked.  Eval mode only.  Over a beam state (make_decode_state(beam=W)) tokens and the
+        prediction have B W rows, the self-attention reads its keys through the state's ancestor table and the W rows of an utterance
+        share its projected memory (smx_attn_step_rows)."""
         if self.training:
             raise RuntimeError("TransformerASR.decode_step: decoding runs in eval mode only (self.training is set)")
         if not tokens.is_cuda:
             raise RuntimeError(ops.NO_CPU)
-        if tokens.dim() != 1 or tokens.is_floating_point() or tokens.shape[0] != state.B:
-            raise ValueError(f"tokens must be ({state.B},) integer tokens, got {tokens.dtype} {tuple(tokens.shape)}")
+        if tokens.dim() != 1 or tokens.is_floating_point() or tokens.shape[0] != state.rows:
+            raise ValueError(f"tokens must be ({state.rows},) integer tokens, got {tokens.dtype} {tuple(tokens.shape)}")
         tok = tokens if (tokens.dtype == torch.int32 and tokens.is_contiguous()) else tokens.to(torch.int32).contiguous()
         emb = self.custom_tgt_module.layers[0]
         pe = self.positional_encoding.pe[0] if self.positional_encoding_type == "fixed_abs_sine" else None
-        x = ops.s2s_embed_step(tok, emb.emb.Embedding.weight.detach(), pe, state.pos, state.done, state.cap, out_dtype=state.stream)
+        x = ops.s2s_embed_step(tok, emb.emb.Embedding.weight.detach(), pe, state.pos, state.row_done, state.cap, out_dtype=state.stream)
         return self.decoder.step(x, state)
 
     def encode(self, src, wav_len=None, pad_idx=0, dynchunktrain_config=None, masked_false_or_true: Optional[bool] = True):

@@ -1684,11 +1684,16 @@ def _step_operand(t, B, H, D, what, cap=None):
     return L.AttnOperand(t.data_ptr(), sb if B > 1 else 0, (st[1] if cap > 1 else 0) if cap is not None else 0, sh if H > 1 else 0, sd)
 
 
-def attention_step_plan(B, H, D, cap, dtype=torch.float32):
-    """smx_attn_step_plan_query for a problem size (needs no GPU): a dict of the launch geometry.  Raises where the library refuses."""
+def attention_step_plan(B, H, D, cap, dtype=torch.float32, kv_div=None):
+    """smx_attn_step_plan_query for a problem size (needs no GPU): a dict of the launch geometry.  Raises where the library refuses.
+    kv_div: ask smx_attn_step_rows_plan_query, the indexed entry's (B = the query rows), instead."""
     a = L.AttnStepArgs(dtype=_DT.get(dtype, -1), B=B, H=H, D=D, cap=cap, scale=1.0)
     p = L.AttnStepPlan()
-    L.check(L.lib().smx_attn_step_plan_query(ctypes.byref(a), ctypes.byref(p)), "smx_attn_step_plan_query")
+    if kv_div is None:
+        L.check(L.lib().smx_attn_step_plan_query(ctypes.byref(a), ctypes.byref(p)), "smx_attn_step_plan_query")
+    else:
+        r = L.AttnStepRowsArgs(s=a, kv_div=int(kv_div))
+        L.check(L.lib().smx_attn_step_rows_plan_query(ctypes.byref(r), ctypes.byref(p)), "smx_attn_step_rows_plan_query")
     return dict(lanes_per_key=p.lanes_per_key, keys_per_wave=p.keys_per_wave, waves=p.waves, threads=p.threads, splits=p.splits,
                 chunk=p.chunk, launches=p.launches, lds_bytes=p.lds_bytes, grid=tuple(p.grid), workspace_bytes=p.workspace_bytes)
 
@@ -1705,34 +1710,45 @@ def attention_step_workspace(B, H, D, cap, dtype=torch.float32):
     return n
 
 
-def attention_step(q, K, V, n_keys=None, k_new=None, v_new=None, scale=None, out=None, workspace=None):
+def attention_step(q, K, V, n_keys=None, k_new=None, v_new=None, scale=None, out=None, workspace=None, anc=None, kv_div=None):
     """One query row per (batch row, head) over a cache: q (B, H, D), K / V (B, cap, H, D), n_keys (B) int32 on the device (None:
     all cap keys) -> o (B, H, D) in q's dtype (smx_attn_step).  With k_new / v_new (B, H, D) the call first stores them into cache slot
     n_keys[b] - 1.  All operands are read in place through their strides (unit stride along D, 16-byte aligned rows).  out / workspace
     (fp32, at least attention_step_workspace elements): buffers the caller owns - a decoding state hands in its own, so a step
-    allocates nothing here; fresh ones otherwise."""
+    allocates nothing here; fresh ones otherwise.
+    anc / kv_div (beam search; smx_attn_step_rows, the same arithmetic over an indexed cache): with kv_div = W query row r reads cache
+    row and n_keys entry r // W, so K / V hold B / W rows and n_keys as many entries; with anc (B, cap) int32 on the device key
+    j < n - 1 of row r is read from cache row anc[r, j] (an entry outside [0, B) removes the key).  With neither, smx_attn_step."""
     if not (q.is_cuda and K.is_cuda and V.is_cuda):
         raise RuntimeError(NO_CPU)
     B, H, D = q.shape
     cap = K.shape[1]
+    rows = anc is not None or kv_div is not None
+    kv_div = 1 if kv_div is None else int(kv_div)
+    Bc = -(-B // kv_div) if kv_div >= 1 else B                # cache rows (the library refuses kv_div < 1)
     assert K.dtype == q.dtype and V.dtype == q.dtype and (k_new is None) == (v_new is None)
     assert k_new is None or (k_new.dtype == q.dtype and v_new.dtype == q.dtype)
-    assert n_keys is None or (n_keys.is_cuda and n_keys.dtype == torch.int32 and n_keys.is_contiguous() and n_keys.shape == (B,))
+    assert n_keys is None or (n_keys.is_cuda and n_keys.dtype == torch.int32 and n_keys.is_contiguous() and n_keys.shape == (Bc,))
+    assert anc is None or (anc.is_cuda and anc.dtype == torch.int32 and tuple(anc.shape) == (B, cap) and anc.stride(1) == 1)
     if out is None:
         out = torch.empty((B, H, D), dtype=q.dtype, device=q.device)
     a = L.AttnStepArgs(dtype=dt(q), B=B, H=H, D=D, cap=cap, scale=float(D ** -0.5 if scale is None else scale), n_keys=_p(n_keys))
     a.q, a.o = _step_operand(q, B, H, D, "q"), _step_operand(out, B, H, D, "out")
     a.k_new, a.v_new = _step_operand(k_new, B, H, D, "k_new"), _step_operand(v_new, B, H, D, "v_new")
-    a.K, a.V = _step_operand(K, B, H, D, "K", cap), _step_operand(V, B, H, D, "V", cap)
+    a.K, a.V = _step_operand(K, Bc, H, D, "K", cap), _step_operand(V, Bc, H, D, "V", cap)
     need = attention_step_workspace(B, H, D, cap, q.dtype)
     if need:
         if workspace is None:
             workspace = torch.empty((need,), dtype=torch.float32, device=q.device)
         assert workspace.is_cuda and workspace.dtype == torch.float32 and workspace.is_contiguous() and workspace.numel() >= need
         a.workspace = workspace.data_ptr()
-    tok = _pb(f"attn_step {'bf16' if _es(q) == 2 else 'f32'} (B {B}, cap {cap}, H {H}, D {D})" + (" self" if k_new is not None else ""),
-              2 * B * cap * H * D * _es(q), 4.0 * B * H * cap * D)
-    L.check(L.lib().smx_attn_step(ctypes.byref(a), _stream()), "smx_attn_step")
+    tok = _pb(f"attn_step {'bf16' if _es(q) == 2 else 'f32'} (B {B}, cap {cap}, H {H}, D {D})" + (" self" if k_new is not None else "") +
+              (" rows" if rows else ""), 2 * B * cap * H * D * _es(q), 4.0 * B * H * cap * D)
+    if rows:
+        r = L.AttnStepRowsArgs(s=a, anc=_p(anc), ld_anc=anc.stride(0) if anc is not None else 0, kv_div=kv_div)
+        L.check(L.lib().smx_attn_step_rows(ctypes.byref(r), _stream()), "smx_attn_step_rows")
+    else:
+        L.check(L.lib().smx_attn_step(ctypes.byref(a), _stream()), "smx_attn_step")
     _pe(tok)
     return out
 
@@ -1775,3 +1791,37 @@ def s2s_select(logits, tok, done, n_tok, score, tokens, logp_tok, eos, min_steps
     a = L.S2SSelectArgs(logits=pz, ldz=ldz, forced=_p(forced), tok=_p(tok), done=_p(done), n_tok=_p(n_tok), score=_p(score), tokens=_p(tokens),
                         logp_tok=_p(logp_tok), inv_temp=float(inv_temp), dtype=dt(logits), B=B, V=V, cap=cap, eos=int(eos), min_steps=int(min_steps))
     L.check(L.lib().smx_s2s_select(ctypes.byref(a), _stream()), "smx_s2s_select")
+
+
+def s2s_beam_select(logits, st, eos, min_steps=0, inv_temp=1.0, length_norm=True, extra=None):
+    """The selection of one beam-search step over logits (B W, V) (smx_s2s_beam_select): per utterance the W best of its rows'
+    candidates score + log-probability (+ extra (B W, V) fp32, the scorer hook) become its new slots, the ones that end go to its
+    pool.  st: the beam part of a Transformer.DecodeState (tok, score, row_done, done, n_tok, tokens, logp_tok, anc, the scratch
+    tables, the candidate workspace, the pool and the result), all updated IN PLACE; two launches, the same at every step."""
+    if not logits.is_cuda:
+        raise RuntimeError(NO_CPU)
+    pz, ldz = _mat(logits)
+    R, V = logits.shape
+    B, W, cap = st.B, st.beam, st.cap
+    assert R == B * W, f"s2s_beam_select: logits must have B W = {B * W} rows, got {R}"
+    px, ldx = (None, 0)
+    if extra is not None:
+        assert extra.is_cuda and extra.dtype == torch.float32 and tuple(extra.shape) == (R, V)
+        px, ldx = _mat(extra)
+    shapes = {"tok": ((R,), torch.int32), "score": ((R,), torch.float32), "row_done": ((R,), torch.uint8), "done": ((B,), torch.uint8),
+              "n_tok": ((B,), torch.int32), "tokens": ((R, cap), torch.int32), "logp_tok": ((R, cap), torch.float32),
+              "anc": ((R, cap), torch.int32), "s_tokens": ((R, cap), torch.int32), "s_logp": ((R, cap), torch.float32),
+              "s_anc": ((R, cap), torch.int32), "cand_val": ((R, W), torch.float32), "cand_lp": ((R, W), torch.float32),
+              "cand_idx": ((R, W), torch.int32), "cand_n": ((R,), torch.int32), "pool_tokens": ((B, W, cap), torch.int32),
+              "pool_logp": ((B, W, cap), torch.float32), "pool_len": ((B, W), torch.int32), "pool_final": ((B, W), torch.float32),
+              "pool_sum": ((B, W), torch.float32), "pool_seq": ((B, W), torch.int32), "pool_cnt": ((B,), torch.int32),
+              "pool_ins": ((B,), torch.int32), "res_tokens": ((B, W, cap), torch.int32), "res_logp": ((B, W, cap), torch.float32),
+              "res_len": ((B, W), torch.int32), "res_final": ((B, W), torch.float32), "res_sum": ((B, W), torch.float32)}
+    ptr = {}
+    for name, (shape, dtype) in shapes.items():
+        t = getattr(st, name)
+        assert t.is_cuda and t.is_contiguous() and t.dtype == dtype and tuple(t.shape) == shape, f"s2s_beam_select: {name} must be {dtype} {shape}"
+        ptr["done_row" if name == "row_done" else name] = t.data_ptr()
+    a = L.S2SBeamArgs(logits=pz, ldz=ldz, extra=px, ldx=ldx, inv_temp=float(inv_temp), dtype=dt(logits), B=B, W=W, V=V, cap=cap, eos=int(eos),
+                      min_steps=int(min_steps), length_norm=1 if length_norm else 0, **ptr)
+    L.check(L.lib().smx_s2s_beam_select(ctypes.byref(a), _stream()), "smx_s2s_beam_select")
