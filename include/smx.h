@@ -1162,6 +1162,55 @@ int smx_attn_step_rows(const smx_attn_step_rows_args* r, void* stream);
 int smx_attn_step_rows_plan_query(const smx_attn_step_rows_args* r, smx_attn_step_plan* plan);
 int smx_s2s_beam_select(const smx_s2s_beam_args* a, void* stream);
 
+/* ---- CTC prefix scoring for the beam search (csrc/ctc_prefix.hip) --------------------------------------------------------------------
+ * The recipes' `ctc_scorer: CTCScorer(eos_index, blank_index, ctc_fc: ctc_lin)` inside `ScorerBuilder(full_scorers: [ctc_scorer],
+ * weights: {ctc: ctc_weight_decode})`, handed as `scorer:` to valid_search / test_search
+ * (recipes/LibriSpeech/ASR/transformer/hparams/branchformer_summarymixing.yaml:227-240, 257; AISHELL-1 .../branchformer_summarymixing.yaml:
+ * 181-189, 200, 211; CommonVoice .../branchformer_summarymixing.yaml:174-183, 194, 205).  DESIGN.md I.23 holds the definition.
+ * x (B, T, V) fp32: the log-softmax of ctc_fc(encoder_out), frame t of utterance b at x + (b T + t) ldx; frames t >= T_b =
+ * clamp(enc_len[b], 1, T) are never read.  R = B W rows as in smx_s2s_beam_select, whose score / done / n_tok / tokens / anc the
+ * three entries read (none is written).  The prefix state of row r at step parity q = n_tok[b] & 1: state + ((q R + r) T + t) 2 holds
+ * (r_n[t], r_b[t]) for t < T_b, psi + q R + r the log prefix probability.
+ * smx_ctc_prefix_init (once per search, n_tok = 0): slot 0 of every utterance, parity 0: r_n = -inf, r_b = the running sum of
+ *   x[t, blank], psi = 0.  Nothing else is written.
+ * smx_ctc_prefix_score (before the selection): extra[r, v] = weight * (ctc[r, v] - lp[r, v]), ctc[r, v] = psi(g v) - psi(g), lp the
+ *   log-probability of logits[r] at inv_temp in smx_s2s_beam_select's own expressions (row_scan.h: SelRow), so that the selection's
+ *   lp + extra is (1 - weight) lp + weight ctc.  One lane per column v, serial over t; the parent's r_b and logaddexp(r_n, r_b) are
+ *   staged once per workgroup in LDS (8 T bytes: T <= 4096, SMX_EINVAL beyond).  v == blank: -inf; v == eos: the whole-sequence
+ *   probability logaddexp(r_n[T_b - 1], r_b[T_b - 1]); lp == -inf or ctc == -inf: -inf.  A row with score <= -inf (or NaN), a row
+ *   of a done utterance, a row with psi(g) = -inf, a row whose logits hold a NaN or no number, and a row at n_tok outside [0, cap)
+ *   write -inf into all V columns and read neither x nor their state.
+ * smx_ctc_prefix_advance (after the selection): for every slot r of an utterance that is not done, with score[r] > -inf, at
+ *   n = n_tok[b] >= 1: parent p = anc[r, n - 1], token c = tokens[r, n - 1]; r_n' / r_b' / psi' of g c from the parent's state at
+ *   parity (n - 1) & 1 into row r at parity n & 1.  One wave per row: the lanes stage phi, x[., c], x[., blank] in LDS (12 T bytes),
+ *   lane 0 runs the recursion in frame order, the lanes write the state.  A parent outside the utterance's rows or a token outside
+ *   [0, V) or equal to blank / eos writes nothing.  A done utterance changes nothing; dead slots are skipped.
+ * All fp32 log-domain, no atomics, fixed order: two runs agree bit for bit; nothing allocates or synchronises: capturable.
+ * SMX_EINVAL: a NULL pointer the entry needs, sizes < 1, T > 4096, ldx / lde / ldz < V, blank or eos negative, blank >= V, blank ==
+ * eos, weight outside (0, 1], inv_temp <= 0, R beyond 2^24. */
+typedef struct smx_ctc_prefix_args {
+  const float* x;          /* (B, T, V) fp32 CTC log-probabilities */
+  int64_t ldx;
+  const int32_t* enc_len;  /* (B) */
+  const float* score;      /* (R) the search's running sums */
+  const uint8_t* done;     /* (B) */
+  const int32_t* n_tok;    /* (B) */
+  const int32_t* tokens;   /* (R, cap) */
+  const int32_t* anc;      /* (R, cap) */
+  float* state;            /* (2, R, T, 2) fp32 */
+  float* psi;              /* (2, R) fp32 */
+  const void* logits;      /* (R, V) in dtype (score only) */
+  int64_t ldz;
+  float* extra;            /* (R, V) fp32 (score only) */
+  int64_t lde;
+  double inv_temp;
+  float weight;
+  int32_t dtype, B, W, V, T, cap, blank, eos, pad_;
+} smx_ctc_prefix_args;     /* 160 bytes */
+int smx_ctc_prefix_init(const smx_ctc_prefix_args* a, void* stream);
+int smx_ctc_prefix_score(const smx_ctc_prefix_args* a, void* stream);
+int smx_ctc_prefix_advance(const smx_ctc_prefix_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

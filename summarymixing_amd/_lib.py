@@ -178,6 +178,14 @@ class S2SBeamArgs(ctypes.Structure):
                 (n, ctypes.c_int32) for n in ("dtype", "B", "W", "V", "cap", "eos", "min_steps", "length_norm")]
 
 
+class CtcPrefixArgs(ctypes.Structure):
+    """smx_ctc_prefix_args of include/smx.h."""
+    _fields_ = [("x", c_vp), ("ldx", c_i64), ("enc_len", c_vp), ("score", c_vp), ("done", c_vp), ("n_tok", c_vp), ("tokens", c_vp),
+                ("anc", c_vp), ("state", c_vp), ("psi", c_vp), ("logits", c_vp), ("ldz", c_i64), ("extra", c_vp), ("lde", c_i64),
+                ("inv_temp", ctypes.c_double), ("weight", ctypes.c_float)] + [
+                (n, ctypes.c_int32) for n in ("dtype", "B", "W", "V", "T", "cap", "blank", "eos", "pad_")]
+
+
 # name -> (restype, argtypes); mirrors include/smx.h one to one (tests/test_abi.py checks the export list)
 SIGNATURES = {
     "smx_version": (c_i, []),
@@ -337,6 +345,9 @@ SIGNATURES = {
     "smx_attn_step_rows": (c_i, [ctypes.POINTER(AttnStepRowsArgs), c_vp]),
     "smx_attn_step_rows_plan_query": (c_i, [ctypes.POINTER(AttnStepRowsArgs), ctypes.POINTER(AttnStepPlan)]),
     "smx_s2s_beam_select": (c_i, [ctypes.POINTER(S2SBeamArgs), c_vp]),
+    "smx_ctc_prefix_init": (c_i, [ctypes.POINTER(CtcPrefixArgs), c_vp]),
+    "smx_ctc_prefix_score": (c_i, [ctypes.POINTER(CtcPrefixArgs), c_vp]),
+    "smx_ctc_prefix_advance": (c_i, [ctypes.POINTER(CtcPrefixArgs), c_vp]),
 }
 
 _lib = None

@@ -20,8 +20,9 @@ The search is defined in DESIGN.md §I.22.  Still one captured chain, still poll
 before beam search existed: ``S2STransformerBeamSearcher`` refuses ``beam_size > 1`` by name and ``beam_size=1`` without a scorer runs
 the greedy search (``length_normalization`` is accepted: one hypothesis has nothing to rank, and the score stays the plain sum).  A
 recipe that wants ``beam_size: 10`` points ``valid_search`` at ``summarymixing_amd.decoders.S2SBeamSearcher``, which takes the same
-arguments.  Scorers (CTC / LM), ``TransformerLM`` and the remaining beam options (eos threshold, attention shift, top-k) are not built
-and are refused by name everywhere.  No parameters of their own: the modules are plain
+arguments - its ``scorer:`` included when that is the recipes' ``ScorerBuilder`` over one ``CTCScorer`` (decoders.scorer: joint CTC /
+attention scoring, two more launches in the same captured chain).  LM scorers, ``TransformerLM`` and the remaining
+beam options (eos threshold, attention shift, top-k) are not built and are refused by name.  No parameters of their own: the modules are plain
 attributes, as SpeechBrain's searchers hold them outside the checkpointed ``modules``.  SpeechBrain's ``decoders/seq2seq.py`` is not
 part of the reference tree: the constructor arguments are the recipes', the returned tuple ``(hyps, lengths, scores, log_probs)`` is
 written from memory."""
@@ -31,6 +32,7 @@ import torch
 
 from .. import functional as F
 from .. import ops
+from . import scorer as _scorer
 
 S2SGreedyResult = collections.namedtuple("S2SGreedyResult", "tokens counts scores log_probs state")
 S2SGreedyResult.__doc__ = """tokens (B, cap) int32 (entries at and beyond counts[b] are -1), counts (B) int32, scores (B) fp32 = the sum of
@@ -140,13 +142,22 @@ def _check_beam(beam_size):
         raise ValueError(f"seq2seq beam search: beam_size must be in [1, 128], got {beam_size}")
 
 
-def beam_step(model, seq_lin, state, eos, min_steps, inv_temp, length_normalization):
+def beam_step(model, seq_lin, state, eos, min_steps, inv_temp, length_normalization, scorer=None):
     """The launches of one beam-search step on the current stream: decode_step over the B W rows of the beam state -> seq_lin ->
-    smx_s2s_beam_select into the state.  -> the logits (B W, V) the selection read."""
+    smx_s2s_beam_select into the state.  With a scorer (an active ScorerBuilder whose scorer.begin ran on this state) the CTC prefix
+    score goes in front of the selection, which reads it as its extra, and the prefix state advances behind it (DESIGN.md §I.23);
+    without one, exactly the launches above.  -> the logits (B W, V) the selection read."""
     pred = model.decode_step(state.tok, state)
     W, b = seq_lin.w.weight, seq_lin.w.bias
     logits, _ = F.linear_fwd(pred, F.wcast(W, pred.dtype), b.detach() if b is not None else None)
-    ops.s2s_beam_select(logits, state, eos, min_steps, inv_temp, length_normalization)
+    if scorer is None:
+        ops.s2s_beam_select(logits, state, eos, min_steps, inv_temp, length_normalization)
+        return logits
+    if logits.shape[1] != state.ctc.x.shape[2]:
+        raise ValueError(f"seq2seq beam search: seq_lin has {logits.shape[1]} outputs, the CTC head {state.ctc.x.shape[2]}")
+    extra = ops.ctc_prefix_score(state.ctc, state, logits, inv_temp)
+    ops.s2s_beam_select(logits, state, eos, min_steps, inv_temp, length_normalization, extra=extra)
+    ops.ctc_prefix_advance(state.ctc, state)
     return logits
 
 
@@ -156,37 +167,47 @@ def _beam_result(state):
 
 @torch.no_grad()
 def beam_search(model, seq_lin, encoder_out, enc_len, bos, eos, min_steps, max_steps, beam_size, temperature=1.0, length_normalization=True,
-                state=None, poll_every=8):
+                state=None, poll_every=8, scorer=None):
     """Beam search of beam_size hypotheses per utterance over encoder_out (B, S, d), greedy_search's arguments otherwise (DESIGN.md
     §I.22 defines the search): a hypothesis ends with its eos, an utterance ends when beam_size hypotheses have ended or at max_steps,
     where the ones alive end as they are.  beam_size=1 gives greedy_search's bits.  state: a beam DecodeState of this (B, S, max_steps,
-    dtype, beam_size) to reuse.  -> S2SBeamResult."""
+    dtype, beam_size) to reuse.  scorer: a decoders.scorer.ScorerBuilder - joint CTC / attention scoring, the search then ranks
+    (1 - weight) lp + weight ctc summed over the steps (the stored log_probs stay lp); None or a ctc weight of 0: the
+    plain search, launch for launch.  -> S2SBeamResult."""
     _check_args(bos, eos, min_steps, max_steps, temperature)
     _check_beam(beam_size)
+    scorer = _scorer.active(scorer)
     state = _begin(model, encoder_out, enc_len, bos, max_steps, state, beam=int(beam_size))
+    if scorer is not None:
+        _scorer.begin(scorer, state, encoder_out, eos)
     inv_temp, norm = 1.0 / float(temperature), bool(length_normalization)
-    _poll_loop(lambda: beam_step(model, seq_lin, state, eos, min_steps, inv_temp, norm), state, max_steps, poll_every)
+    _poll_loop(lambda: beam_step(model, seq_lin, state, eos, min_steps, inv_temp, norm, scorer), state, max_steps, poll_every)
     return _beam_result(state)
 
 
 class CapturedS2SBeam:
     """beam_search with ONE step captured as a graph, as CapturedS2SGreedy captures the greedy step: beam_step is a plain chain of
     launches on one stream and every position is a device counter, so the same graph serves every step and every utterance of its
-    (B, S, max_steps, dtype, beam_size).  search(encoder_out, enc_len) equals beam_search bit for bit."""
+    (B, S, max_steps, dtype, beam_size).  search(encoder_out, enc_len) equals beam_search bit for bit.  scorer: as beam_search takes it;
+    the scorer's two launches are part of the captured chain, its per-utterance start (the CTC log-probabilities into their fixed
+    buffer, the empty prefix's state) runs eagerly in search, as the cross-attention projections do."""
 
     def __init__(self, model, seq_lin, B, S, max_steps, dtype, bos, eos, beam_size, min_steps=0, temperature=1.0, length_normalization=True,
-                 device="cuda"):
+                 device="cuda", scorer=None):
         _check_args(bos, eos, min_steps, max_steps, temperature)
         _check_beam(beam_size)
         self.model, self.seq_lin, self.bos, self.max_steps, self.beam_size = model, seq_lin, int(bos), int(max_steps), int(beam_size)
+        self.scorer, self.eos = _scorer.active(scorer), int(eos)
         d = model.custom_tgt_module.layers[0].d_model
         eos, min_steps, inv_temp, norm = int(eos), int(min_steps), 1.0 / float(temperature), bool(length_normalization)
         with torch.no_grad():
             mem = torch.zeros((B, S, d), dtype=dtype, device=device)
             self.state = _begin(model, mem, None, self.bos, self.max_steps, None, beam=self.beam_size)
+            if self.scorer is not None:
+                _scorer.begin(self.scorer, self.state, mem, eos)
 
             def run():
-                beam_step(model, seq_lin, self.state, eos, min_steps, inv_temp, norm)
+                beam_step(model, seq_lin, self.state, eos, min_steps, inv_temp, norm, self.scorer)
             s = torch.cuda.Stream(device=device)
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
@@ -200,6 +221,8 @@ class CapturedS2SBeam:
     @torch.no_grad()
     def search(self, encoder_out, enc_len=None, poll_every=8):
         state = _begin(self.model, encoder_out, enc_len, self.bos, self.max_steps, self.state, beam=self.beam_size)
+        if self.scorer is not None:
+            _scorer.begin(self.scorer, state, encoder_out, self.eos)
         _poll_loop(self.graph.replay, state, self.max_steps, poll_every)
         return _beam_result(state)
 
@@ -286,14 +309,15 @@ class S2SBeamSearcher(S2STransformerGreedySearcher):
     base-class name; here it is the Transformer searcher).  forward(enc_states (B, S, d), wav_len (B) relative) -> (hyps, lengths,
     scores, log_probs) of the BEST hypothesis per utterance, the greedy searcher's tuple: hyps exclude eos, scores are the final scores
     (the summed log-probabilities over the length, eos counted, under length_normalization), log_probs (B, max_steps) per token - from
-    ONE host copy at the end.  beam_size in [1, 128]; a scorer, using_eos_threshold, using_max_attn_shift and topk > 1 are not built and
-    are refused by name."""
+    ONE host copy at the end.  beam_size in [1, 128]; scorer: a decoders.scorer.ScorerBuilder (one CTCScorer and its ``ctc`` weight, the
+    recipes' joint CTC / attention scoring) or None - anything else, using_eos_threshold, using_max_attn_shift and topk > 1 are not
+    built and are refused by name."""
 
     def __init__(self, modules, bos_index, eos_index, min_decode_ratio, max_decode_ratio, beam_size, scorer=None, temperature=1.0,
                  length_normalization=True, **beam_options):
-        if scorer is not None:
-            raise NotImplementedError("S2SBeamSearcher: a scorer (CTC / LM scoring) is not built (the selection kernel has the hook, "
-                                      "smx_s2s_beam_select's extra)")
+        if scorer is not None and not isinstance(scorer, _scorer.ScorerBuilder):
+            raise NotImplementedError(f"S2SBeamSearcher: scorer must be a decoders.scorer.ScorerBuilder (one CTCScorer with its 'ctc' "
+                                      f"weight is what is built), got {type(scorer).__name__}")
         if isinstance(beam_size, bool) or int(beam_size) != beam_size or not 1 <= beam_size <= 128:
             raise NotImplementedError(f"S2SBeamSearcher: beam_size={beam_size} is outside [1, 128], what the selection kernel holds")
         for k, v in beam_options.items():
@@ -305,6 +329,7 @@ class S2SBeamSearcher(S2STransformerGreedySearcher):
                 raise NotImplementedError(f"S2SBeamSearcher: {k}={v!r} is not built")
         super().__init__(modules, bos_index, eos_index, min_decode_ratio, max_decode_ratio, temperature)
         self.beam_size, self.length_normalization = int(beam_size), bool(length_normalization)
+        object.__setattr__(self, "scorer", scorer)            # a plain attribute: the CTC head is the recipe's module, not the searcher's
 
     def forward(self, enc_states, wav_len):
         if not enc_states.is_cuda:
@@ -313,7 +338,7 @@ class S2SBeamSearcher(S2STransformerGreedySearcher):
         max_steps, min_steps = int(S * self.max_decode_ratio), int(S * self.min_decode_ratio)
         enc_len = None if wav_len is None else torch.round(wav_len.to(enc_states.device) * S)
         r = beam_search(self.model, self.fc, enc_states, enc_len, self.bos_index, self.eos_index, min_steps, max_steps, self.beam_size,
-                        self.temperature, self.length_normalization)
+                        self.temperature, self.length_normalization, scorer=self.scorer)
         cap = r.tokens.shape[2]
         packed = torch.cat([r.tokens[:, 0].double(), r.log_probs[:, 0].double(), r.lengths[:, :1].double(), r.scores[:, :1].double()], 1).cpu()
         tokens, log_probs = packed[:, :cap].long(), packed[:, cap:2 * cap].float()          # the one host copy, taken apart

@@ -932,10 +932,11 @@ def resample(x2, image, out2, L_in):
     return out2
 
 
-def log_softmax_fwd(x):
-    """log_softmax over the last dim of a (N, V) view."""
+def log_softmax_fwd(x, out=None):
+    """log_softmax over the last dim of a (N, V) view (out: a contiguous (N, V) buffer of x's dtype to write instead of a fresh one)."""
     N, V = x.shape
-    y = torch.empty((N, V), dtype=x.dtype, device=x.device)
+    y = torch.empty((N, V), dtype=x.dtype, device=x.device) if out is None else out
+    assert y.is_cuda and y.is_contiguous() and y.dtype == x.dtype and tuple(y.shape) == (N, V)
     px, ldx = _mat(x)
     L.check(L.lib().smx_log_softmax_fwd(dt(x), px, ldx, _p(y), V, N, V, _stream()), "smx_log_softmax_fwd")
     return y
@@ -1825,3 +1826,49 @@ def s2s_beam_select(logits, st, eos, min_steps=0, inv_temp=1.0, length_norm=True
     a = L.S2SBeamArgs(logits=pz, ldz=ldz, extra=px, ldx=ldx, inv_temp=float(inv_temp), dtype=dt(logits), B=B, W=W, V=V, cap=cap, eos=int(eos),
                       min_steps=int(min_steps), length_norm=1 if length_norm else 0, **ptr)
     L.check(L.lib().smx_s2s_beam_select(ctypes.byref(a), _stream()), "smx_s2s_beam_select")
+
+
+# ---- CTC prefix scoring for the beam search (csrc/ctc_prefix.hip).  cs: a decoders.scorer.CTCPrefixState (x (B, T, V) fp32 CTC
+# log-probabilities, enc_len (B) int32, state (2, R, T, 2) / psi (2, R) / extra (R, V) fp32, blank, eos, weight); st: the beam part of
+# a Transformer.DecodeState, which the kernels only read.
+def _ctc_prefix_args(cs, st, logits=None, inv_temp=1.0):
+    B, W, cap = st.B, st.beam, st.cap
+    R = B * W
+    x = cs.x
+    if not (x.is_cuda and cs.state.is_cuda):
+        raise RuntimeError(NO_CPU)
+    T, V = x.shape[1], x.shape[2]
+    f32, i32 = torch.float32, torch.int32
+    want = {"x": (cs.x, (B, T, V), f32), "enc_len": (cs.enc_len, (B,), i32), "state": (cs.state, (2, R, T, 2), f32),
+            "psi": (cs.psi, (2, R), f32), "extra": (cs.extra, (R, V), f32), "score": (st.score, (R,), f32),
+            "done": (st.done, (B,), torch.uint8), "n_tok": (st.n_tok, (B,), i32), "tokens": (st.tokens, (R, cap), i32),
+            "anc": (st.anc, (R, cap), i32)}
+    ptr = {}
+    for name, (t, shape, dtype) in want.items():
+        assert t.is_cuda and t.is_contiguous() and t.dtype == dtype and tuple(t.shape) == shape, f"ctc_prefix: {name} must be {dtype} {shape}"
+        ptr[name] = t.data_ptr()
+    a = L.CtcPrefixArgs(ldx=V, lde=V, inv_temp=float(inv_temp), weight=float(cs.weight), dtype=L.F32, B=B, W=W, V=V, T=T, cap=cap,
+                        blank=int(cs.blank), eos=int(cs.eos), **ptr)
+    if logits is not None:
+        assert logits.is_cuda and tuple(logits.shape) == (R, V), f"ctc_prefix_score: logits must be (B W, V) = {(R, V)}"
+        pz, a.ldz = _mat(logits)
+        a.logits, a.dtype = pz, dt(logits)
+    return a
+
+
+def ctc_prefix_init(cs, st):
+    """The prefix state of the empty hypothesis into slot 0 of every utterance, parity 0 (smx_ctc_prefix_init)."""
+    L.check(L.lib().smx_ctc_prefix_init(ctypes.byref(_ctc_prefix_args(cs, st)), _stream()), "smx_ctc_prefix_init")
+
+
+def ctc_prefix_score(cs, st, logits, inv_temp=1.0):
+    """cs.extra (B W, V) = weight (ctc - lp) for the step the selection is about to take over logits (smx_ctc_prefix_score)."""
+    tok = _pb(f"ctc_prefix_score (R {st.B * st.beam}, V {cs.x.shape[2]}, T {cs.x.shape[1]})", 4.0 * cs.x.numel() * st.beam)
+    L.check(L.lib().smx_ctc_prefix_score(ctypes.byref(_ctc_prefix_args(cs, st, logits, inv_temp)), _stream()), "smx_ctc_prefix_score")
+    _pe(tok)
+    return cs.extra
+
+
+def ctc_prefix_advance(cs, st):
+    """The prefix state of every slot the selection just filled, from its parent's (smx_ctc_prefix_advance)."""
+    L.check(L.lib().smx_ctc_prefix_advance(ctypes.byref(_ctc_prefix_args(cs, st)), _stream()), "smx_ctc_prefix_advance")
