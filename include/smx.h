@@ -1211,6 +1211,39 @@ int smx_ctc_prefix_init(const smx_ctc_prefix_args* a, void* stream);
 int smx_ctc_prefix_score(const smx_ctc_prefix_args* a, void* stream);
 int smx_ctc_prefix_advance(const smx_ctc_prefix_args* a, void* stream);
 
+/* ---- the language model's share of the scorer hook (csrc/lm_score.hip) -----------------------------------------------------------------
+ * The recipes' `transformerlm_scorer: TransformerLMScorer(language_model: lm_model, temperature: 1.15)` inside
+ * `scorer_test_search: ScorerBuilder(full_scorers: [transformerlm_scorer, ctc_scorer], weights: {ctc: 0.40, transformerlm: 0.60})`
+ * (recipes/LibriSpeech/ASR/transformer/hparams/branchformer_summarymixing.yaml:182-191, 233-235, 242-246, 259-269).  DESIGN.md I.24
+ * holds the definition.  R = B W rows as in smx_s2s_beam_select, whose score / done / n_tok the entry reads (none is written).
+ * smx_lm_score (before the selection, behind smx_ctc_prefix_score when there is one): per row r of the LM's logits z (R, V),
+ *     lmlp[r, v] = (z[r, v] - max z[r]) inv_temp - log sum_j exp((z[r, j] - max z[r]) inv_temp)
+ *   in smx_s2s_select's expressions (row_scan.h: SelRow - one fp64 inv_temp, fp32 expf of the fp64 exponent, fp32 per-lane sums, the 64
+ *   lanes and the final expression in fp64, rounded to fp32), inv_temp = 1 / the LM scorer's temperature; then
+ *     accumulate == 0:  extra[r, v]  = weight * lmlp[r, v]        (the LM alone)
+ *     accumulate == 1:  extra[r, v] += weight * lmlp[r, v]        (fp32; -inf in extra stays -inf)
+ *   A row with score <= -inf (or NaN), a row of a done utterance and a row at n_tok outside [0, cap) score nothing: -inf in all V
+ *   columns when accumulate == 0, left as they are when accumulate == 1 (smx_ctc_prefix_score wrote -inf under the same conditions).
+ *   A row whose logits hold a NaN or no number: -inf in all V columns in both modes.
+ *   One wave per row, two passes over the row (the second comes from L2); 16-byte loads of z and 16-byte loads / stores of extra on
+ *   rows that are 16-byte aligned, element by element otherwise, with the same bits.  No atomics, no LDS; nothing allocates or
+ *   synchronises: capturable; two runs agree bit for bit.
+ * SMX_EINVAL: a NULL pointer, sizes < 1, ldz / lde < V, an unknown dtype, inv_temp <= 0 or not finite, weight <= 0 or not finite,
+ * accumulate outside {0, 1}, R beyond 2^24. */
+typedef struct smx_lm_score_args {
+  const void* logits;      /* (R, V) the LM's logits in dtype */
+  int64_t ldz;
+  float* extra;            /* (R, V) fp32, what smx_s2s_beam_select reads */
+  int64_t lde;
+  const float* score;      /* (R) the search's running sums */
+  const uint8_t* done;     /* (B) */
+  const int32_t* n_tok;    /* (B) */
+  double inv_temp;
+  float weight;
+  int32_t dtype, B, W, V, cap, accumulate, pad_;
+} smx_lm_score_args;       /* 96 bytes */
+int smx_lm_score(const smx_lm_score_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -186,6 +186,13 @@ class CtcPrefixArgs(ctypes.Structure):
                 (n, ctypes.c_int32) for n in ("dtype", "B", "W", "V", "T", "cap", "blank", "eos", "pad_")]
 
 
+class LmScoreArgs(ctypes.Structure):
+    """smx_lm_score_args of include/smx.h."""
+    _fields_ = [("logits", c_vp), ("ldz", c_i64), ("extra", c_vp), ("lde", c_i64), ("score", c_vp), ("done", c_vp), ("n_tok", c_vp),
+                ("inv_temp", ctypes.c_double), ("weight", ctypes.c_float)] + [
+                (n, ctypes.c_int32) for n in ("dtype", "B", "W", "V", "cap", "accumulate", "pad_")]
+
+
 # name -> (restype, argtypes); mirrors include/smx.h one to one (tests/test_abi.py checks the export list)
 SIGNATURES = {
     "smx_version": (c_i, []),
@@ -348,6 +355,7 @@ SIGNATURES = {
     "smx_ctc_prefix_init": (c_i, [ctypes.POINTER(CtcPrefixArgs), c_vp]),
     "smx_ctc_prefix_score": (c_i, [ctypes.POINTER(CtcPrefixArgs), c_vp]),
     "smx_ctc_prefix_advance": (c_i, [ctypes.POINTER(CtcPrefixArgs), c_vp]),
+    "smx_lm_score": (c_i, [ctypes.POINTER(LmScoreArgs), c_vp]),
 }
 
 _lib = None

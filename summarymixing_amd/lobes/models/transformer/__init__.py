@@ -1,0 +1,1 @@
+from .TransformerLM import TransformerLM  # noqa: F401

@@ -1872,3 +1872,28 @@ def ctc_prefix_score(cs, st, logits, inv_temp=1.0):
 def ctc_prefix_advance(cs, st):
     """The prefix state of every slot the selection just filled, from its parent's (smx_ctc_prefix_advance)."""
     L.check(L.lib().smx_ctc_prefix_advance(ctypes.byref(_ctc_prefix_args(cs, st)), _stream()), "smx_ctc_prefix_advance")
+
+
+# ---- the language model's share of the scorer hook (csrc/lm_score.hip)
+def lm_score(logits, extra, st, weight, inv_temp=1.0, accumulate=False):
+    """extra (B W, V) fp32 (+)= weight * log_softmax(logits * inv_temp) over the LM's logits (B W, V) of the step the selection is about
+    to take (smx_lm_score): written when accumulate is false, added to what smx_ctc_prefix_score wrote when it is true.  st: the beam
+    part of a Transformer.DecodeState (score, done, n_tok), which the kernel only reads.  Rows that score nothing: include/smx.h."""
+    if not (logits.is_cuda and extra.is_cuda):
+        raise RuntimeError(NO_CPU)
+    R, V = logits.shape
+    B, W, cap = st.B, st.beam, st.cap
+    assert R == B * W, f"lm_score: logits must have B W = {B * W} rows, got {R}"
+    assert extra.dtype == torch.float32 and tuple(extra.shape) == (R, V), f"lm_score: extra must be float32 {(R, V)}"
+    assert st.score.is_cuda and st.score.dtype == torch.float32 and st.score.is_contiguous() and st.score.shape == (R,)
+    assert st.done.dtype == torch.uint8 and st.done.is_contiguous() and st.done.shape == (B,)
+    assert st.n_tok.dtype == torch.int32 and st.n_tok.is_contiguous() and st.n_tok.shape == (B,)
+    pz, ldz = _mat(logits)
+    px, lde = _mat(extra)
+    a = L.LmScoreArgs(logits=pz, ldz=ldz, extra=px, lde=lde, score=st.score.data_ptr(), done=st.done.data_ptr(), n_tok=st.n_tok.data_ptr(),
+                      inv_temp=float(inv_temp), weight=float(weight), dtype=dt(logits), B=B, W=W, V=V, cap=cap, accumulate=1 if accumulate else 0)
+    tok = _pb(f"lm_score {'bf16' if _es(logits) == 2 else 'f32'} (R {R}, V {V})" + (" acc" if accumulate else ""),
+              R * V * (2 * _es(logits) + (8 if accumulate else 4)))
+    L.check(L.lib().smx_lm_score(ctypes.byref(a), _stream()), "smx_lm_score")
+    _pe(tok)
+    return extra
