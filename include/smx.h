@@ -1244,6 +1244,90 @@ typedef struct smx_lm_score_args {
 } smx_lm_score_args;       /* 96 bytes */
 int smx_lm_score(const smx_lm_score_args* a, void* stream);
 
+/* ---- Transducer beam search (csrc/tbeam.hip) ---------------------------------------------------------------------------------------------
+ * The transducer recipes' `Beamsearcher: speechbrain.decoders.transducer.TransducerBeamSearcher(beam_size: 10, nbest: 1, lm_module:
+ * lm_model, lm_weight: 0.50, state_beam: 2.3, expand_beam: 2.3)` (recipes/LibriSpeech/ASR/transducer/hparams/
+ * conformer_summarymixing_transducer.yaml:383-393).  Its source is not part of the reference tree: DESIGN.md I.25 holds the definition,
+ * written from memory, and the two caps upstream does not have (E = max expansions per frame, U = max symbols per hypothesis).
+ * The unit is the EXPANSION: per utterance b that is not done, one step expands its current best open hypothesis `a` (token
+ * cur_tok[b], prediction-network state h_in[b] / c_in[b], LM state lm_*_in[:, b]) at its own frame frames[b]; every step is the same
+ * launches, nothing synchronises with the host (which polls `done`), no atomics, fixed summation orders: two runs agree bit for bit
+ * and an utterance's result does not depend on B or on the other rows.
+ * smx_tbeam_init:   the start of a search: the one hypothesis [blank], sum 0, zero states, picked and staged (cur_tok = blank, the
+ *                   staging rows zero); frames / expansions / overflow / n_hyps 0, tokens -1, out_len 0, scores / sums -inf; done[b] =
+ *                   (lengths[b] == 0), such an utterance returning the one empty hypothesis with score 0.
+ * smx_tbeam_step:   three launches.  h_out / c_out = one LSTM step on cur_tok[b] from h_in / c_in (the W_ih^T row gather of
+ *                   smx_onehot_gates_fwd; c fp32, h rounded to dtype - smx_greedy_decode's step); pdec = h_out W_proj^T; z[b,:] =
+ *                   act(enc[b, t, :] + pdec[b]) W_lin^T + b_lin with t = clamp(frames[b], 0, T - 1), smx_greedy_decode's arithmetic
+ *                   and roundings, stored in fp32.  Rows of done utterances are computed too and read by nobody.
+ * smx_tbeam_select: one launch, one workgroup per utterance that is not done.  lp = log-softmax(z[b]) in fp32 (the row code of
+ *                   smx_s2s_select at temperature 1), lm = log-softmax(lm_logits[b]) likewise when lm_logits is given; the W best
+ *                   of lp in the order (value descending, index ascending), found by repeated arg-max "strictly after the previous
+ *                   (value, index)"; best = the first's value, the second's if the first is the blank.  In that order: the blank
+ *                   -> the closed list gets (a's prediction, a's sum + lp, a's states); another token k with lp >= best - expand_beam
+ *                   -> the open list gets (a's prediction + k, a's sum + lp + lm_weight lm[k], the new states).  A hypothesis of U
+ *                   symbols gets no other child than the blank, which it always gets, and sets overflow bit 1.  Then the frame
+ *                   ends if the closed list holds W entries; else if this was the frame's E-th expansion (the closed list is filled
+ *                   up to W with the best of the open list by key = sum / (symbols + 1), overflow bit 0); else if the open list is
+ *                   empty; else if the closed list's best by key has sum >= state_beam + the sum of the open list's best by key
+ *                   (a tie on keys takes the earlier insertion).  A frame end advances frames[b], turns the closed list into the
+ *                   open list of the next frame (prefixes written out, states copied to the other half of their ping-pong) and, at
+ *                   frames[b] == lengths[b], sets done[b] and writes the closed list sorted by key (stable) into tokens (B, nbest, U;
+ *                   padded with -1) / out_len / scores (keys) / sums / n_hyps.  Otherwise the open list's best by key is removed and
+ *                   staged: cur_tok and the staging rows *_in of the next step.  The new states h_out / c_out / lm_*_out are copied
+ *                   into state storage once per expansion.  expansions[b] counts the steps; overflow bit 2: a row without numbers.
+ * `state`: smx_tbeam_state_bytes(...) bytes, 16-byte aligned, opaque (lists, nodes, prefixes, state slots; csrc/tbeam.hip TbLayout),
+ * initialised by smx_tbeam_init.  lm_logits (B, V; leading dimension ld_lm) in dtype with lm_h_* (lm_L, B, lm_H) dtype and lm_c_*
+ * (lm_L, B, lm_H) fp32 - the buffers of RNNLM.step on cur_tok - or all NULL: no LM.  The three entries take the same struct.
+ * Supported (smx_tbeam_ok; SMX_EUNSUPPORTED otherwise): H (and lm_H) as smx_lstm_ok, J as smx_greedy_ok, V in [3, 8192], W in [2, 32]
+ * and below V, 4 V + 16 (W + E W) bytes within the selection's 60 KB of LDS, 16-byte aligned operands.  SMX_EINVAL: a NULL pointer
+ * the entry needs, sizes < 1, nbest outside [1, W], blank outside [0, V), a NaN parameter, staging rows in == out, bad strides. */
+typedef struct smx_tbeam_args {
+  const void* enc;         /* (B, T, J) dtype: enc[b, t, :] at enc + b ld_b + t ld_t */
+  int64_t ld_b, ld_t;
+  const int32_t* lengths;  /* (B) frames per utterance, or NULL: all T */
+  const void* WihT;        /* (V - 1, 4H; ldw) = W_ih^T */
+  int64_t ldw;
+  const float* bias;       /* (4H) = b_ih + b_hh */
+  const void* Whh;         /* (4H, H) */
+  const void* Wproj;       /* (J, H) */
+  const void* Wlin;        /* (V, J) */
+  const float* blin;       /* (V) or NULL */
+  int32_t* cur_tok;        /* (B) the staged hypothesis' last token */
+  void* h_in;              /* (B, H) dtype: its prediction-network state */
+  float* c_in;             /* (B, H) */
+  void* h_out;             /* (B, H) dtype: the state after the step */
+  float* c_out;            /* (B, H) */
+  void* pdec;              /* (B, J) dtype */
+  float* z;                /* (B, V) fp32 joint logits */
+  const void* lm_logits;   /* (B, V; ld_lm) dtype, or NULL */
+  int64_t ld_lm;
+  void* lm_h_in;           /* (lm_L, B, lm_H) dtype */
+  float* lm_c_in;          /* (lm_L, B, lm_H) */
+  const void* lm_h_out;    /* (lm_L, B, lm_H) dtype */
+  const float* lm_c_out;   /* (lm_L, B, lm_H) */
+  void* state;             /* smx_tbeam_state_bytes */
+  uint8_t* done;           /* (B) what the host polls */
+  int32_t* overflow;       /* (B) bit 0: the expansion cap ended a frame; bit 1: a hypothesis reached U symbols; bit 2: a row without numbers */
+  int32_t* expansions;     /* (B) steps taken */
+  int32_t* frames;         /* (B) frames closed = the current frame */
+  int32_t* tokens;         /* (B, nbest, U) */
+  int32_t* out_len;        /* (B, nbest) */
+  float* scores;           /* (B, nbest) keys */
+  float* sums;             /* (B, nbest) */
+  int32_t* n_hyps;         /* (B) */
+  float lm_weight, state_beam, expand_beam;
+  int32_t dtype, B, T, H, J, V, W, nbest;
+  int32_t E;               /* max expansions per frame */
+  int32_t U;               /* max symbols per hypothesis */
+  int32_t act, blank, lm_L, lm_H, pad_;
+} smx_tbeam_args;          /* 344 bytes */
+int smx_tbeam_ok(int dtype, int H, int J, int V, int W);
+size_t smx_tbeam_state_bytes(int dtype, int B, int H, int W, int max_expansions, int max_symbols, int lm_layers, int lm_H);
+int smx_tbeam_init(const smx_tbeam_args* a, void* stream);
+int smx_tbeam_step(const smx_tbeam_args* a, void* stream);
+int smx_tbeam_select(const smx_tbeam_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -193,6 +193,18 @@ class LmScoreArgs(ctypes.Structure):
                 (n, ctypes.c_int32) for n in ("dtype", "B", "W", "V", "cap", "accumulate", "pad_")]
 
 
+class TbeamArgs(ctypes.Structure):
+    """smx_tbeam_args of include/smx.h."""
+    _fields_ = [("enc", c_vp), ("ld_b", c_i64), ("ld_t", c_i64), ("lengths", c_vp), ("WihT", c_vp), ("ldw", c_i64)] + [
+                (n, c_vp) for n in ("bias", "Whh", "Wproj", "Wlin", "blin", "cur_tok", "h_in", "c_in", "h_out", "c_out", "pdec", "z",
+                                    "lm_logits")] + [("ld_lm", c_i64)] + [
+                (n, c_vp) for n in ("lm_h_in", "lm_c_in", "lm_h_out", "lm_c_out", "state", "done", "overflow", "expansions", "frames",
+                                    "tokens", "out_len", "scores", "sums", "n_hyps")] + [
+                (n, ctypes.c_float) for n in ("lm_weight", "state_beam", "expand_beam")] + [
+                (n, ctypes.c_int32) for n in ("dtype", "B", "T", "H", "J", "V", "W", "nbest", "E", "U", "act", "blank", "lm_L", "lm_H",
+                                              "pad_")]
+
+
 # name -> (restype, argtypes); mirrors include/smx.h one to one (tests/test_abi.py checks the export list)
 SIGNATURES = {
     "smx_version": (c_i, []),
@@ -356,6 +368,11 @@ SIGNATURES = {
     "smx_ctc_prefix_score": (c_i, [ctypes.POINTER(CtcPrefixArgs), c_vp]),
     "smx_ctc_prefix_advance": (c_i, [ctypes.POINTER(CtcPrefixArgs), c_vp]),
     "smx_lm_score": (c_i, [ctypes.POINTER(LmScoreArgs), c_vp]),
+    "smx_tbeam_ok": (c_i, [c_i, c_i, c_i, c_i, c_i]),
+    "smx_tbeam_state_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i]),
+    "smx_tbeam_init": (c_i, [ctypes.POINTER(TbeamArgs), c_vp]),
+    "smx_tbeam_step": (c_i, [ctypes.POINTER(TbeamArgs), c_vp]),
+    "smx_tbeam_select": (c_i, [ctypes.POINTER(TbeamArgs), c_vp]),
 }
 
 _lib = None

@@ -7,8 +7,9 @@ from .seq2seq import (CapturedS2SBeam, CapturedS2SGreedy, S2SBeamResult, S2SBeam
                       S2STransformerGreedySearcher, beam_search, greedy_search)
 from . import scorer
 from .scorer import CTCScorer, ScorerBuilder, TransformerLMScorer
+from . import transducer_beam
 from .transducer import TransducerBeamSearcher
 
-__all__ = ["scorer", "CTCScorer", "ScorerBuilder", "TransformerLMScorer", "TransducerBeamSearcher", "ctc_greedy_decode", "filter_ctc_output", "greedy_decode", "greedy_decode_from_encoder",
+__all__ = ["scorer", "transducer_beam", "CTCScorer", "ScorerBuilder", "TransformerLMScorer", "TransducerBeamSearcher", "ctc_greedy_decode", "filter_ctc_output", "greedy_decode", "greedy_decode_from_encoder",
            "CapturedCTCGreedy", "CTCGreedyState", "CTCGreedyResult", "greedy_search", "CapturedS2SGreedy", "S2SGreedyResult",
            "S2STransformerGreedySearcher", "S2STransformerBeamSearcher", "beam_search", "CapturedS2SBeam", "S2SBeamResult", "S2SBeamSearcher"]

@@ -1897,3 +1897,66 @@ def lm_score(logits, extra, st, weight, inv_temp=1.0, accumulate=False):
     L.check(L.lib().smx_lm_score(ctypes.byref(a), _stream()), "smx_lm_score")
     _pe(tok)
     return extra
+
+
+# ---- transducer beam search (csrc/tbeam.hip).  st: a nnet.transducer.beam.TransducerBeamState - the weight images, the staging rows,
+# the opaque state block, the counters and the result, all on the device and updated IN PLACE; nothing here synchronises with the host.
+def tbeam_ok(dtype, H, J, V, W):
+    return dtype in _DT and bool(L.lib().smx_tbeam_ok(_DT[dtype], H, J, V, W))
+
+
+def tbeam_state_bytes(dtype, B, H, W, max_expansions, max_symbols, lm_layers=0, lm_H=0):
+    return int(L.lib().smx_tbeam_state_bytes(_DT[dtype], B, H, W, max_expansions, max_symbols, lm_layers, lm_H))
+
+
+def _tbeam_args(st, lm_logits=None):
+    enc = st.enc
+    if not enc.is_cuda:
+        raise RuntimeError(NO_CPU)
+    B, T, J = enc.shape
+    H, V, W, nb, U, DT = st.H, st.V, st.W, st.nbest, st.U, enc.dtype
+    f32, i32 = torch.float32, torch.int32
+    want = {"WihT": (st.WihT, None, DT), "bias": (st.bias, (4 * H,), f32), "Whh": (st.Whh, (4 * H, H), DT), "Wproj": (st.Wproj, (J, H), DT),
+            "Wlin": (st.Wlin, (V, J), DT), "cur_tok": (st.cur_tok, (B,), i32), "h_in": (st.h_in, (B, H), DT), "c_in": (st.c_in, (B, H), f32),
+            "h_out": (st.h_out, (B, H), DT), "c_out": (st.c_out, (B, H), f32), "pdec": (st.pdec, (B, J), DT), "z": (st.z, (B, V), f32),
+            "done": (st.done, (B,), torch.uint8), "overflow": (st.overflow, (B,), i32), "expansions": (st.expansions, (B,), i32),
+            "frames": (st.frames, (B,), i32), "tokens": (st.tokens, (B, nb, U), i32), "out_len": (st.out_len, (B, nb), i32),
+            "scores": (st.scores, (B, nb), f32), "sums": (st.sums, (B, nb), f32), "n_hyps": (st.n_hyps, (B,), i32)}
+    if st.blin is not None:
+        want["blin"] = (st.blin, (V,), f32)
+    if st.lengths is not None:
+        want["lengths"] = (st.lengths, (B,), i32)
+    Lc, Hl = st.lm_L, st.lm_H
+    if Lc:
+        want.update({"lm_h_in": (st.lm_h_in, (Lc, B, Hl), DT), "lm_c_in": (st.lm_c_in, (Lc, B, Hl), f32),
+                     "lm_h_out": (st.lm_h_out, (Lc, B, Hl), DT), "lm_c_out": (st.lm_c_out, (Lc, B, Hl), f32)})
+    ptr = {}
+    for name, (t, shape, dtype) in want.items():
+        assert t.is_cuda and t.dtype == dtype and (shape is None or (t.is_contiguous() and tuple(t.shape) == shape)), \
+            f"tbeam: {name} must be {dtype} {shape}"
+        ptr[name] = t.data_ptr()
+    assert st.WihT.shape == (V - 1, 4 * H) and st.WihT.stride(1) == 1 and enc.stride(2) == 1
+    assert st.state.dtype == torch.uint8 and st.state.numel() >= tbeam_state_bytes(DT, B, H, W, st.E, U, Lc, Hl)
+    a = L.TbeamArgs(enc=enc.data_ptr(), ld_b=enc.stride(0), ld_t=enc.stride(1), ldw=st.WihT.stride(0), state=st.state.data_ptr(),
+                    lm_weight=float(st.lm_weight), state_beam=float(st.state_beam), expand_beam=float(st.expand_beam), dtype=_DT[DT], B=B, T=T,
+                    H=H, J=J, V=V, W=W, nbest=nb, E=st.E, U=U, act=st.act, blank=st.blank, lm_L=Lc, lm_H=Hl, **ptr)
+    if lm_logits is not None:
+        assert Lc and lm_logits.is_cuda and lm_logits.dtype == DT and tuple(lm_logits.shape) == (B, V) and lm_logits.stride(1) == 1
+        a.lm_logits, a.ld_lm = lm_logits.data_ptr(), lm_logits.stride(0)
+    return a
+
+
+def tbeam_init(st):
+    """The start of a search (smx_tbeam_init): the hypothesis [blank] of every utterance, picked and staged; counters and result cleared."""
+    L.check(L.lib().smx_tbeam_init(ctypes.byref(_tbeam_args(st)), _stream()), "smx_tbeam_init")
+
+
+def tbeam_step(st):
+    """The arithmetic of one expansion (smx_tbeam_step): LSTM step on cur_tok from h_in / c_in -> h_out / c_out, pdec, and the joint
+    logits z (B, V) fp32 of every utterance's current frame.  Three launches."""
+    L.check(L.lib().smx_tbeam_step(ctypes.byref(_tbeam_args(st)), _stream()), "smx_tbeam_step")
+
+
+def tbeam_select(st, lm_logits=None):
+    """The selection of one expansion (smx_tbeam_select) over st.z and, with an LM, its logits (B, V) for cur_tok.  One launch."""
+    L.check(L.lib().smx_tbeam_select(ctypes.byref(_tbeam_args(st, lm_logits)), _stream()), "smx_tbeam_select")
