@@ -4,6 +4,7 @@ waveform -> Fbank -> InputNormalization -> ConvolutionFrontEnd -> TransformerASR
 log_softmax -> ctc_cost, optimised by the flat-buffer AdamW (needs an MI355X; synthetic data).
 
     python examples/encoder_ctc_step.py [--steps 20] [--batch 16] [--seconds 8] [--augment] [--wav-augment] [--decode]
+                                        [--noam-warmup N] [--sgd-after K]
 
 --augment inserts the recipe's fea_augment (time drops, frequency drops, time warp: yaml:195-245) between the filterbank and the
 normalisation, where upstream's transducer train.py applies it; off by default.
@@ -11,6 +12,10 @@ normalisation, where upstream's transducer train.py applies it; off by default.
 the filterbank, where upstream's train.py applies it; off by default.
 --decode prints, after the last step, the batch's hypotheses under CTC greedy decoding (speechbrain.decoders.ctc.ctc_greedy_decode:
 row arg-max, merge repeats, drop the blank - on the device, one copy to the host at the end).
+--noam-warmup N attaches the transformer recipes' NoamScheduler (lr_initial = the optimizer's rate, n_warmup_steps = N) to the
+optimizer: the rate of every update is computed on the device (opt.lr_dev); the recipe's `noam_annealing(optimizer)` line stays.
+--sgd-after K is the two-stage recipes' switch (AISHELL-1, CommonVoice: stage_one_epochs of Adam, then SGD with momentum 0.99 and
+Nesterov): after K steps FlatSGD.adopt takes the flat buffers and shadows over in place and training goes on at a constant rate.
 
 The module names and constructor arguments are the ones the reference YAML passes (…/LibriSpeech/ASR/transducer/
 hparams/conformer_summarymixing_transducer.yaml); only the import root changes: speechbrain.* -> summarymixing_amd.*."""
@@ -32,7 +37,8 @@ from summarymixing_amd.lobes.models.transformer.TransformerASR import EncoderWra
 from summarymixing_amd.nnet.activations import Softmax                                       # noqa: E402
 from summarymixing_amd.nnet.linear import Linear                                             # noqa: E402
 from summarymixing_amd.nnet.losses import ctc_loss                                           # noqa: E402
-from summarymixing_amd.trainer import FlatAdamW                                              # noqa: E402
+from summarymixing_amd.nnet.schedulers import NoamScheduler                                  # noqa: E402
+from summarymixing_amd.trainer import FlatAdamW, FlatSGD                                     # noqa: E402
 
 
 class EncoderSide(torch.nn.Module):
@@ -85,10 +91,16 @@ def main():
     ap.add_argument("--augment", action="store_true", help="apply the recipe's fea_augment to the features")
     ap.add_argument("--wav-augment", action="store_true", help="apply the recipe's wav_augment (speed perturbation) to the waveforms")
     ap.add_argument("--decode", action="store_true", help="print the batch's CTC greedy hypotheses after the last step")
+    ap.add_argument("--noam-warmup", type=int, default=0, metavar="N", help="Noam schedule on the device with N warm-up steps")
+    ap.add_argument("--sgd-after", type=int, default=0, metavar="K", help="switch to Nesterov SGD (FlatSGD.adopt) after K steps")
     args = ap.parse_args()
     torch.manual_seed(0)
     model = EncoderSide(augment=args.augment, wav_augment=args.wav_augment).cuda().train()
     opt = FlatAdamW(model, lr=8e-4, betas=(0.9, 0.98), weight_decay=0.01, max_grad_norm=5.0, compute_dtype=torch.bfloat16)
+    noam_annealing = None
+    if args.noam_warmup > 0:
+        noam_annealing = NoamScheduler(lr_initial=8e-4, n_warmup_steps=args.noam_warmup)
+        opt.set_lr_schedule(noam_annealing)
     B, L = args.batch, int(16000 * args.seconds)
     wav = torch.randn(B, L, device="cuda") * 0.1
     wav_lens = torch.linspace(1.0, 0.6, B, device="cuda")
@@ -105,8 +117,14 @@ def main():
         loss = ctc_loss(model(wav, wav_lens), tokens, wav_lens, tok_lens, blank_index=0)
         loss.backward()
         opt.step()
+        if noam_annealing is not None:
+            noam_annealing(opt)                # (attached: counts only; the device computed this update's rate)
         if step % 5 == 0 or step == args.steps - 1:
-            print(f"step {step:3d}  ctc loss {loss.item():9.4f}")
+            print(f"step {step:3d}  ctc loss {loss.item():9.4f}" + (f"  lr {opt.current_lr():.3e}" if args.noam_warmup or args.sgd_after else ""))
+        if args.sgd_after > 0 and step + 1 == args.sgd_after:
+            opt = FlatSGD.adopt(opt, lr=1e-5, momentum=0.99, nesterov=True)     # lr_sgd of the AISHELL-1 recipe
+            noam_annealing = None
+            print(f"step {step:3d}  switched to Nesterov SGD over the same flat buffers")
     torch.cuda.synchronize()
     if t0 is not None and args.steps > 3:
         dt = (time.perf_counter() - t0) / (args.steps - 3)

@@ -512,6 +512,37 @@ int smx_cast_to_f32(int dtype, const void* src, float* dst, int64_t n, void* str
 int smx_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow_bf16,
                    int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                    float grad_scale, const float* gscale_dev, const uint64_t* step_dev, void* stream);
+/* smx_adamw_step with the learning rate in device memory: a non-NULL `lr_dev` (fp32[1], written by smx_lr_schedule) replaces
+ * `lr`; with lr_dev NULL, or holding lr, the result equals smx_adamw_step's bit for bit. */
+int smx_adamw_step_lr(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow_bf16,
+                      int64_t n, float lr, const float* lr_dev, float beta1, float beta2, float eps, float weight_decay, int step,
+                      float grad_scale, const float* gscale_dev, const uint64_t* step_dev, void* stream);
+/* Fused torch.optim.SGD (dampening 0) over a flat fp32 range, the second stage of the two-stage recipes
+ * (recipes/AISHELL-1/.../hparams: SGD(lr_sgd, momentum=0.99, nesterov=True)):
+ *   g = grad * grad_scale * gscale_dev[0] + weight_decay * p;  buf = momentum * buf + g;
+ *   p -= lr * (nesterov ? g + momentum * buf : buf);           momentum == 0: p -= lr * g, momentum_buf may be NULL.
+ * A zero-initialised buffer gives torch's first step (buf = g) exactly, so no step number is needed.  A non-NULL lr_dev (fp32[1])
+ * replaces lr; a device clip factor gscale_dev[0] of exactly 0 skips the whole update (smx_clip_factor's verdict on a non-finite
+ * norm: parameters, buffer and shadows untouched).  shadow (optional) receives the updated parameters cast to bf16.
+ * 16-byte accesses of param / grad / momentum_buf and 8-byte stores of four shadows where the pointers sit at the same offset
+ * from a 16-byte boundary (views of parallel flat buffers do), a scalar head and tail around them; any other alignment runs
+ * scalar.  At most SMX_SGD_MAX_BLOCKS blocks of 256 lanes x 4 elements, grid-strided; no atomics: two runs agree bit for bit. */
+#define SMX_SGD_MAX_BLOCKS 2048
+int smx_sgd_step(float* param, const float* grad, float* momentum_buf, void* shadow_bf16, int64_t n, float lr,
+                 const float* lr_dev, float momentum, float weight_decay, int nesterov, float grad_scale,
+                 const float* gscale_dev, void* stream);
+/* lr_out[0] = the learning rate of update t (counted from 1), evaluated in float64 by one thread and stored as float32.
+ * t = step when step > 0, else step_dev[0] (the device step counter, smx_step_counter_add: a captured step follows its schedule
+ * on replay).  The rate restates what a recipe gets by calling its scheduler once behind every optimizer step:
+ *   t == 1: lr0, the optimizer's own rate.
+ *   SMX_LR_NOAM (c0 = lr_initial, c1 = n_warmup_steps, c2 = model_size or 0), t >= 2, n = t - 1:
+ *     c0 * norm * min(n^-0.5, n * c1^-1.5), norm = c1^0.5, or c2^-0.5 when c2 > 0.
+ *   SMX_LR_WARM_EXP_DECAY (c0 = base rate, c1 = n_warmup_steps, c2 = total_steps, c3 = decay_factor), t >= 2, c = t - 2:
+ *     c0 * c / c1 while c < c1, else min(c0, c0 * c3^((c - c1) / c2)). */
+#define SMX_LR_NOAM 0
+#define SMX_LR_WARM_EXP_DECAY 1
+int smx_lr_schedule(int kind, double c0, double c1, double c2, double c3, double lr0, int64_t step,
+                    const uint64_t* step_dev, float* lr_out, void* stream);
 /* ---- InputNormalization between the filterbank and the CNN front-end (recipe key `normalize`:
  * speechbrain.processing.features.InputNormalization, …transducer.yaml:167-169; upstream-only arithmetic). ----
  * smx_utt_meanstd: mean[b,f] and unbiased std[b,f] over the frames t < len[b] (std clamped below by eps; 0 / 1 when the

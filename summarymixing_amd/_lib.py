@@ -8,6 +8,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SMX_LIB") or os.path.join(_HERE, "libsmx.so")
 
 c_i, c_i64, c_f, c_vp, c_sz = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
+c_d = ctypes.c_double
+LR_NOAM, LR_WARM_EXP_DECAY = 0, 1      # include/smx.h SMX_LR_*
+SGD_MAX_BLOCKS = 2048                  # include/smx.h SMX_SGD_MAX_BLOCKS (blocks of 256 lanes x 4 elements)
 
 # enums of include/smx.h
 F32, BF16 = 0, 1
@@ -278,6 +281,9 @@ SIGNATURES = {
     "smx_cast_from_f32": (c_i, [c_i, c_vp, c_vp, c_i64, c_vp]),
     "smx_cast_to_f32": (c_i, [c_i, c_vp, c_vp, c_i64, c_vp]),
     "smx_adamw_step": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_f, c_f, c_f, c_f, c_f, c_i, c_f, c_vp, c_vp, c_vp]),
+    "smx_adamw_step_lr": (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_f, c_vp, c_f, c_f, c_f, c_f, c_i, c_f, c_vp, c_vp, c_vp]),
+    "smx_sgd_step": (c_i, [c_vp, c_vp, c_vp, c_vp, c_i64, c_f, c_vp, c_f, c_f, c_i, c_f, c_vp, c_vp]),
+    "smx_lr_schedule": (c_i, [c_i, c_d, c_d, c_d, c_d, c_d, c_i64, c_vp, c_vp, c_vp]),
     "smx_utt_meanstd": (c_i, [c_i, c_vp, c_i64, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_f, c_vp]),
     "smx_stats_combine": (c_i, [c_vp, c_vp, c_i, c_i, c_vp, c_vp, c_f, c_vp]),
     "smx_colnorm": (c_i, [c_i, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_i, c_i, c_i, c_vp]),

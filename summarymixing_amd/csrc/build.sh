@@ -20,7 +20,7 @@ FLAGS=(--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffast-math -fno-finite-math-o
 [[ -n "${SMX_CXXFLAGS:-}" ]] && FLAGS+=(${SMX_CXXFLAGS})
 mkdir -p "$OBJ"
 pids=()
-for f in capi gemm gemm_ln256 gemm_ln256r64 gemm_ln512 gemm_panel gemm_panel_bwd rowwise layernorm slab_epilogue dwconv frontend ctc transducer lstm lstm_step greedy reduce wgrad_group stream augment resample seqloss ctcdec attention tgt_embed attn_step beam ctc_prefix lm_score tbeam; do
+for f in capi gemm gemm_ln256 gemm_ln256r64 gemm_ln512 gemm_panel gemm_panel_bwd rowwise layernorm slab_epilogue dwconv frontend ctc transducer lstm lstm_step greedy reduce wgrad_group stream augment resample seqloss ctcdec attention tgt_embed attn_step beam ctc_prefix lm_score tbeam optim; do
   src="${HERE}/${f}.hip"; obj="${OBJ}/${f}.o"
   stale=0
   for dep in "$src" "${HERE}"/*.h "${HERE}/build.sh" "${HERE}/../../include/smx.h"; do
@@ -33,5 +33,5 @@ for f in capi gemm gemm_ln256 gemm_ln256r64 gemm_ln512 gemm_panel gemm_panel_bwd
   fi
 done
 for p in "${pids[@]:-}"; do [[ -n "$p" ]] && wait "$p"; done
-"$HIPCC" --offload-arch=gfx950 -shared -fPIC -o "$OUT" "${OBJ}"/{capi,gemm,gemm_ln256,gemm_ln256r64,gemm_ln512,gemm_panel,gemm_panel_bwd,rowwise,layernorm,slab_epilogue,dwconv,frontend,ctc,transducer,lstm,lstm_step,greedy,reduce,wgrad_group,stream,augment,resample,seqloss,ctcdec,attention,tgt_embed,attn_step,beam,ctc_prefix,lm_score,tbeam}.o
+"$HIPCC" --offload-arch=gfx950 -shared -fPIC -o "$OUT" "${OBJ}"/{capi,gemm,gemm_ln256,gemm_ln256r64,gemm_ln512,gemm_panel,gemm_panel_bwd,rowwise,layernorm,slab_epilogue,dwconv,frontend,ctc,transducer,lstm,lstm_step,greedy,reduce,wgrad_group,stream,augment,resample,seqloss,ctcdec,attention,tgt_embed,attn_step,beam,ctc_prefix,lm_score,tbeam,optim}.o
 echo "built $OUT"

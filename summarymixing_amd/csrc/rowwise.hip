@@ -649,11 +649,12 @@ __global__ __launch_bounds__(256) void cast_to_f32_kernel(const T* src, float* d
 __global__ __launch_bounds__(256) void adamw_kernel(float* p, const float* g, float* m, float* v, uint16_t* shadow, long n,
                                                     float lr, float b1, float b2, float eps, float wd, float bc1,
                                                     float bc2_sqrt, float gscale, const float* gscale_dev,
-                                                    const uint64_t* step_dev) {
+                                                    const uint64_t* step_dev, const float* lr_dev) {
   // a clip factor of exactly 0 is smx_clip_factor's "non-finite gradient norm" verdict: skip the whole update
   // (no weight decay, no moment update, shadows untouched) like SpeechBrain's check_gradients does
   if (gscale_dev && gscale_dev[0] == 0.f) return;
   const float gs = gscale * (gscale_dev ? gscale_dev[0] : 1.f);
+  if (lr_dev) lr = lr_dev[0];                            // the rate smx_lr_schedule wrote for this update
   if (step_dev) {                                        // bias correction from the device step counter (graph replay)
     const float t = (float)step_dev[0];
     bc1 = 1.f - powf(b1, t);
@@ -1211,17 +1212,23 @@ extern "C" int smx_cast_to_f32(int dtype, const void* src, float* dst, int64_t n
   return check_launch("smx_cast_to_f32");
 }
 
-extern "C" int smx_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow_bf16,
-                              int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
-                              float grad_scale, const float* gscale_dev, const uint64_t* step_dev, void* stream) {
+extern "C" int smx_adamw_step_lr(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow_bf16,
+                                 int64_t n, float lr, const float* lr_dev, float beta1, float beta2, float eps, float weight_decay,
+                                 int step, float grad_scale, const float* gscale_dev, const uint64_t* step_dev, void* stream) {
   SMX_REQUIRE(param && grad && exp_avg && exp_avg_sq, "smx_adamw_step: bad arguments");
   if (n <= 0) return SMX_OK;
   SMX_REQUIRE(step > 0 || step_dev, "smx_adamw_step: step <= 0 needs the device step counter (step_dev)");
   float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
   hipLaunchKernelGGL(adamw_kernel, dim3(grid1d(n)), dim3(256), 0, STREAM, param, grad, exp_avg, exp_avg_sq,
                      (uint16_t*)shadow_bf16, n, lr, beta1, beta2, eps, weight_decay, bc1, sqrtf(bc2), grad_scale, gscale_dev,
-                     step > 0 ? nullptr : step_dev);
+                     step > 0 ? nullptr : step_dev, lr_dev);
   return check_launch("smx_adamw_step");
+}
+extern "C" int smx_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow_bf16,
+                              int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                              float grad_scale, const float* gscale_dev, const uint64_t* step_dev, void* stream) {
+  return smx_adamw_step_lr(param, grad, exp_avg, exp_avg_sq, shadow_bf16, n, lr, nullptr, beta1, beta2, eps, weight_decay, step,
+                           grad_scale, gscale_dev, step_dev, stream);
 }
 extern "C" size_t smx_sumsq_workspace(void) { return SUMSQ_BLOCKS * sizeof(float); }
 extern "C" int smx_sumsq(const float* x, int64_t n, float* out, void* workspace, void* stream) {

@@ -817,11 +817,37 @@ def cast(src, dtype):
     return dst
 
 
-def adamw_step(param, grad, m, v, shadow, lr, b1, b2, eps, wd, step, grad_scale=1.0, gscale_dev=None):
+def adamw_step(param, grad, m, v, shadow, lr, b1, b2, eps, wd, step, grad_scale=1.0, gscale_dev=None, lr_dev=None):
     tok = _pb(f"adamw ({param.numel()} params)", (28 + (2 if shadow is not None else 0)) * param.numel())
-    L.check(L.lib().smx_adamw_step(_p(param), _p(grad), _p(m), _p(v), _p(shadow), param.numel(), lr, b1, b2, eps, wd,
-                                   step, grad_scale, _p(gscale_dev), _epoch() if step <= 0 else None, _stream()), "smx_adamw_step")
+    if lr_dev is None:
+        L.check(L.lib().smx_adamw_step(_p(param), _p(grad), _p(m), _p(v), _p(shadow), param.numel(), lr, b1, b2, eps, wd,
+                                       step, grad_scale, _p(gscale_dev), _epoch() if step <= 0 else None, _stream()), "smx_adamw_step")
+    else:                             # the rate of this update is in device memory (lr_schedule below)
+        L.check(L.lib().smx_adamw_step_lr(_p(param), _p(grad), _p(m), _p(v), _p(shadow), param.numel(), lr, _p(lr_dev), b1, b2,
+                                          eps, wd, step, grad_scale, _p(gscale_dev), _epoch() if step <= 0 else None, _stream()),
+                "smx_adamw_step_lr")
     _pe(tok)
+
+
+SGD_GRID_SWEEP = L.SGD_MAX_BLOCKS * 256 * 4     # elements one sweep of smx_sgd_step's capped grid covers
+
+
+def sgd_step(param, grad, buf, shadow, lr, momentum=0.0, wd=0.0, nesterov=False, grad_scale=1.0, gscale_dev=None, lr_dev=None):
+    """torch.optim.SGD (dampening 0) on a flat fp32 range, in place; buf: the momentum buffer (None with momentum 0)."""
+    n = param.numel()
+    tok = _pb(f"sgd ({n} params)", (12 + (8 if buf is not None else 0) + (2 if shadow is not None else 0)) * n)
+    L.check(L.lib().smx_sgd_step(_p(param), _p(grad), _p(buf), _p(shadow), n, lr, _p(lr_dev), momentum, wd, int(bool(nesterov)),
+                                 grad_scale, _p(gscale_dev), _stream()), "smx_sgd_step")
+    _pe(tok)
+
+
+def lr_schedule(kind, consts, lr0, step, out):
+    """out[0] (device float32) = the rate of update `step` (> 0: by value; <= 0: read from the device step counter of
+    set_step_counter) under schedule `kind` (L.LR_NOAM / L.LR_WARM_EXP_DECAY) with its four constants (include/smx.h)."""
+    assert out.is_cuda and out.dtype == torch.float32
+    c = [float(x) for x in consts] + [0.0] * (4 - len(consts))
+    L.check(L.lib().smx_lr_schedule(kind, c[0], c[1], c[2], c[3], float(lr0), int(step), _epoch() if step <= 0 else None,
+                                    _p(out), _stream()), "smx_lr_schedule")
 
 
 def utt_meanstd(x2, lens, mean, std, B, T, mean_norm=True, std_norm=True, eps=1e-10):

@@ -21,6 +21,10 @@ its cost is the bytes on the wire):
   grad_dtype=torch.bfloat16   gradients cross the wire in bf16 (half the bytes; the accumulation inside the kernels, the
                       clip and AdamW stay fp32).
 comm_exposed_ms() reports how long the compute stream stood waiting for the collectives (bench.py prints it).
+
+FlatOptimizer is all of the above but the update rule; FlatAdamW and FlatSGD (the two-stage recipes' second stage; FlatSGD.adopt
+switches in place) add theirs.  set_lr_schedule(sched) moves the learning rate of every update into device memory
+(smx_lr_schedule -> lr_dev -> the update kernel), so a captured step follows its schedule on replay.
 """
 import contextlib
 import os
@@ -99,13 +103,21 @@ def shard_map(buckets, world):
     return out
 
 
-class FlatAdamW:
-    def __init__(self, module, lr=8e-4, betas=(0.9, 0.98), eps=1e-8, weight_decay=0.01, max_grad_norm=5.0,
-                 compute_dtype=torch.bfloat16, process_group=None, buckets=None, reduce="allreduce", grad_dtype=torch.float32):
+class FlatOptimizer:
+    """What FlatAdamW and FlatSGD share - everything but the update rule: the flat buffers and the views into them, the bf16
+    shadows, the gradient buckets and both exchange modes, the device clip, the step counter, graph capture and the optional
+    device-side learning-rate schedule.  A subclass names its per-element state buffers (_STATE: same length and sharding as the
+    weights), allocates them in _alloc_state and applies its rule to one flat range in _k_update."""
+    _NAME = "FlatOptimizer"
+    _STATE = ()                   # attribute names of the per-element state buffers
+    _HPARAMS = ()                 # attribute names of the rule's own hyper-parameters (not carried over by adopt)
+
+    def __init__(self, module, lr, max_grad_norm=5.0, compute_dtype=torch.bfloat16, process_group=None, buckets=None,
+                 reduce="allreduce", grad_dtype=torch.float32):
         if reduce not in ("allreduce", "rs_ag"):
-            raise ValueError("FlatAdamW: reduce must be 'allreduce' or 'rs_ag'")
+            raise ValueError(f"{self._NAME}: reduce must be 'allreduce' or 'rs_ag'")
         if grad_dtype not in (torch.float32, torch.bfloat16):
-            raise ValueError("FlatAdamW: grad_dtype must be torch.float32 or torch.bfloat16")
+            raise ValueError(f"{self._NAME}: grad_dtype must be torch.float32 or torch.bfloat16")
         self.reduce, self.grad_dtype = reduce, grad_dtype
         self.params = [p for p in module.parameters() if p.requires_grad]
         dev = self.params[0].device
@@ -116,8 +128,7 @@ class FlatAdamW:
         self.total, self.offs = total, offs
         self.flat_p = torch.zeros(total, dtype=torch.float32, device=dev)
         self.flat_g = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.exp_avg = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.exp_avg_sq = torch.zeros(total, dtype=torch.float32, device=dev)
+        self._alloc_state(total, dev)
         self.shadow = torch.zeros(total, dtype=torch.bfloat16, device=dev) if compute_dtype == torch.bfloat16 else None
         for p, o in zip(self.params, offs):
             n = p.numel()
@@ -129,7 +140,9 @@ class FlatAdamW:
                                                       ops._stream()), "smx_cast_from_f32")
             for p, o in zip(self.params, offs):
                 F.register_shadow(p, self.shadow[o:o + p.numel()].view(p.shape))
-        self.lr, self.betas, self.eps, self.wd, self.max_grad_norm = lr, betas, eps, weight_decay, max_grad_norm
+        self.lr, self.max_grad_norm = lr, max_grad_norm
+        self._sched, self.lr_dev = None, None     # set_lr_schedule: the schedule and the device scalar it writes
+        self._adopted = None                      # set once another optimizer has taken these buffers over (FlatSGD.adopt)
         self.step_count = 0
         self.pg = process_group
         self.world = dist.get_world_size(process_group) if (dist.is_available() and dist.is_initialized()) else 1
@@ -157,7 +170,40 @@ class FlatAdamW:
         self.buckets = buckets or [(0, total)]
         # in-place weight changes behind the optimizer's back (module.load_state_dict of a checkpoint) must reach the bf16
         # shadows the GEMMs read: they are only refreshed inside smx_adamw_step otherwise
-        self._hook = module.register_load_state_dict_post_hook(lambda mod, incompatible: self.refresh_shadows())
+        # (the hook reaches the optimizer through a one-element list, so that adopt can hand it to the optimizer that takes over)
+        self._owner = owner = [self]
+        self._hook = module.register_load_state_dict_post_hook(lambda mod, incompatible: owner[0].refresh_shadows())
+
+    def _alloc_state(self, total, dev):
+        """Allocate the buffers named in _STATE (total float32 elements each, zero)."""
+        for name in self._STATE:
+            setattr(self, name, torch.zeros(total, dtype=torch.float32, device=dev))
+
+    def _alive(self):
+        if self._adopted:
+            raise RuntimeError(f"{self._NAME}: this optimizer's buffers were taken over by {self._adopted}; "
+                               "use the optimizer that adopt returned")
+
+    # ---- learning-rate schedule on the device -------------------------------------------------------------
+    def set_lr_schedule(self, sched):
+        """Attach a schedule of nnet.schedulers (or detach with None).  Attached, every update launches smx_lr_schedule in front
+        of its update kernel: the rate of update t - t by value in an eager step, from the device step counter in a captured one -
+        goes into the device scalar `lr_dev`, which the update kernel reads instead of the host float `lr` (`lr` stays the
+        optimizer's own rate, the one update 1 runs at).  Detached, nothing is launched and `lr` is used as given."""
+        if sched is not None and self.lr_dev is None:
+            self.lr_dev = torch.full((1,), float(self.lr), dtype=torch.float32, device=self.flat_p.device)
+        self._sched = sched
+
+    def current_lr(self):
+        """The rate of the last update (host read of lr_dev when a schedule is attached; for logs)."""
+        return float(self.lr_dev.item()) if self._sched is not None else float(self.lr)
+
+    def _k_lr(self):
+        kind, consts = self._sched.device_args()
+        ops.lr_schedule(kind, consts, self.lr, 0 if self._dev_step is not None else self.step_count, self.lr_dev)
+
+    def _lr_dev(self):
+        return self.lr_dev if self._sched is not None else None
 
     # ---- state ------------------------------------------------------------------------------------
     def refresh_shadows(self):
@@ -168,17 +214,19 @@ class FlatAdamW:
                                                       ops._stream()), "smx_cast_from_f32")
         F.weights_changed()           # (packed weight images of the panel GEMM are stale now)
 
-    def _full_moments(self):
-        """Complete copies of the two AdamW moment buffers.  reduce="rs_ag": every rank updates only its 1/world shard of each
-        bucket, so the local buffers are current there and stale elsewhere - the shards are all-gathered bucket by bucket
-        (mirroring the weight all-gather of _apply_update) into fresh tensors; a COLLECTIVE in that mode."""
-        m, v = self.exp_avg.clone(), self.exp_avg_sq.clone()
+    def _full_state(self):
+        """Complete copies of the state buffers (AdamW: the two moments; SGD: the momentum buffer).  reduce="rs_ag": every rank
+        updates only its 1/world shard of each bucket, so the local buffers are current there and stale elsewhere - the shards
+        are all-gathered bucket by bucket (mirroring the weight all-gather of _apply_update) into fresh tensors; a COLLECTIVE in
+        that mode."""
+        local = [getattr(self, name) for name in self._STATE]
+        full = [t.clone() for t in local]
         if self._collective and self.reduce == "rs_ag" and self._shard_layout:
             for a, b in self._shard_layout:
                 sa, sb = self._shard(a, b)
-                for full, local in ((m, self.exp_avg), (v, self.exp_avg_sq)):
-                    dist.all_gather_into_tensor(full[a:b], local[sa:sb].contiguous(), group=self.pg)
-        return m, v
+                for f, l in zip(full, local):
+                    dist.all_gather_into_tensor(f[a:b], l[sa:sb].contiguous(), group=self.pg)
+        return full
 
     def state_dict(self, gather=True):
         """Optimizer state for checkpoint / resume (the weights themselves are in module.state_dict()).
@@ -196,28 +244,31 @@ class FlatAdamW:
         sd = {"step": step, "skipped_steps": self.skipped_steps(), "total": self.total, "complete": True}
         sharded = bool(self._collective and self.reduce == "rs_ag" and self._shard_layout)
         if gather or not sharded:
-            sd["exp_avg"], sd["exp_avg_sq"] = self._full_moments()
+            sd.update(zip(self._STATE, self._full_state()))
         else:
-            sd["exp_avg"], sd["exp_avg_sq"] = self.exp_avg.clone(), self.exp_avg_sq.clone()
+            sd.update((name, getattr(self, name).clone()) for name in self._STATE)
             sd.update(complete=False, rank=self.rank, world=self.world,
                       owned=[self._shard(a, b) for a, b in self._shard_layout], layout=list(self._shard_layout))
         return sd
 
     def load_state_dict(self, sd):
         if sd["total"] != self.total:
-            raise ValueError(f"FlatAdamW.load_state_dict: flat size {sd['total']} != {self.total} (different model?)")
+            raise ValueError(f"{self._NAME}.load_state_dict: flat size {sd['total']} != {self.total} (different model?)")
+        missing = [name for name in self._STATE if sd.get(name) is None]
+        if missing:
+            raise ValueError(f"{self._NAME}.load_state_dict: no {missing[0]!r} in the checkpoint (saved by another optimizer?)")
         if not sd.get("complete", True):
             layout = tuple(tuple(r) for r in sd.get("layout", ()))
             mine = (self.reduce == "rs_ag" and sd.get("rank") == self.rank and sd.get("world") == self.world
                     and self._shard_layout in (None, layout))
             if not mine:
-                raise ValueError("FlatAdamW.load_state_dict: a state_dict(gather=False) shard of rank "
+                raise ValueError(f"{self._NAME}.load_state_dict: a state_dict(gather=False) shard of rank "
                                  f"{sd.get('rank')} / world {sd.get('world')} only resumes on that rank of the same world "
                                  "size and bucket layout under reduce='rs_ag'; save with gather=True (a collective) for a "
                                  "portable checkpoint")
             self._shard_layout = layout        # the next step checks its buckets against the checkpoint's ownership map
-        self.exp_avg.copy_(sd["exp_avg"])
-        self.exp_avg_sq.copy_(sd["exp_avg_sq"])
+        for name in self._STATE:
+            getattr(self, name).copy_(sd[name])
         self.step_count = int(sd["step"])
         if self._dev_step is not None:
             self._dev_step.fill_(self.step_count)
@@ -238,7 +289,7 @@ class FlatAdamW:
             if g is not None and g.data_ptr() == base + 4 * o:
                 continue
             if self._collective:
-                raise RuntimeError("FlatAdamW: a parameter's .grad no longer points into the flat gradient buffer "
+                raise RuntimeError(f"{self._NAME}: a parameter's .grad no longer points into the flat gradient buffer "
                                    "(module.zero_grad(set_to_none=True)?) - use optimizer.zero_grad(); the gradient buckets "
                                    "were all-reduced without it")
             view = self.flat_g[o:o + p.numel()].view(p.shape)
@@ -349,7 +400,8 @@ class FlatAdamW:
             self._dev_step = None
 
     def step(self, reduce_all=False):
-        F.flush_deferred()          # (no-op unless a backward ran outside functional.block)
+        self._alive()
+        F.flush_deferred()        # (no-op unless a backward ran outside functional.block)
         if not (self.flat_p.is_cuda and torch.cuda.is_current_stream_capturing()):
             self._rebind_grads()
         if self._collective:
@@ -378,7 +430,8 @@ class FlatAdamW:
         F.weights_changed()
 
     def update_only(self):
-        """The part of step() behind the collective (capturable: device step counter, clip, AdamW, shadows)."""
+        """The part of step() behind the collective (capturable: device step counter, schedule, clip, update, shadows)."""
+        self._alive()
         assert self._dev_step is not None, "call use_device_step_counter(True) before capturing"
         assert not (self._collective and self.reduce == "rs_ag"), "update_only (graph capture) needs reduce='allreduce'"
         ops.step_counter_add(self._dev_step, 1)
@@ -399,17 +452,17 @@ class FlatAdamW:
     def _k_clip(self, gscale):
         ops.clip_factor(self._sumsq, self.max_grad_norm, gscale, self._clip)
 
-    def _k_adamw(self, a, b, g, gscale, clip):
-        """AdamW on flat elements [a, b) with the gradient tensor g (b - a elements)."""
-        F.weights_changed()           # (the bf16 shadows / fp32 biases change in place: packed weight images are stale)
-        ops.adamw_step(self.flat_p[a:b], g, self.exp_avg[a:b], self.exp_avg_sq[a:b],
-                       self.shadow[a:b] if self.shadow is not None else None, self.lr, self.betas[0], self.betas[1], self.eps,
-                       self.wd, 0 if self._dev_step is not None else self.step_count, gscale, clip)
+    def _k_update(self, a, b, g, gscale, clip):
+        """The subclass's rule on flat elements [a, b) with the gradient tensor g (b - a elements)."""
+        raise NotImplementedError
 
     def _apply_update(self, gscale):
-        """Global-norm clip + AdamW + bf16 shadow refresh: three HIP kernel launches per owned range, nothing visits the
-        host.  reduce="rs_ag": the ranges are this rank's shards of the reduce-scattered buckets, the squared norm is
-        completed by one scalar all-reduce and the updated weights are all-gathered bucket by bucket."""
+        """Global-norm clip + the update rule + bf16 shadow refresh: three HIP kernel launches per owned range (one more, a
+        single thread, with a learning-rate schedule attached), nothing visits the host.  reduce="rs_ag": the ranges are this
+        rank's shards of the reduce-scattered buckets, the squared norm is completed by one scalar all-reduce and the updated
+        weights are all-gathered bucket by bucket."""
+        if self._sched is not None:
+            self._k_lr()
         sharded = self._collective and self.reduce == "rs_ag"
         W = self.world
         if sharded:
@@ -420,8 +473,8 @@ class FlatAdamW:
             if self._shard_layout is None:
                 self._shard_layout = layout
             elif layout != self._shard_layout:
-                raise RuntimeError("FlatAdamW(reduce='rs_ag'): the gradient buckets changed between steps - the AdamW moments are "
-                                   "sharded by bucket and would be mixed up (keep ONE bucket plan, or reduce='allreduce')")
+                raise RuntimeError(f"{self._NAME}(reduce='rs_ag'): the gradient buckets changed between steps - the optimizer state "
+                                   "is sharded by bucket and would be mixed up (keep ONE bucket plan, or reduce='allreduce')")
             work = [(self._shard(a, b), self._shard_g[a // W:b // W]) for a, b in self._reduced]
         else:
             work = [((0, self.total), self.flat_g)]
@@ -435,7 +488,7 @@ class FlatAdamW:
             self._k_clip(gscale)
             clip = self._clip
         for (a, b), g in work:
-            self._k_adamw(a, b, g, gscale, clip)
+            self._k_update(a, b, g, gscale, clip)
         if sharded:
             for a, b in self._reduced:
                 sa, sb = self._shard(a, b)
@@ -447,3 +500,99 @@ class FlatAdamW:
     def grad_norm(self):
         """Host read of the last global gradient norm (diagnostics only)."""
         return float(self._sumsq.sqrt().item()) / self.world
+
+
+class FlatAdamW(FlatOptimizer):
+    _NAME = "FlatAdamW"
+    _STATE = ("exp_avg", "exp_avg_sq")
+    _HPARAMS = ("betas", "eps", "wd")
+
+    def __init__(self, module, lr=8e-4, betas=(0.9, 0.98), eps=1e-8, weight_decay=0.01, max_grad_norm=5.0,
+                 compute_dtype=torch.bfloat16, process_group=None, buckets=None, reduce="allreduce", grad_dtype=torch.float32):
+        self.betas, self.eps, self.wd = betas, eps, weight_decay
+        super().__init__(module, lr, max_grad_norm, compute_dtype, process_group, buckets, reduce, grad_dtype)
+
+    def _full_moments(self):
+        """Complete copies of the two AdamW moment buffers (a COLLECTIVE under reduce="rs_ag", see _full_state)."""
+        m, v = self._full_state()
+        return m, v
+
+    def _k_adamw(self, a, b, g, gscale, clip):
+        """AdamW on flat elements [a, b) with the gradient tensor g (b - a elements)."""
+        F.weights_changed()           # (the bf16 shadows / fp32 biases change in place: packed weight images are stale)
+        ops.adamw_step(self.flat_p[a:b], g, self.exp_avg[a:b], self.exp_avg_sq[a:b],
+                       self.shadow[a:b] if self.shadow is not None else None, self.lr, self.betas[0], self.betas[1], self.eps,
+                       self.wd, 0 if self._dev_step is not None else self.step_count, gscale, clip, lr_dev=self._lr_dev())
+
+    def _k_update(self, a, b, g, gscale, clip):
+        self._k_adamw(a, b, g, gscale, clip)
+
+
+class FlatSGD(FlatOptimizer):
+    """torch.optim.SGD (momentum, Nesterov, coupled weight decay; dampening 0) over the flat buffers: stage two of the two-stage
+    recipes (AISHELL-1, CommonVoice: SGD(lr_sgd, momentum=0.99, nesterov=True) behind stage_one_epochs of Adam), with the
+    shadows, the bucketed gradient exchange and the device clip of FlatAdamW.  One state buffer, `momentum_buffer` (none at
+    momentum 0); a zero buffer gives torch's first step exactly.  FlatSGD.adopt(adamw, ...) switches stages in place."""
+    _NAME = "FlatSGD"
+    _HPARAMS = ("momentum", "nesterov", "wd")
+
+    def __init__(self, module, lr, momentum=0.0, nesterov=False, weight_decay=0.0, dampening=0, max_grad_norm=5.0,
+                 compute_dtype=torch.bfloat16, process_group=None, buckets=None, reduce="allreduce", grad_dtype=torch.float32,
+                 **unsupported):
+        self._set_rule(momentum, nesterov, weight_decay, dampening, unsupported)
+        super().__init__(module, lr, max_grad_norm, compute_dtype, process_group, buckets, reduce, grad_dtype)
+
+    def _set_rule(self, momentum, nesterov, weight_decay, dampening, unsupported):
+        if unsupported.pop("maximize", False):
+            raise ValueError("FlatSGD: maximize is not supported (negate the loss)")
+        if unsupported:
+            raise TypeError(f"FlatSGD: unsupported keyword {sorted(unsupported)[0]!r}")
+        if dampening != 0:
+            raise ValueError(f"FlatSGD: dampening must be 0 (got {dampening}); smx_sgd_step has no dampening")
+        if momentum < 0:
+            raise ValueError(f"FlatSGD: momentum must not be negative (got {momentum})")
+        if nesterov and momentum <= 0:
+            raise ValueError("FlatSGD: nesterov needs momentum > 0 (and dampening 0), as in torch.optim.SGD")
+        self.momentum, self.nesterov, self.wd = float(momentum), bool(nesterov), float(weight_decay)
+        self._STATE = ("momentum_buffer",) if momentum > 0 else ()
+        self.momentum_buffer = None
+
+    @classmethod
+    def adopt(cls, opt, lr, momentum=0.0, nesterov=False, weight_decay=0.0, dampening=0, **unsupported):
+        """The stage switch: an SGD optimizer over `opt`'s buffers.  flat_p, flat_g, the shadows (still registered with the
+        GEMMs), the parameter views, buckets, process group, exchange mode, clip threshold, step counter and skipped-step count
+        are taken over as they are - nothing is copied, the weights do not move - the momentum buffer is allocated and `opt`'s
+        own state (the AdamW moments) released.  `opt` is unusable afterwards: its step() raises.  A learning-rate schedule
+        attached to `opt` is not carried over (stage two runs at a constant rate unless one is attached to the result)."""
+        opt._alive()
+        if opt._pending:
+            raise RuntimeError("FlatSGD.adopt: gradient collectives are in flight; switch between steps")
+        new = cls.__new__(cls)
+        new._set_rule(momentum, nesterov, weight_decay, dampening, unsupported)
+        own = set(opt._STATE) | set(opt._HPARAMS) | {"_STATE", "lr", "lr_dev", "_sched"}
+        for k, v in vars(opt).items():
+            if k not in own:
+                setattr(new, k, v)
+        new.lr, new._sched, new.lr_dev = lr, None, None
+        new._alloc_state(new.total, new.flat_p.device)
+        new._owner[0] = new                               # the module's load_state_dict hook refreshes the shadows through it
+        for k in opt._STATE + ("flat_p", "flat_g", "shadow", "_comm", "lr_dev"):
+            setattr(opt, k, None)
+        opt._sched, opt._adopted = None, "FlatSGD.adopt"
+        return new
+
+    def state_dict(self, gather=True):
+        """As FlatAdamW.state_dict (same gather / partial-shard rules) with `momentum_buffer` (None at momentum 0)."""
+        sd = super().state_dict(gather)
+        sd.setdefault("momentum_buffer", None)
+        return sd
+
+    def _k_sgd(self, a, b, g, gscale, clip):
+        """SGD on flat elements [a, b) with the gradient tensor g (b - a elements)."""
+        F.weights_changed()           # (the bf16 shadows / fp32 biases change in place: packed weight images are stale)
+        ops.sgd_step(self.flat_p[a:b], g, self.momentum_buffer[a:b] if self.momentum_buffer is not None else None,
+                     self.shadow[a:b] if self.shadow is not None else None, self.lr, self.momentum, self.wd, self.nesterov,
+                     gscale, clip, lr_dev=self._lr_dev())
+
+    def _k_update(self, a, b, g, gscale, clip):
+        self._k_sgd(a, b, g, gscale, clip)
