@@ -1359,6 +1359,36 @@ int smx_tbeam_init(const smx_tbeam_args* a, void* stream);
 int smx_tbeam_step(const smx_tbeam_args* a, void* stream);
 int smx_tbeam_select(const smx_tbeam_args* a, void* stream);
 
+/* ---- The same search carried across streaming chunks ------------------------------------------------------------------
+ * A STREAM is one utterance's search in one batch slot, fed (n_1, n_2, ...) frames over successive chunk calls, each n_k in [0, C].
+ * After the call that delivers chunk k the slot's result is the result of the search above over the concatenation of the frames
+ * delivered so far - every field, `frames` counted over the whole stream - so after the last chunk it is smx_tbeam_init / _step /
+ * _select's result over the whole utterance, bit for bit.  The two entries take the struct above, read for ONE CHUNK: enc (B, C, J)
+ * with T = C, lengths (B) REQUIRED = the frames of this chunk per slot (clamped to [0, C]), frames (B) = the frame index inside the
+ * chunk (what smx_tbeam_step reads), U required as ever (a stream has no T to derive it from).  smx_tbeam_step and the LM step are
+ * used as they are.  What a stream needs beyond the struct - which stays 344 bytes - travels like this:
+ *   start          (B) bytes on the device, an extra argument of smx_tbeam_resume: nonzero = the slot begins a new stream;
+ *   stream_frames  (B) int32 on the device, an extra argument of both entries: the frames closed over the whole stream, the result's
+ *                  `frames` (the struct's `frames` restarts at 0 with every chunk);
+ *   the dead flag  the eighth, so far spare, counter of the slot's state block (0 after an init): set when the search ended on a row
+ *                  without numbers (overflow bit 2, an empty closed list).  smx_tbeam_state_bytes is what it was.
+ * smx_tbeam_resume:        one launch before a chunk's steps, one workgroup per slot.  start[b]: smx_tbeam_init's work for that row
+ *                          alone, stream_frames[b] = 0; with lengths[b] == 0 the slot reports the one empty hypothesis, score 0, and
+ *                          goes on from the staged [blank] when frames arrive.  Otherwise a dead slot, or one with lengths[b] == 0,
+ *                          is left exactly as it was.  Otherwise the slot is re-armed: frames[b] = 0, done[b] = 0 - nothing is
+ *                          picked again, the hypothesis staged at the pause is the one to expand.
+ * smx_tbeam_select_stream: smx_tbeam_select's kernel instantiated with a flag; one launch.  It differs where frames[b] reaches
+ *                          lengths[b]: the result is written as above (rows past n_hyps and tokens past out_len reset to their
+ *                          cleared values, the closed list left in insertion order), and then the ordinary frame end is done as
+ *                          well - the closed list becomes the open list of the next frame, prefixes written out, this expansion's
+ *                          state saved, the survivors' states copied to the other half, the next hypothesis picked and staged -
+ *                          and done[b] = 1: for a stream `done` means PAUSED.  An empty closed list ends the search as it does
+ *                          above and marks the slot dead.  Every frame end advances stream_frames[b] with frames[b].
+ * SMX_EINVAL: NULL start / stream_frames / lengths / state (or any pointer the selection needs), sizes < 1; SMX_EUNSUPPORTED as
+ * smx_tbeam_ok and the selection's LDS bound. */
+int smx_tbeam_resume(const smx_tbeam_args* a, const uint8_t* start, int32_t* stream_frames, void* stream);
+int smx_tbeam_select_stream(const smx_tbeam_args* a, int32_t* stream_frames, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -379,6 +379,8 @@ SIGNATURES = {
     "smx_tbeam_init": (c_i, [ctypes.POINTER(TbeamArgs), c_vp]),
     "smx_tbeam_step": (c_i, [ctypes.POINTER(TbeamArgs), c_vp]),
     "smx_tbeam_select": (c_i, [ctypes.POINTER(TbeamArgs), c_vp]),
+    "smx_tbeam_resume": (c_i, [ctypes.POINTER(TbeamArgs), c_vp, c_vp, c_vp]),
+    "smx_tbeam_select_stream": (c_i, [ctypes.POINTER(TbeamArgs), c_vp, c_vp]),
 }
 
 _lib = None

@@ -17,6 +17,8 @@
 // Lists, nodes, prefixes and state slots of an utterance live in one block of `state` (TbLayout below); every index read from it is
 // clamped to its capacity before use and every insert is checked against it.  No atomics, every sum in a fixed order, nothing
 // depends on B or on the other rows.
+// The same search carried across streaming chunks: tbeam_resume_kernel before a chunk's steps (a slot starts, sits out or
+// is re-armed) and tbeam_select_kernel<T, true>, which at a chunk's last frame writes the result AND does the frame end (done = paused).
 #include "lstm_tile.h"
 #include "row_scan.h"
 
@@ -41,7 +43,7 @@ template <> struct TbeamPad<bf16_t> { static constexpr int value = 8; };
 
 // ---- the per-utterance block of `state`, byte offsets (every section 16-byte aligned)
 struct TbLayout {
-  long meta;                 // int32[8]: nA, nB, nexp, half, cur_node, cur_len, cur_score (bits), -
+  long meta;                 // int32[8]: nA, nB, nexp, half, cur_node, cur_len, cur_score (bits), a stream's dead flag (0 after an init)
   long a_node, a_len, a_tok, a_score;      // NA entries each: the open list in insertion order, node -1 = removed
   long b_node, b_len, b_tok, b_score;      // W entries each: the closed list in insertion order
   long nd_parent, nd_tok;    // E W in-frame nodes: node W + e W + j is child j of expansion e
@@ -184,8 +186,11 @@ __device__ __forceinline__ void tb_walk(int node, int len, const int* nd_parent,
   rootlen = max(pos + 1, 0);
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void tbeam_select_kernel(smx_tbeam_args a, TbLayout L) {
+// STREAMED (smx_tbeam_select_stream): a.T / a.lengths / a.frames are those of one CHUNK and sframes counts the frames of
+// the whole stream.  The one difference is the frame end at the chunk's last frame: the result is written AND the ordinary turnover is
+// done, so that the next chunk goes on from the staged pick; done[b] then means paused.  Everything else is the code below, once.
+template <typename T, bool STREAMED>
+__global__ __launch_bounds__(256) void tbeam_select_kernel(smx_tbeam_args a, TbLayout L, int32_t* __restrict__ sframes) {
   extern __shared__ __attribute__((aligned(16))) char tbeam_lds[];
   __shared__ int B_node[TBEAM_W_MAX], B_len[TBEAM_W_MAX], B_tok[TBEAM_W_MAX], topk[TBEAM_W_MAX], w_root[TBEAM_W_MAX], w_rootlen[TBEAM_W_MAX],
       src_slot[TBEAM_W_MAX], order[TBEAM_W_MAX];
@@ -344,10 +349,29 @@ __global__ __launch_bounds__(256) void tbeam_select_kernel(smx_tbeam_args a, TbL
         const int n = min(w_rootlen[r], min(max(g_plen[half * W + w_root[r]], 0), U));
         for (int p = tid; p < n; p += 256) a.tokens[((long)b * a.nbest + r) * U + p] = src[p];
       }
-      if (tid == 0) {
-        a.n_hyps[b] = n_out; a.frames[b] = frame; a.overflow[b] = sh[OVF_] | (nB == 0 ? 4 : 0); a.done[b] = 1;
+      if constexpr (!STREAMED) {
+        if (tid == 0) {
+          a.n_hyps[b] = n_out; a.frames[b] = frame; a.overflow[b] = sh[OVF_] | (nB == 0 ? 4 : 0); a.done[b] = 1;
+        }
+        return;
+      } else {
+        // a pause: an earlier pause's result lies in the buffers, so what this one does not write goes back to its cleared value
+        // (order[] and B_len[] are as the sort left them; the positions written above and those padded here are disjoint)
+        for (long i = tid; i < (long)a.nbest * U; i += 256) {
+          const int r = (int)(i / U), p = (int)(i - (long)r * U);
+          if (p >= (r < n_out ? min(B_len[order[r]] - 1, U) : 0)) a.tokens[(long)b * a.nbest * U + i] = -1;
+        }
+        for (int r = n_out + tid; r < a.nbest; r += 256) {
+          a.out_len[(long)b * a.nbest + r] = 0; a.scores[(long)b * a.nbest + r] = NEG_INF; a.sums[(long)b * a.nbest + r] = NEG_INF;
+        }
+        if (tid == 0) { a.n_hyps[b] = n_out; a.done[b] = 1; }
+        if (nB == 0) {                                                        // nothing to go on from: the slot is dead until started again
+          if (tid == 0) { a.frames[b] = frame; sframes[b] += 1; a.overflow[b] = sh[OVF_] | 4; meta[7] = 1; }
+          return;
+        }
+        if (tid < nB && B_node[tid] < 0) B_node[tid] = -1 - B_node[tid];      // the sort's marks off: the turnover reads the nodes
+        __syncthreads();
       }
-      return;
     }
     // the survivors become the roots of the next frame: prefixes materialised and states copied into the other half
     new_half = half ^ 1;
@@ -368,7 +392,10 @@ __global__ __launch_bounds__(256) void tbeam_select_kernel(smx_tbeam_args a, TbL
     }
     __syncthreads();
     nA = nB; nB = 0;
-    if (tid == 0) a.frames[b] = frame;
+    if (tid == 0) {
+      a.frames[b] = frame;
+      if constexpr (STREAMED) sframes[b] += 1;
+    }
     ia = tb_pick(A_node, A_len, A_score, nA, pv, pi);
     ia = min(ia, nA - 1);                                                     // (nA >= 1 here; a list of NaN keys takes its last)
   }
@@ -423,8 +450,8 @@ __global__ __launch_bounds__(256) void tbeam_select_kernel(smx_tbeam_args a, TbL
 
 // ---- the start of a search: every utterance holds the one hypothesis [blank] with zero states, already picked for step 0
 template <typename T>
-__global__ __launch_bounds__(256) void tbeam_init_kernel(smx_tbeam_args a, TbLayout L) {
-  const int b = blockIdx.x, tid = threadIdx.x;
+__device__ __forceinline__ void tb_init_row(const smx_tbeam_args& a, const TbLayout& L, int b) {
+  const int tid = threadIdx.x;
   char* st = reinterpret_cast<char*>(a.state) + (long)b * L.total;
   const long es = sizeof(T), H = a.H, Hl = a.lm_H, Lc = a.lm_L;
   const uint4 zero = {0u, 0u, 0u, 0u};
@@ -458,6 +485,29 @@ __global__ __launch_bounds__(256) void tbeam_init_kernel(smx_tbeam_args a, TbLay
       a.done[b] = 0;
     }
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void tbeam_init_kernel(smx_tbeam_args a, TbLayout L) {
+  tb_init_row<T>(a, L, blockIdx.x);
+}
+
+// ---- the start of a chunk of a stream: a slot marked `start` is initialised as above, for its own row; a slot that is
+// dead (meta[7]) or gets no frame is left as it was; any other is re-armed - the hypothesis staged at the pause is the one to expand
+template <typename T>
+__global__ __launch_bounds__(256) void tbeam_resume_kernel(smx_tbeam_args a, TbLayout L, const uint8_t* __restrict__ start, int32_t* __restrict__ sframes) {
+  const int b = blockIdx.x;
+  if (start[b]) {
+    tb_init_row<T>(a, L, b);
+    if (threadIdx.x == 0) sframes[b] = 0;
+    return;
+  }
+  if (threadIdx.x != 0) return;
+  const int len_b = min(max(a.lengths[b], 0), a.T);
+  const int dead = reinterpret_cast<const int*>(reinterpret_cast<const char*>(a.state) + (long)b * L.total + L.meta)[7];
+  if (dead || len_b == 0) return;
+  a.frames[b] = 0;
+  a.done[b] = 0;
 }
 
 }  // namespace smx
@@ -539,16 +589,49 @@ extern "C" int smx_tbeam_step(const smx_tbeam_args* a, void* stream) {
   return check_launch("smx_tbeam_step");
 }
 
-extern "C" int smx_tbeam_select(const smx_tbeam_args* a, void* stream) {
+template <bool STREAMED>
+static int tbeam_select_launch(const char* what, const smx_tbeam_args* a, int32_t* stream_frames, void* stream) {
   TbLayout L;
-  const int rc = tbeam_check("smx_tbeam_select", a, &L);
+  const int rc = tbeam_check(what, a, &L);
   if (rc != SMX_OK) return rc;
-  SMX_REQUIRE((a->lm_L > 0) == (a->lm_logits != nullptr) && (!a->lm_logits || a->ld_lm >= a->V), "smx_tbeam_select: lm_logits (ld_lm >= V) if and only if lm_L > 0");
-  if (a->lm_logits && (reinterpret_cast<uintptr_t>(a->lm_logits) & 3u)) return fail(SMX_EUNSUPPORTED, "smx_tbeam_select: lm_logits must be 4-byte aligned");
+  SMX_REQUIRE((a->lm_L > 0) == (a->lm_logits != nullptr) && (!a->lm_logits || a->ld_lm >= a->V), "%s: lm_logits (ld_lm >= V) if and only if lm_L > 0", what);
+  if (a->lm_logits && (reinterpret_cast<uintptr_t>(a->lm_logits) & 3u)) return fail(SMX_EUNSUPPORTED, "%s: lm_logits must be 4-byte aligned", what);
   const size_t lds = tbeam_select_lds(a->V, a->W, a->E);
   dispatch_dtype(a->dtype, [&](auto tag) {
     using E = decltype(tag);
-    hipLaunchKernelGGL(tbeam_select_kernel<E>, dim3(a->B), dim3(256), lds, STREAM, *a, L);
+    hipLaunchKernelGGL((tbeam_select_kernel<E, STREAMED>), dim3(a->B), dim3(256), lds, STREAM, *a, L, stream_frames);
   });
-  return check_launch("smx_tbeam_select");
+  return check_launch(what);
+}
+
+extern "C" int smx_tbeam_select(const smx_tbeam_args* a, void* stream) {
+  return tbeam_select_launch<false>("smx_tbeam_select", a, nullptr, stream);
+}
+
+// a stream's entries read `lengths` and `stream_frames` on the device: both must be there (checked before tbeam_check, which allows
+// lengths == NULL for the whole search)
+static int tbeam_stream_check(const char* what, const smx_tbeam_args* a, const int32_t* stream_frames) {
+  SMX_REQUIRE(a, "%s: null argument struct", what);
+  SMX_REQUIRE(a->lengths && stream_frames && a->state, "%s: a stream needs lengths (the chunk's frames per slot), stream_frames and state", what);
+  return SMX_OK;
+}
+
+extern "C" int smx_tbeam_select_stream(const smx_tbeam_args* a, int32_t* stream_frames, void* stream) {
+  const int rc = tbeam_stream_check("smx_tbeam_select_stream", a, stream_frames);
+  if (rc != SMX_OK) return rc;
+  return tbeam_select_launch<true>("smx_tbeam_select_stream", a, stream_frames, stream);
+}
+
+extern "C" int smx_tbeam_resume(const smx_tbeam_args* a, const uint8_t* start, int32_t* stream_frames, void* stream) {
+  int rc = tbeam_stream_check("smx_tbeam_resume", a, stream_frames);
+  if (rc != SMX_OK) return rc;
+  SMX_REQUIRE(start, "smx_tbeam_resume: null start vector");
+  TbLayout L;
+  rc = tbeam_check("smx_tbeam_resume", a, &L);
+  if (rc != SMX_OK) return rc;
+  dispatch_dtype(a->dtype, [&](auto tag) {
+    using E = decltype(tag);
+    hipLaunchKernelGGL(tbeam_resume_kernel<E>, dim3(a->B), dim3(256), 0, STREAM, *a, L, start, stream_frames);
+  });
+  return check_launch("smx_tbeam_resume");
 }

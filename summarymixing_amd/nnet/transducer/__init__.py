@@ -11,13 +11,14 @@ from ... import _lib as L
 from ... import functional as F
 from ... import ops
 from ..losses import TRANSDUCER_REDUCTIONS, reduce_transducer, transducer_lengths
-from .beam import CapturedTransducerBeam, TransducerBeamResult, beam_decode
+from .beam import CapturedTransducerBeam, TransducerBeamResult, TransducerBeamStream, beam_decode
 from .greedy import CapturedGreedy, GreedyResult, GreedyState, greedy_decode
 from .prediction_network import prediction_network, prediction_network_masks
 from .transducer_joint import Transducer_joint, joint_inputs
 
 __all__ = ["Transducer_joint", "transducer_joint_loss", "prediction_network", "prediction_network_masks", "greedy_decode",
-           "CapturedGreedy", "GreedyState", "GreedyResult", "beam_decode", "CapturedTransducerBeam", "TransducerBeamResult"]
+           "CapturedGreedy", "GreedyState", "GreedyResult", "beam_decode", "CapturedTransducerBeam", "TransducerBeamResult",
+           "TransducerBeamStream"]
 
 # lattice rows per backward group (whole utterances; at least one): bounds the live dz / dH slices
 _BWD_GROUP_ROWS = 49152

@@ -13,7 +13,8 @@ current best open hypothesis of every utterance that is not done.  One step is a
 - so ``beam_decode`` loops over them and reads the ``done`` vector (B bytes) every ``poll_every`` steps, its only synchronisation, and
 ``CapturedTransducerBeam`` captures ONE step as a graph - a plain chain, no parallel branches - and replays it in the same loop.  A
 search takes at most T * max_expansions steps.  No atomics, fixed summation orders: two runs agree bit for bit, and an utterance's
-result does not depend on B or on the other rows.  GPU only."""
+result does not depend on B or on the other rows.  ``TransducerBeamStream`` carries the search across streaming chunks, one stream per
+batch slot: smx_tbeam_resume before a chunk's steps and smx_tbeam_select_stream in place of the selection.  GPU only."""
 from typing import NamedTuple, Optional
 
 import torch
@@ -76,14 +77,16 @@ class TransducerBeamState:
             self.lengths.copy_(lengths.to(self.enc.device).clamp(0, T).to(torch.int32))
         ops.tbeam_init(self)
 
+    _select = staticmethod(ops.tbeam_select)
+
     def step(self):
         """The launches of one expansion on the current stream."""
         ops.tbeam_step(self)
         if self.lm is None:
-            ops.tbeam_select(self)
+            self._select(self)
         else:
             logits, _ = self.lm.step(self.cur_tok, hx=(self.lm_h_in, self.lm_c_in), out=(self.lm_h_out, self.lm_c_out))
-            ops.tbeam_select(self, logits)
+            self._select(self, logits)
 
     def max_steps(self):
         return self.enc.shape[1] * self.E
@@ -109,7 +112,7 @@ def _check_lm(lm, lm_weight, V, dtype):
 
 
 def _make_state(enc_like, emb, dec, proj_dec, tjoint, transducer_lin, beam_size, nbest, lm, lm_weight, state_beam, expand_beam, max_expansions,
-                max_symbols):
+                max_symbols, cls=TransducerBeamState):
     w = _weights(enc_like, emb, dec, proj_dec, tjoint, transducer_lin)
     B, T, J = enc_like.shape
     H, V = dec.hidden_size, emb.num_embeddings
@@ -121,8 +124,8 @@ def _make_state(enc_like, emb, dec, proj_dec, tjoint, transducer_lin, beam_size,
     if T < 1:
         raise ValueError("transducer beam search: no frames")
     lm = _check_lm(lm, lm_weight, V, enc_like.dtype)
-    return TransducerBeamState(w, B, T, J, H, V, enc_like.dtype, enc_like.device, beam_size, nbest, lm, lm_weight if lm is not None else 0.0,
-                               state_beam, expand_beam, max_expansions, max_symbols)
+    return cls(w, B, T, J, H, V, enc_like.dtype, enc_like.device, beam_size, nbest, lm, lm_weight if lm is not None else 0.0, state_beam,
+               expand_beam, max_expansions, max_symbols)
 
 
 def _poll_loop(step, st, poll_every):
@@ -185,4 +188,96 @@ class CapturedTransducerBeam:
             raise RuntimeError(ops.NO_CPU)
         st.begin(enc, lengths)
         _poll_loop(self.graph.replay, st, poll_every)
+        return st.result()
+
+
+class TransducerBeamStreamState(TransducerBeamState):
+    """The buffers of B streams fed chunk by chunk: ``enc`` / ``lengths`` / ``frames`` are those of ONE chunk of T = C
+    frames, ``start`` marks the slots that begin a new stream and ``stream_frames`` counts the frames of the whole stream - the result's
+    ``frames``.  ``done`` means paused; a slot that was never started is paused."""
+
+    _select = staticmethod(ops.tbeam_select_stream)
+
+    def __init__(self, *args):
+        super().__init__(*args)
+        B, device = self.enc.shape[0], self.enc.device
+        self.start = torch.zeros((B,), dtype=torch.uint8, device=device)
+        self.stream_frames = torch.zeros((B,), dtype=torch.int32, device=device)
+        self.done.fill_(1)
+
+    def result(self):
+        return TransducerBeamResult(self.tokens, self.out_len, self.scores, self.sums, self.n_hyps, self.overflow, self.expansions,
+                                    self.stream_frames)
+
+
+class TransducerBeamStream:
+    """The beam search of B independent streams, one per batch slot, fed in chunks of at most ``chunk_frames`` frames: after every
+    ``decode_chunk`` a slot's result is exactly ``beam_decode``'s over the frames it has been given so far - every field, bit for bit, with
+    the same caps - so after the last chunk it is the whole utterance's.  A chunk's last frame writes the result AND
+    does the ordinary frame end, so the next chunk goes on from the hypothesis staged there; nothing is recomputed.  ``max_symbols`` has
+    no default: a stream has no T to derive it from.  ``captured=True`` captures ONE step as a graph (a plain chain on one stream) and
+    replays it in the polling loop; the weight images are then those of the capture.  The returned tensors are views of the buffers:
+    clone what must outlive the next call."""
+
+    def __init__(self, emb, dec, proj_dec, tjoint, transducer_lin, B, chunk_frames, beam_size, max_symbols, nbest=1, lm=None, lm_weight=0.0,
+                 state_beam=2.3, expand_beam=2.3, max_expansions=None, dtype=torch.float32, device=None, captured=False):
+        if max_symbols is None:
+            raise ValueError("TransducerBeamStream: max_symbols is required (a stream has no length to derive it from)")
+        device = device or transducer_lin.w.weight.device
+        J = transducer_lin.w.weight.shape[1]
+        self.B, self.chunk_frames = int(B), int(chunk_frames)
+        with torch.no_grad():
+            like = torch.zeros((self.B, self.chunk_frames, J), dtype=dtype, device=device)
+            self.state = _make_state(like, emb, dec, proj_dec, tjoint, transducer_lin, beam_size, nbest, lm, lm_weight, state_beam, expand_beam,
+                                     max_expansions, max_symbols, cls=TransducerBeamStreamState)
+            self._step = self.state.step
+            if captured:
+                # every slot is paused, so the warm-up and the captured step select nothing and leave the search state as it is
+                s = torch.cuda.Stream(device=device)
+                s.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(s):
+                    self.state.step()                         # warm-up: weight casts exist before the capture
+                torch.cuda.current_stream().wait_stream(s)
+                self.graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self.graph, stream=s):
+                    self.state.step()
+                self._step = self.graph.replay
+        self._started = [False] * self.B
+        self._calls = 0
+
+    def _check(self, enc, lengths, start):
+        st, B, C = self.state, self.B, self.chunk_frames
+        if tuple(enc.shape) != tuple(st.enc.shape) or enc.dtype != st.enc.dtype or enc.device != st.enc.device:
+            raise ValueError(f"TransducerBeamStream: made for chunks {tuple(st.enc.shape)} {st.enc.dtype} on {st.enc.device}, got "
+                             f"{tuple(enc.shape)} {enc.dtype} on {enc.device}")
+        lengths = [C] * B if lengths is None else [int(n) for n in lengths]
+        start = [self._calls == 0] * B if start is None else [bool(s) for s in start]
+        if len(lengths) != B or len(start) != B:
+            raise ValueError(f"TransducerBeamStream: lengths and start hold one entry per slot ({B}), got {len(lengths)} and {len(start)}")
+        if any(n < 0 or n > C for n in lengths):
+            raise ValueError(f"TransducerBeamStream: lengths {lengths} outside [0, chunk_frames = {C}]")
+        never = [b for b in range(B) if lengths[b] > 0 and not (start[b] or self._started[b])]
+        if never:
+            raise ValueError(f"TransducerBeamStream: frames for slots {never}, which were never started (start[b] = True begins a stream)")
+        return lengths, start
+
+    @torch.no_grad()
+    def decode_chunk(self, enc, lengths=None, start=None, poll_every=32) -> TransducerBeamResult:
+        """enc (B, C, J): one chunk of the encoder output AFTER proj_enc; rows at and beyond lengths[b] may hold anything.  lengths: B host
+        ints in [0, C], the frames of this chunk per slot, None: all C.  start: B host bools, the slots that begin a new stream with
+        this chunk, None: all on the first call and none afterwards.  A slot with 0 frames that is not started is left exactly as it
+        was; a slot whose search ended on a row without numbers (overflow bit 2) ignores frames until it is started again."""
+        lengths, start = self._check(enc, lengths, start)
+        st = self.state
+        st.enc.copy_(enc)
+        st.lengths.copy_(torch.tensor(lengths, dtype=torch.int32))
+        st.start.copy_(torch.tensor(start, dtype=torch.uint8))
+        self._started = [a or b for a, b in zip(self._started, start)]
+        self._calls += 1
+        ops.tbeam_resume(st)
+        n = max(lengths) * st.E                               # a frame takes at most max_expansions steps
+        for i in range(n):
+            self._step()
+            if poll_every and (i + 1) % poll_every == 0 and i + 1 < n and bool(st.done.all()):
+                break
         return st.result()

@@ -1986,3 +1986,26 @@ def tbeam_step(st):
 def tbeam_select(st, lm_logits=None):
     """The selection of one expansion (smx_tbeam_select) over st.z and, with an LM, its logits (B, V) for cur_tok.  One launch."""
     L.check(L.lib().smx_tbeam_select(ctypes.byref(_tbeam_args(st, lm_logits)), _stream()), "smx_tbeam_select")
+
+
+# ---- the same search carried across streaming chunks (DESIGN.md §I.27).  st: a nnet.transducer.beam.TransducerBeamStreamState - st.enc
+# holds ONE chunk (B, C, J), st.lengths the chunk's frames per slot, st.frames the frame inside the chunk, and two more device vectors:
+# st.start (B) uint8 and st.stream_frames (B) int32, the frames closed over the whole stream.
+def _tbeam_stream_vec(st, name, dtype):
+    t = getattr(st, name)
+    assert t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == (st.enc.shape[0],), f"tbeam: {name} must be {dtype} (B,)"
+    return t.data_ptr()
+
+
+def tbeam_resume(st):
+    """The start of a chunk (smx_tbeam_resume): slots with st.start set begin a new stream (smx_tbeam_init's work for that row), dead slots
+    and slots without frames in this chunk are left as they were, the others are re-armed at the hypothesis staged at the pause."""
+    L.check(L.lib().smx_tbeam_resume(ctypes.byref(_tbeam_args(st)), _tbeam_stream_vec(st, "start", torch.uint8),
+                                     _tbeam_stream_vec(st, "stream_frames", torch.int32), _stream()), "smx_tbeam_resume")
+
+
+def tbeam_select_stream(st, lm_logits=None):
+    """smx_tbeam_select for a stream (smx_tbeam_select_stream): at a chunk's last frame the result is written AND the frame end is done,
+    done[b] = 1 meaning paused.  One launch."""
+    L.check(L.lib().smx_tbeam_select_stream(ctypes.byref(_tbeam_args(st, lm_logits)), _tbeam_stream_vec(st, "stream_frames", torch.int32),
+                                            _stream()), "smx_tbeam_select_stream")
