@@ -316,19 +316,23 @@ __global__ __launch_bounds__(256) void chunk_window_kernel(const float* csum, T*
 // =================================================================================================
 constexpr int ED_CH = 16;                                // rows per chunk
 
+// 1 - gamma^n is formed as -expm1f(n ln gamma): 2 - gamma^(t+1) - gamma^(T-t) loses every digit the powers share with 1 (at the
+// recipe's gamma = 0.995 and T = 1 the denominator came out 3.6e-5 off, 1.5e-5 at T = 2, 8.8e-6 at T = 3 - the first frames of a short
+// utterance or streaming chunk).  lng = ln gamma comes from the host (rounded once from double): the relative error of the small
+// differences is that of lng, and the device's fast logf is only absolutely accurate near 1.
 __device__ __forceinline__ float ed_inv_den(int t, int T_, float lng, float inv1mg) {
-  const float den = (2.f - expf((float)(t + 1) * lng) - expf((float)(T_ - t) * lng)) * inv1mg - 1.f;
+  const float den = (-expm1f((float)(t + 1) * lng) - expm1f((float)(T_ - t) * lng)) * inv1mg - 1.f;
   return 1.f / den;
 }
 
 // grid (DC, ceil(NC/4), B); a wave owns one chunk; lane owns 4 columns.  ws[b][c][0][D] = F_c, ws[b][c][1][D] = G_c
 template <typename T>
 __global__ __launch_bounds__(256) void expdecay_chunk_kernel(const T* __restrict__ X, long ldx, float* __restrict__ ws,
-                                                             int T_, int D, int NC, float gamma, int mode, int t_off, int T_glob) {
+                                                             int T_, int D, int NC, float gamma, float lng, int mode, int t_off, int T_glob) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, b = blockIdx.z;
   const int c = blockIdx.y * 4 + w, col = (blockIdx.x * 64 + lane) * 4;
   if (c >= NC || col >= D) return;
-  const float lng = logf(gamma), inv1mg = 1.f / (1.f - gamma);
+  const float inv1mg = 1.f / (1.f - gamma);
   const int t0 = c * ED_CH;
   float F[4] = {0.f, 0.f, 0.f, 0.f}, G[4] = {0.f, 0.f, 0.f, 0.f};
   float v[ED_CH][4];
@@ -406,11 +410,11 @@ __global__ __launch_bounds__(256) void expdecay_carry_kernel(float* __restrict__
 template <typename T>
 __global__ __launch_bounds__(256) void expdecay_apply_kernel(const T* __restrict__ X, long ldx, const float* __restrict__ ws,
                                                              T* __restrict__ Y, long ldy, int T_, int D, int NC, float gamma,
-                                                             int mode, int t_off, int T_glob) {
+                                                             float lng, int mode, int t_off, int T_glob) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, b = blockIdx.z;
   const int c = blockIdx.y * 4 + w, col = (blockIdx.x * 64 + lane) * 4;
   if (c >= NC || col >= D) return;
-  const float lng = logf(gamma), inv1mg = 1.f / (1.f - gamma);
+  const float inv1mg = 1.f / (1.f - gamma);
   const int t0 = c * ED_CH;
   float v[ED_CH][4], a[ED_CH][4];
 #pragma unroll
@@ -1066,12 +1070,13 @@ static int expdecay_impl(const void* X, int64_t ldx, void* Y, int64_t ldy, int B
   dim3 grid((D + 255) / 256, (NC + 3) / 4, B);
   const dim3 gc((unsigned)(((long)B * D + 255) / 256));
   float* w = reinterpret_cast<float*>(ws);
-  if (phase & 1) hipLaunchKernelGGL((expdecay_chunk_kernel<T>), grid, dim3(256), 0, s, (const T*)X, ldx, w, T_, D, NC, gamma, mode, t_off, T_glob);
+  const float lng = (float)log((double)gamma);             // (ed_inv_den: the denominators are as accurate as this logarithm)
+  if (phase & 1) hipLaunchKernelGGL((expdecay_chunk_kernel<T>), grid, dim3(256), 0, s, (const T*)X, ldx, w, T_, D, NC, gamma, lng, mode, t_off, T_glob);
   if (phase == 1) hipLaunchKernelGGL(expdecay_carry_kernel, gc, dim3(256), 0, s, w, D, NC, B, gamma, (const float*)nullptr, (const float*)nullptr, ends, T_);
   if (phase & 2) {
     const float* fin = phase == 2 ? ends : nullptr;
     hipLaunchKernelGGL(expdecay_carry_kernel, gc, dim3(256), 0, s, w, D, NC, B, gamma, fin, fin ? fin + (long)B * D : nullptr, (float*)nullptr, T_);
-    hipLaunchKernelGGL((expdecay_apply_kernel<T>), grid, dim3(256), 0, s, (const T*)X, ldx, w, (T*)Y, ldy, T_, D, NC, gamma, mode, t_off, T_glob);
+    hipLaunchKernelGGL((expdecay_apply_kernel<T>), grid, dim3(256), 0, s, (const T*)X, ldx, w, (T*)Y, ldy, T_, D, NC, gamma, lng, mode, t_off, T_glob);
   }
   return check_launch("smx_expdecay_mean");
 }
